@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """bench.py -- diffusion-steps/s of the posterior-sampling hot path on MI355X (contract: see the round prompt).
 
-    python bench.py --gpus N --steps K --warmup W          (N > 1 without a launcher: re-executes itself under torch.distributed.run)
+    python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
+                                                (N > 1 without a launcher: runs itself under torch.distributed.run, as a child)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
 A "step" is one iteration of VPSDE.sample's loop (sda/score.py:250-261): 1 predictor + C corrector score
@@ -16,8 +17,12 @@ Synthetic score net: a raw random-init net makes the *reference itself* overflow
 item 5), so the timed noise estimator is eps(x,t) = sigma x/(mu^2+sigma^2) + 0.1 * UNet(x,t): the exact estimator for
 N(0,I) data plus the full U-Net, which still runs (forward and VJP) at every evaluation.
 
-Rank 0 prints ONE JSON line with `roofline` and `cpu_baseline` (the CPU oracle timed on this box's host cores on a bounded
-sample of the same workload; N=1 only).
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times `--steps` steps and prints the headline (`value`,
+`ms_per_step`, ...); everything else it can measure runs only with `--full`, after the timed region: `roofline` (per-kernel
+HIP-event timings of extra eager steps), `opt_in_f16x2` (the same step on the opt-in multiply), `other_configs` (every other
+BASELINE configuration, bounded) and `cpu_baseline` (the CPU oracle timed on the host cores on a bounded sample of the same
+workload; N=1 only).  `--dump-outputs DIR` writes what the timed steps computed (the gathered samples after the last timed
+step) as DIR/<name>.npy; the inputs are seeded, so two builds run with the same arguments can be compared output for output.
 
 roofline: the dominant kernel is the Winograd F(2x2,3x3) convolution (conv_wino4_kernel; ~85 % of a step).  It is
 MFMA-bound, and what it ISSUES is 1/2.25 of the algorithmic (direct-convolution) flops, so
@@ -26,7 +31,8 @@ MFMA-bound, and what it ISSUES is 1/2.25 of the algorithmic (direct-convolution)
 with the direct-equivalent figure, the other kernel families (direct implicit GEMM: TFLOP/s vs the same peak; LayerNorm:
 GB/s vs 8 TB/s) and their shares of the step alongside in `roofline.families`.  The step is replayed from a captured hipGraph
 in the timed region (`--graph 1`, default); the per-kernel HIP-event timings come from `--profile-steps` extra EAGER steps run
-after it (events cannot bracket launches inside a graph replay) -- same kernels, same shapes, outside `value`.
+after it (events cannot bracket launches inside a graph replay) -- same kernels, same shapes, outside `value`.  With `--graph 0
+--full` the events bracket the timed launches themselves.
 """
 import argparse
 import json
@@ -388,7 +394,7 @@ def run_lorenz_eval(args, device):
     for _ in range(max(args.warmup, 1)):
         wu.step()
     torch.cuda.synchronize(device)
-    runs, loop_s, setup_s, finite, note = {}, 0.0, 0.0, True, None
+    runs, loop_s, setup_s, finite, note, results = {}, 0.0, 0.0, True, None, {}
     torch.manual_seed(1)
     for C in (0, 1, 2, 4, 8, 16):
         t0 = time.perf_counter()
@@ -408,6 +414,8 @@ def run_lorenz_eval(args, device):
         t2 = time.perf_counter()
         ok = bool(torch.isfinite(sampler.result()).all().item())
         finite = finite and ok
+        if args.dump_outputs:
+            results[f'x_C{C}'] = sampler.result()
         runs[str(C)] = {'sample_s': t2 - t1, 'setup_s': t1 - t0, 'ms_per_step': (t2 - t1) / steps * 1e3,
                         'ms_per_score_eval': (t2 - t1) / steps / (1 + C) * 1e3, 'finite': ok}
         loop_s += t2 - t1
@@ -430,7 +438,9 @@ def run_lorenz_eval(args, device):
            'ms_per_score_eval_all_runs': loop_s / (steps * 37) * 1e3}
     if os.environ.get('SDA_HIP_LIB'):
         out['kernel_library_override'] = os.environ['SDA_HIP_LIB']
-    if not args.no_cpu_baseline:
+    if args.dump_outputs:
+        out['outputs_dumped'] = dump_outputs(args.dump_outputs, results)
+    if args.full and not args.no_cpu_baseline:
         out['cpu_baseline'] = lorenz_eval_cpu(args, step, std, B, L, S, steps)
         out['gpu_over_cpu'] = out['value'] / out['cpu_baseline']['value']
     print(json.dumps(out), flush=True)
@@ -504,6 +514,40 @@ def rank_inputs(wl, event, scaling, rank, world):
         gen.manual_seed((1 * 1000003 + i) & 0x7fffffffffffffff)
         rows.append(torch.randn(tuple(event), generator=gen))
     return y, torch.stack(rows)
+
+
+DUMP_BUDGET = 64 << 20           # bytes --dump-outputs writes, in all
+DUMP_SAMPLE = 1 << 22            # elements kept of an output too large to write whole
+
+
+def dump_outputs(out_dir, arrays):
+    """`--dump-outputs DIR`: the arrays the timed path hands its caller, as DIR/<name>.npy (float32; float64 for the row sums and
+    indices).  An array over its share of DUMP_BUDGET is written as a fixed sample of its elements -- <name>_sample.npy at the flat
+    indices of <name>_sample_index.npy, drawn from a fixed seed, so every run keeps the same ones -- plus <name>_row_sum.npy and
+    <name>_row_sumsq.npy, float64 sums over every element of each row (trajectory).  Returns {file name: shape}."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    files = {}
+
+    def save(name, t):
+        a = t.detach().cpu().numpy()
+        np.save(os.path.join(out_dir, name + '.npy'), a)
+        files[name + '.npy'] = list(a.shape)
+
+    share = DUMP_BUDGET // max(1, len(arrays)) - 4 * 4096             # (room for the .npy headers)
+    for name, t in arrays.items():
+        t = t.detach()
+        if t.numel() * 4 <= share:
+            save(name, t.float())
+            continue
+        rows = t.reshape(t.shape[0], -1)
+        n = min(DUMP_SAMPLE, (share - 16 * rows.shape[0]) // 12)           # 4 B per value + 8 B per index
+        idx = torch.randint(t.numel(), (n,), generator=torch.Generator().manual_seed(0)).unique()
+        save(name + '_sample', t.reshape(-1)[idx.to(t.device)].float())
+        save(name + '_sample_index', idx.double())
+        save(name + '_row_sum', rows.sum(dim=1, dtype=torch.float64))
+        save(name + '_row_sumsq', torch.stack([r.double().square().sum() for r in rows]))
+    return files
 
 
 def launch_plan(gpus, env, argv):
@@ -663,8 +707,8 @@ def main():
     ap.add_argument('--cpu-seconds', type=float, default=20.0, help='timed CPU steps continue past the minimum of 3 while under this budget')
     ap.add_argument('--cpu-windows', type=int, default=1, help='trajectory windows of the CPU sample (Kolmogorov workloads)')
     ap.add_argument('--cpu-threads', type=int, default=0, help='0 = calibrate: fastest of 16..128 threads on one score evaluation of the sample')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-profile', action='store_true')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='--full without cpu_baseline')
+    ap.add_argument('--no-profile', action='store_true', help='--full without roofline and the clock probe')
     ap.add_argument('--graph', type=int, default=1, help='1 (default): replay each step from a captured hipGraph')
     ap.add_argument('--profile-steps', type=int, default=1, help='extra eager steps (outside the timed region) for the per-kernel HIP-event timings when --graph 1')
     ap.add_argument('--scaling', default='weak', choices=['weak', 'strong'], help="weak: every rank owns a configuration shard (N = 8 is the configuration itself); strong: the 8-shard global batch is split over the ranks")
@@ -674,28 +718,36 @@ def main():
                     help="f32 (default, the headline): fp32 MFMAs.  f16x2 (OPT-IN second line): the block convolutions multiply on the f16 matrix "
                          "cores, every fp32 operand as two halves, three products, fp32 accumulation (csrc/conv_h2.hip)")
     ap.add_argument('--second-line', type=int, default=1,
-                    help="1 (default; N = 1, Kolmogorov-shaped workloads, --multiply f32): after the f32 headline, time the same step with "
+                    help="1 (default; --full, N = 1, Kolmogorov-shaped workloads, --multiply f32): after the f32 headline, time the same step with "
                          "--multiply f16x2 and report it as the `opt_in_f16x2` object of the same JSON line (never `value`)")
     ap.add_argument('--second-steps', type=int, default=8)
     ap.add_argument('--second-warmup', type=int, default=1)
     ap.add_argument('--other-configs', type=int, default=-1,
                     help="1: add the bounded `other_configs` object (every other BASELINE configuration + the reference's default-width net, "
-                         "<= ~60 s in total) to the line; default: on for the default workload at N = 1, off otherwise")
+                         "<= ~60 s in total) to the line; default: on for the default workload at N = 1, off otherwise (--full only)")
     ap.add_argument('--force-pg', type=int, default=0,
                     help="1: initialise the process group (and issue the final all-gather through it) even at WORLD_SIZE = 1 -- first contact "
                          "of RCCL, the HSA IPC setting and libsda_hip.so in one process on a 1-GPU box (tests/test_gpu_rccl.py)")
     ap.add_argument('--backend', default='nccl', help="torch.distributed backend ('nccl' = RCCL; 'gloo' only to exercise the launch path on a 1-GPU box)")
+    ap.add_argument('--full', action='store_true',
+                    help='also measure everything beyond the headline, after the timed region: roofline (+ clock probe), opt_in_f16x2, '
+                         'other_configs, cpu_baseline (each still subject to its own switch above).  Off: set up, warm up, time the '
+                         'steps, dump the outputs if asked, print the line')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write what the timed steps computed (the samples after the last timed step) as DIR/<name>.npy, <= 64 MB in all')
     args = ap.parse_args()
 
     # (the host driver of this pool only supports dmabuf IPC: without this RCCL's hipIpcGetMemHandle fails; normally exported already)
     os.environ.setdefault('HSA_ENABLE_IPC_MODE_LEGACY', '0')
     plan = launch_plan(args.gpus, os.environ, sys.argv[1:])
     if plan is not None:
-        # `python bench.py --gpus N` (the driver's verbatim call, no torchrun): this process becomes the launcher of N ranks
+        # `python bench.py --gpus N` (the driver's verbatim call, no torchrun): this process becomes the launcher of N ranks, in a
+        # child process, and exits with its status
         if args.backend == 'nccl' and torch.cuda.device_count() < args.gpus:
             sys.exit(f'bench.py: --gpus {args.gpus} with backend nccl (RCCL) needs {args.gpus} visible GPUs, found '
                      f'{torch.cuda.device_count()} (one rank per GPU; `--backend gloo` only exercises the launch path on a smaller box)')
-        os.execv(sys.executable, plan)
+        import subprocess
+        sys.exit(subprocess.call(plan))
 
     world = int(os.environ.get('WORLD_SIZE', '1'))
     rank = int(os.environ.get('RANK', '0'))
@@ -729,6 +781,7 @@ def main():
     wl = dict(WORKLOADS[args.workload])
     if args.per_gpu:
         wl['per_gpu'] = args.per_gpu
+    schedule_steps = max(1000, args.warmup + args.steps)     # (the reference's 1000-step schedule unless more steps are asked for)
     b, global_batch, lo = partition(wl['per_gpu'], args.scaling, rank, world)
     net, event, A = build_model(wl, device)
     score = SyntheticScore(net)
@@ -740,7 +793,7 @@ def main():
     sde.initial_noise = x_init
     if args.corrections > 0:
         sde.noise_source = parallel.KeyedNoise((lo, lo + b), event, 2, args.corrections, device)
-    sampler = sde.sampler((b,), steps=1000, corrections=args.corrections, tau=args.tau)
+    sampler = sde.sampler((b,), steps=schedule_steps, corrections=args.corrections, tau=args.tau)
 
     def sync():
         torch.cuda.synchronize(device)
@@ -756,17 +809,18 @@ def main():
             graph_note = f'capture failed, ran eagerly: {type(e).__name__}: {str(e)[:200]}'
             args.graph = 0
             torch.cuda.synchronize(device)
-            sampler = sde.sampler((b,), steps=1000, corrections=args.corrections, tau=args.tau)
+            sampler = sde.sampler((b,), steps=schedule_steps, corrections=args.corrections, tau=args.tau)
     for _ in range(args.warmup):
         sampler.step()
     sync()
+    profile = args.full and not args.no_profile
     probe = None
-    if rank == 0 and not args.no_profile:
+    if rank == 0 and profile:
         probe = ops.clock_probe(device)              # (before the timed region; synchronises)
     if world > 1:
         sync()
     prof = None
-    if rank == 0 and not args.no_profile and not args.graph:
+    if rank == 0 and profile and not args.graph:
         prof = ops.ConvProfile()                     # eager timed region: the events bracket the timed launches themselves
         ops.conv_profile = prof
     t0 = time.perf_counter()
@@ -779,8 +833,20 @@ def main():
         tmax = torch.tensor([elapsed], device=device, dtype=torch.float64)
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         elapsed = tmax.item()
+
+    finite = bool(torch.isfinite(sampler.x).all().item())
+    # the one collective of the job: gather the samples (after the loop; not part of a step)
+    t1 = time.perf_counter()
+    gathered = parallel.all_gather_samples(sampler.x, global_batch, always_collective=pg_live)
+    sync()
+    gather_ms = (time.perf_counter() - t1) * 1e3
+    assert gathered.shape[0] == global_batch
+    dumped = None
+    if rank == 0 and args.dump_outputs:
+        dumped = dump_outputs(args.dump_outputs, {'x': gathered})
+
     prof_steps = 0
-    if rank == 0 and not args.no_profile and args.graph and args.profile_steps > 0:
+    if rank == 0 and profile and args.graph and args.profile_steps > 0:
         # events cannot bracket launches inside a graph replay: time the same kernels in extra EAGER steps, outside `value`
         sampler._graph = None
         prof = ops.ConvProfile()
@@ -792,14 +858,6 @@ def main():
         prof_steps = args.profile_steps
     elif prof is not None:
         prof_steps = args.steps
-
-    finite = bool(torch.isfinite(sampler.x).all().item())
-    # the one collective of the job: gather the samples (after the loop; not part of a step)
-    t1 = time.perf_counter()
-    gathered = parallel.all_gather_samples(sampler.x, global_batch, always_collective=pg_live)
-    sync()
-    gather_ms = (time.perf_counter() - t1) * 1e3
-    assert gathered.shape[0] == global_batch
 
     if rank == 0:
         # unit of `value`: one diffusion step of one configuration shard (per_gpu trajectories); weak scaling: every rank
@@ -816,7 +874,7 @@ def main():
             'data': 'synthetic (random-init net + exact Gaussian term, synthetic observations)',
             'config': {'workload': args.workload, 'description': wl['desc'], 'event': list(event),
                        'per_gpu_batch': b, 'global_batch': global_batch, 'guided': bool(args.guided),
-                       'corrections': args.corrections, 'tau': args.tau, 'schedule_steps': 1000,
+                       'corrections': args.corrections, 'tau': args.tau, 'schedule_steps': schedule_steps,
                        'score_evals_per_step': 1 + args.corrections, 'hipgraph_step': bool(args.graph), 'hipgraph_note': graph_note,
                        'observation': 'fused Subsample (hand-written adjoint; no autograd through A)',
                        'corrector_noise': 'row-keyed Philox (sda_randn_rows)',
@@ -828,17 +886,19 @@ def main():
         }
         if os.environ.get('SDA_HIP_LIB'):            # a tooling build of the kernels was swapped in: say so in the line
             out['kernel_library_override'] = os.environ['SDA_HIP_LIB']
+        if dumped is not None:
+            out['outputs_dumped'] = dumped
         if prof is not None and prof_steps > 0:
             out['roofline'] = roofline_report(prof, prof_steps, elapsed / args.steps, args, ROOT, probe)
-        if world == 1 and args.second_line and args.multiply == 'f32' and wl['kind'] == 'kolmogorov':
+        if args.full and world == 1 and args.second_line and args.multiply == 'f32' and wl['kind'] == 'kolmogorov':
             out['opt_in_f16x2'] = second_line(args, sde, sampler, b, device, elapsed / args.steps)
         want_other = args.other_configs == 1 or (args.other_configs < 0 and args.workload == 'kolmogorov256' and args.multiply == 'f32')
-        if world == 1 and want_other:
+        if args.full and world == 1 and want_other:
             sampler = gathered = None                # (the shard's state, its graph pool and the gathered copy: 50+ GB back to the allocator)
             sde.initial_noise = None
             torch.cuda.empty_cache()
             out['other_configs'] = other_configs(args, device)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out['cpu_baseline'] = cpu_baseline(wl, args, bool(args.guided), args.corrections)
             out['gpu_over_cpu'] = value / out['cpu_baseline']['value']
         print(json.dumps(out), flush=True)

@@ -35,16 +35,18 @@ def main():
     spec.loader.exec_module(rutils)
 
     # ---------------------------------------------------------------- mmd: two sample sets of different size
+    # (samples on a grid of quarters: every product and sum in the Gram matrices is exact in fp32, so the reference's
+    # |x|^2 + |y|^2 - 2 x.y arithmetic gives the same bits whichever BLAS kernel, on whichever CPU, forms them)
     torch.manual_seed(21)
-    x = torch.randn(48, 5, 3) * 0.7
-    y = torch.randn(40, 5, 3) * 0.9 + 0.2
+    x = (torch.randn(48, 5, 3) * 0.7 * 4).round() / 4
+    y = ((torch.randn(40, 5, 3) * 0.9 + 0.2) * 4).round() / 4
     G._save('metrics_mmd', x=x, y=y, mmd_xy=rutils.mmd(x, y), mmd_xx=rutils.mmd(x, x[:24]))
 
     # ---------------------------------------------------------------- bpf: noisy rotation, Gaussian likelihood on x[0]
     torch.manual_seed(22)
     x0 = torch.randn(64, 2)
     yobs = torch.randn(5, 1)
-    rot = torch.tensor([[0.96, -0.28], [0.28, 0.96]])
+    rot = torch.tensor([[1.0, -0.25], [0.25, 1.0]])      # (exact products: x @ rot.T rounds once, on any BLAS kernel)
 
     def transition(x):
         return x @ rot.T + 0.1 * torch.randn_like(x)

@@ -61,3 +61,25 @@ def test_gpus8_strong_partition_and_row_keyed_inputs():
     assert not torch.equal(w8[1][1], w8[0][1])
     plan = bench.launch_plan(8, {'MASTER_PORT': '29555'}, ['--gpus', '8', '--scaling', 'strong', '--steps', '5', '--warmup', '2'])
     assert '--nproc-per-node=8' in plan and plan[-8:] == ['--gpus', '8', '--scaling', 'strong', '--steps', '5', '--warmup', '2']
+
+
+def test_dump_outputs_budget_and_fixed_sample(tmp_path):
+    """`--dump-outputs DIR`: a small output is written whole; one over the 64 MB budget as a fixed sample of its elements (the
+    same indices every run) with exact values at those indices, plus float64 row sums over every element."""
+    import numpy as np
+    import torch
+    import bench
+    small = torch.randn(3, 65, 3)
+    assert bench.dump_outputs(str(tmp_path / 's'), {'x': small}) == {'x.npy': [3, 65, 3]}
+    assert np.array_equal(np.load(tmp_path / 's' / 'x.npy'), small.numpy())
+    big = torch.randn(8, 1 << 22)                                     # 128 MB of float32
+    files = [bench.dump_outputs(str(tmp_path / d), {'x': big}) for d in ('a', 'b')]
+    assert files[0] == files[1] and set(files[0]) == {'x_sample.npy', 'x_sample_index.npy', 'x_row_sum.npy', 'x_row_sumsq.npy'}
+    assert sum(os.path.getsize(tmp_path / 'a' / f) for f in files[0]) <= bench.DUMP_BUDGET
+    for f in files[0]:
+        a, b = np.load(tmp_path / 'a' / f), np.load(tmp_path / 'b' / f)
+        assert a.dtype in (np.float32, np.float64) and np.array_equal(a, b), f
+    idx = np.load(tmp_path / 'a' / 'x_sample_index.npy').astype(np.int64)
+    assert len(idx) > 1_000_000 and np.array_equal(np.load(tmp_path / 'a' / 'x_sample.npy'), big.reshape(-1).numpy()[idx])
+    assert np.allclose(np.load(tmp_path / 'a' / 'x_row_sum.npy'), big.double().sum(1).numpy(), rtol=1e-12, atol=1e-9)
+    assert np.allclose(np.load(tmp_path / 'a' / 'x_row_sumsq.npy'), big.double().square().sum(1).numpy(), rtol=1e-12)

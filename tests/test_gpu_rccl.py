@@ -96,7 +96,7 @@ def test_bench_code_path_with_a_live_process_group():
     """`bench.py --gpus 1` with the group initialised: barrier + max-over-ranks all-reduce around the timed region and the final
     all-gather through RCCL; `ranks_seen` is read from the live group."""
     p = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--force-pg', '1', '--workload', 'lorenz96',
-                        '--steps', '2', '--warmup', '1', '--no-cpu-baseline', '--other-configs', '0'],
+                        '--steps', '2', '--warmup', '1', '--full', '--no-cpu-baseline', '--other-configs', '0'],
                        env=_env(), capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, p.stderr[-3000:]
     out = json.loads([ln for ln in p.stdout.splitlines() if ln.startswith('{')][-1])

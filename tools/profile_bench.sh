@@ -11,7 +11,7 @@ TAG="$1"; shift
 R=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$R/gpurun_out/prof_$TAG; mkdir -p $OUT $R/profiles
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats -d $OUT/trace -o t -- python $R/bench.py "$@" --no-cpu-baseline > $OUT/bench_trace.json 2> $OUT/trace.err
+rocprofv3 --kernel-trace --stats -d $OUT/trace -o t -- python $R/bench.py "$@" --full --no-cpu-baseline > $OUT/bench_trace.json 2> $OUT/trace.err
 if [ "${PROFILE_PMC:-1}" != 0 ]; then
 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $OUT/fetch -o p -- python $R/bench.py "$@" --no-cpu-baseline --no-profile > /dev/null 2> $OUT/fetch.err
 rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d $OUT/write -o p -- python $R/bench.py "$@" --no-cpu-baseline --no-profile > /dev/null 2> $OUT/write.err
