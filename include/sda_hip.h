@@ -167,6 +167,43 @@ int sda_conv_igemm_path(const sda_conv_desc* d);
 int64_t sda_conv_igemm_lds_bytes(const sda_conv_desc* d);
 
 /* ------------------------------------------------------------------------------------------
+ * Parameter gradients of the convolutions (csrc/conv_wgrad.hip).  Additions that keep ABI v13: no existing entry or struct
+ * changes.  They replace what torch.autograd forms for the weights and biases of sda/nn.py:113-176's nn.Conv1d / nn.Conv2d when
+ * the reference trains (sda/score.py:265-276 ``loss`` -> ``backward()``, driven by sda/utils.py:89-165 ``loop``):
+ *
+ *   dw[co][ci][ky][kx] (+)= sum_{n,oy,ox} g[n][co][oy][ox] * V(n, ci, oy*stride_h + ky - pad_h, ox*stride_w + kx - pad_w)
+ *   db[co]             (+)= sum_{n,oy,ox} g[n][co][oy][ox]
+ *
+ * V is the layer's input as its FORWARD launch read it: `conv` is that launch's descriptor (source view incl. the sliding-window
+ * and context channels, mod / ln_mean / ln_rstd / act_in, up-sampling, stride, padding, kh / kw, cout, ho / wo); its w, bias, out,
+ * dact_z, res, mt and Winograd / f16 fields are ignored, zins and pool must be off.  g: the cotangent at the convolution's output,
+ * planar contiguous [n][cout][ho][wo].  dw: torch layout [cout][cin][kh][kw] (cin = cx + cctx), db: [cout] or NULL.
+ * The contraction over positions is cut into `slabs` ranges (0 = planner's choice, a function of the shape; at most 64) whose
+ * partial results go to `work` (sda_conv_wgrad_work_floats floats) and are summed in slab order by a second kernel: no atomics,
+ * bitwise reproducible.  accumulate = 1 adds into dw / db (chunks of the image axis), 0 overwrites.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct sda_wgrad_desc {
+    sda_conv_desc conv;
+    const float* g;
+    float* dw;
+    float* db;
+    float* work;
+    int32_t slabs;
+    int32_t accumulate;
+} sda_wgrad_desc;
+
+int sda_conv_wgrad(const sda_wgrad_desc* d, void* stream);
+/* planning only (nothing is launched): the slab count the launch would use / the floats of `work` it needs; <0 error */
+int sda_conv_wgrad_slabs(const sda_wgrad_desc* d);
+int64_t sda_conv_wgrad_work_floats(const sda_wgrad_desc* d);
+/* Gradient of the modulation rows (sda/nn.py:28 ``x + project(y)`` before the LayerNorm): spatial sums of the cotangent at the
+ * LayerNorm's input.  x, y: planar [n][c][hw]; out[i * out_sn + ch] (+)= sum_pix (x - y)[i][ch][pix] (y = NULL: x alone), or
+ * with sum_images = 1 (a time embedding shared by all images) out[ch] (+)= sum_i sum_pix, images summed in order.
+ * accumulate = 1 adds into out.  Fixed-order reductions, no atomics. */
+int sda_plane_sum(const float* x, const float* y, int n, int c, int64_t hw, float* out, int64_t out_sn, int sum_images,
+                  int accumulate, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * One modulated residual block of a 1-D U-Net in ONE launch (sda/nn.py:18-28, 113-176 with spatial = 1):
  *     y = a + conv2(act(conv1(LN(a + mod)))),   both convolutions c -> c, kernel 3, stride 1, same padding mode;
  * and its input VJP  gx = g + LN^T(conv1^T(act'(z) . conv2^T(g))).  For the latency-bound nets of the Lorenz experiments

@@ -167,6 +167,15 @@ class Net1dFuse(Structure):
     ]
 
 
+class WgradDesc(Structure):
+    """include/sda_hip.h sda_wgrad_desc"""
+    _fields_ = [
+        ('conv', ConvDesc),
+        ('g', c_fp), ('dw', c_fp), ('db', c_fp), ('work', c_fp),
+        ('slabs', c_int32), ('accumulate', c_int32),
+    ]
+
+
 SIGNATURES = {
     'sda_abi_version': (c_int, []),
     'sda_conv_igemm': (c_int, [POINTER(ConvDesc), c_void_p]),
@@ -184,6 +193,10 @@ SIGNATURES = {
                                      c_int64, c_void_p]),
     'sda_conv_parity4': (c_int, [POINTER(ConvDesc), c_void_p]),
     'sda_conv_igemm_path': (c_int, [POINTER(ConvDesc)]),
+    'sda_conv_wgrad': (c_int, [POINTER(WgradDesc), c_void_p]),
+    'sda_conv_wgrad_slabs': (c_int, [POINTER(WgradDesc)]),
+    'sda_conv_wgrad_work_floats': (c_int64, [POINTER(WgradDesc)]),
+    'sda_plane_sum': (c_int, [c_fp, c_fp, c_int, c_int, c_int64, c_fp, c_int64, c_int, c_int, c_void_p]),
     'sda_conv_igemm_lds_bytes': (c_int64, [POINTER(ConvDesc)]),
     'sda_pack_conv_weight': (c_int, [c_fp, c_int, c_int, c_int, c_int, c_int, c_int, c_fp, c_int, c_int, c_void_p]),
     'sda_pack_conv_weight_wino': (c_int, [c_fp, c_int, c_int, c_int, c_int, c_fp, c_int, c_int, c_void_p]),

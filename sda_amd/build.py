@@ -16,10 +16,11 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, 'csrc')
 LIBDIR = os.environ.get('SDA_LIBDIR') or os.path.join(HERE, 'lib')      # (SDA_LIBDIR: tooling builds beside the product one)
 ARCH = 'gfx950'
-SOURCES = ['conv_igemm.hip', 'conv_wino.hip', 'conv_wino4.hip', 'conv_small1d.hip', 'conv_few.hip', 'conv_par4.hip', 'conv_h2.hip', 'conv3d.hip', 'block1d.hip', 'net1d.hip', 'step1d.hip', 'norm.hip', 'elementwise.hip', 'linear.hip', 'mlp1d.hip', 'observe.hip', 'metrics.hip', 'noise.hip', 'probe.hip']
+SOURCES = ['conv_igemm.hip', 'conv_wino.hip', 'conv_wino4.hip', 'conv_small1d.hip', 'conv_few.hip', 'conv_par4.hip', 'conv_h2.hip', 'conv3d.hip', 'conv_wgrad.hip', 'block1d.hip', 'net1d.hip', 'step1d.hip', 'norm.hip', 'elementwise.hip', 'linear.hip', 'mlp1d.hip', 'observe.hip', 'metrics.hip', 'noise.hip', 'probe.hip']
 HIPCC = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
 # extra compile flags (e.g. SDA_EXTRA_HIPCC_FLAGS=-DSDA_W4_VARIANTS builds the tuning variants tools/wino4_check.py compares)
 EXTRA_FLAGS = os.environ.get('SDA_EXTRA_HIPCC_FLAGS', '').split()
+EMU_SOURCES = ['conv_igemm.hip', 'conv_wgrad.hip']       # host replays of the tile algorithms (libsda_emu.so)
 CONV_PARTS = 4                                       # see SDA_CONV_PART in csrc/conv_igemm.hip
 
 
@@ -94,12 +95,12 @@ def build(force=False, verbose=False):
 
 def build_emu(force=False):
     os.makedirs(LIBDIR, exist_ok=True)
-    src = os.path.join(CSRC, 'conv_igemm.hip')
+    srcs = [os.path.join(CSRC, f) for f in EMU_SOURCES]
     lib = os.path.join(LIBDIR, 'libsda_emu.so')
-    if force or _newer(lib, [src] + _headers()):
+    if force or _newer(lib, srcs + _headers()):
         subprocess.check_call([HIPCC, '--offload-host-only', '-DSDA_HOST_EMU', '-O2', '-std=c++17', '-fPIC',
-                               '-ffp-contract=off', '-shared', src, '-o', lib])
-        _stamp(lib, [src] + _headers())
+                               '-ffp-contract=off', '-shared'] + srcs + ['-o', lib])
+        _stamp(lib, srcs + _headers())
     return lib
 
 

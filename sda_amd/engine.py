@@ -1,8 +1,9 @@
 """Executor of the modulated residual U-Net on MI355X: forward and backward-data (VJP w.r.t. the input).
 
 It sequences the gfx950 kernels of libsda_hip.so for the reference's ``UNet.forward`` (sda/nn.py:184-206) and for
-the gradient torch.autograd would propagate through it at sda/score.py:394 (guidance needs d/dx only -- no weight
-gradients are ever formed).
+the gradient torch.autograd would propagate through it at sda/score.py:394 (guidance needs d/dx only).  With parameter
+gradients switched on (sda_amd.training) the backward also forms every convolution's weight / bias gradient
+(csrc/conv_wgrad.hip) and the modulation rows' gradient, each launched as soon as its layer's cotangent exists.
 
 Layout: every internal activation is PLANAR ``[n][c][h][w]`` fp32 (1-D nets: ``h = 1``).  Per residual block the
 forward runs three kernels and materialises two tensors:
@@ -71,6 +72,16 @@ class Source:
     ctx: Optional[Tensor] = None
     cctx: int = 0
     ctx_sn: int = 0
+
+
+def _source0(src: Source, lo: int, n: int):
+    """Loader fields of the level-0 head for images [lo, lo + n) of ``src`` (strided / window view) and its context rows."""
+    sdesc = dict(x_ptr=src.x.data_ptr(), n=n, cx=src.cx, hs=src.hs, ws=src.ws, x_sn_outer=src.sn_outer,
+                 x_sn_inner=src.sn_inner, n_inner=src.n_inner, x_n_off=lo, x_sc=src.sc, x_sy=src.sy, x_sx=src.sx)
+    ctx = src.ctx
+    if ctx is not None and src.ctx_sn:
+        ctx = ctx[lo * src.ctx_sn:]
+    return sdesc, ctx
 
 
 def planar_source(a: Tensor) -> dict:
@@ -287,6 +298,38 @@ class UNetEngine:
         st = unet.stride
         self.sh, self.sw = (1, st[0]) if len(st) == 1 else st
 
+    def convs(self) -> List[_ConvCache]:
+        """Every convolution of the net, in a fixed order (heads, tails, then the blocks' conv1 / conv2 per level)."""
+        out = []
+        for lev in self.levels:
+            out += [lev.head, lev.tail]
+            for blk in lev.descent + lev.ascent:
+                out += [blk.conv1, blk.conv2]
+        return out
+
+    def train_params(self) -> List[Tensor]:
+        """The convolution weights and biases whose gradients the training-mode backward forms (inputs of the autograd nodes)."""
+        ps = []
+        for cc in self.convs():
+            ps.append(cc.conv.weight)
+            if cc.conv.bias is not None:
+                ps.append(cc.conv.bias)
+        return ps
+
+    def param_grads(self, pg: Optional['ParamGrads'], params: List[Tensor]) -> list:
+        """Gradients for ``params`` (train_params order) from a finished backward; None where none was asked for."""
+        if pg is None:
+            return [None] * len(params)
+        by_id = {}
+        for cc in self.convs():
+            hit = pg.conv_grads.get(id(cc))
+            if hit is None:
+                continue
+            by_id[id(cc.conv.weight)] = hit[0].view(cc.conv.weight.shape)
+            if cc.conv.bias is not None:
+                by_id[id(cc.conv.bias)] = hit[1]
+        return [by_id.get(id(p)) if p.requires_grad else None for p in params]
+
     def invalidate(self):
         """Drop every packed-weight cache (forward / backward-data / Winograd / parity packs, the concatenated projection
         matrix).  The caches re-key themselves on parameter pointer and version, which in-place writes through ``.data``
@@ -321,6 +364,14 @@ class UNetEngine:
         w, b = self.projection()
         return ops.linear_small(emb.contiguous(), w, b)
 
+    def modulation_train(self, emb: Tensor) -> Tensor:
+        """The same rows, formed differentiably (training route): torch autograd carries their gradient on to the ``project``
+        Linears and the time embedding -- a (T x mod_features) x (mod_features x mod_total) GEMM, a sliver of a training step."""
+        blocks = sorted(self._blocks(), key=lambda b: b.mod_off)
+        w = torch.cat([b.project.weight for b in blocks], dim=0)
+        bias = torch.cat([b.project.bias for b in blocks], dim=0)
+        return torch.nn.functional.linear(emb, w, bias).contiguous()
+
     # -------------------------------------------------------------------------------- memory planning
     def bytes_per_image(self, hs: int, ws: int, save: bool) -> int:
         total, h, w = 0, hs, ws
@@ -340,11 +391,12 @@ class UNetEngine:
         return int(max(1, min(n, (avail * (fraction or CHUNK_HBM_FRACTION)) // per)))
 
     # -------------------------------------------------------------------------------- whole-batch drivers
-    def forward_all(self, src: Source, mod_all, per_image: bool, out: Tensor, need_grad: bool):
+    def forward_all(self, src: Source, mod_all, per_image: bool, out: Tensor, need_grad: bool, train: bool = False):
         """All images of ``src`` -> ``out``; returns the VJP state: a list of (lo, hi, saved-or-None).
 
         With ``need_grad`` the activations of as many images as fit ``KEEP_HBM_FRACTION`` of the unallocated HBM are kept
-        (all of them when they fit: one forward, one backward); the rest is recomputed chunk by chunk in the backward."""
+        (all of them when they fit: one forward, one backward); the rest is recomputed chunk by chunk in the backward.
+        ``train``: keep what the weight gradients need too (training route; no whole-net 1-D kernel)."""
         n = src.n
         dev = out.device
         state = []
@@ -352,25 +404,28 @@ class UNetEngine:
         if need_grad:
             keep = self.chunk_size(n, src.hs, src.ws, True, dev, KEEP_HBM_FRACTION)
             if keep >= n:
-                state.append((0, n, self.forward_chunk(src, 0, n, mod_all, per_image, out, True)))
+                state.append((0, n, self.forward_chunk(src, 0, n, mod_all, per_image, out, True, train)))
                 return state
             if keep >= max(8, n // 16):                 # worth keeping a leading part
-                state.append((0, keep, self.forward_chunk(src, 0, keep, mod_all, per_image, out[:keep], True)))
+                state.append((0, keep, self.forward_chunk(src, 0, keep, mod_all, per_image, out[:keep], True, train)))
                 lo = keep
         chunk = self.chunk_size(n - lo, src.hs, src.ws, False, dev)
         while lo < n:
             hi = min(n, lo + chunk)
-            self.forward_chunk(src, lo, hi, mod_all, per_image, out[lo:hi], False)
+            self.forward_chunk(src, lo, hi, mod_all, per_image, out[lo:hi], False, train)
             state.append((lo, hi, None))
             lo = hi
         return state
 
-    def backward_all(self, state, g_out: Tensor, src: Source, mod_all, per_image: bool, g_in: Tensor):
-        """VJP for every image: kept chunks go straight to the backward, the others recompute their forward first."""
+    def backward_all(self, state, g_out: Tensor, src: Source, mod_all, per_image: bool, g_in: Optional[Tensor],
+                     pg: Optional['ParamGrads'] = None):
+        """VJP for every image: kept chunks go straight to the backward, the others recompute their forward first.
+        g_in None: no input gradient is formed.  pg: the training route's gradient buffers (every chunk adds into them)."""
         dev = g_out.device
+        part = lambda lo, hi: None if g_in is None else g_in[lo:hi]
         for lo, hi, saved in state:
             if saved is not None:
-                self.backward_chunk(saved, g_out[lo:hi], src, lo, mod_all, per_image, g_in[lo:hi])
+                self.backward_chunk(saved, g_out[lo:hi], src, lo, mod_all, per_image, part(lo, hi), pg)
         pending = [(lo, hi) for lo, hi, saved in state if saved is None]
         if not pending:
             return
@@ -380,8 +435,8 @@ class UNetEngine:
                               dtype=torch.float32)
         while lo < end:
             hi = min(end, lo + chunk)
-            saved = self.forward_chunk(src, lo, hi, mod_all, per_image, scratch[:hi - lo], True)
-            self.backward_chunk(saved, g_out[lo:hi], src, lo, mod_all, per_image, g_in[lo:hi])
+            saved = self.forward_chunk(src, lo, hi, mod_all, per_image, scratch[:hi - lo], True, pg is not None)
+            self.backward_chunk(saved, g_out[lo:hi], src, lo, mod_all, per_image, part(lo, hi), pg)
             del saved
             lo = hi
 
@@ -537,15 +592,16 @@ class UNetEngine:
         return y
 
     def forward_chunk(self, src: Source, lo: int, hi: int, mod_all: Optional[Tensor], per_image: bool, out: Tensor,
-                      save: bool):
-        """Images [lo, hi) of ``src`` -> ``out`` (n, out_channels, h, w).  Returns what the VJP needs (or None)."""
-        plan = self.net1d_plan(src)
+                      save: bool, train: bool = False):
+        """Images [lo, hi) of ``src`` -> ``out`` (n, out_channels, h, w).  Returns what the VJP needs (or None); with ``train``
+        also the inputs of the stride-2 heads and of the level-0 tail (the weight gradients read them)."""
+        plan = None if train else self.net1d_plan(src)
         if plan is not None:
             return self._net1d_forward(plan, src, lo, hi, mod_all, per_image, out, save)
         n = hi - lo
         dev = out.device
         L, D = self.levels, self.depth
-        saved = dict(blocks={}, tails={}, dims=[]) if save else None
+        saved = dict(blocks={}, tails={}, dims=[], head_in={}, tail0_in=None) if save else None
         skips, dims = [], []
         a, h, w = None, src.hs, src.ws
         for lvl, lev in enumerate(L):
@@ -554,17 +610,14 @@ class UNetEngine:
             if lvl == 0:
                 ho, wo = conv_out_size(h, hd.kh, hd.sh), conv_out_size(w, hd.kw, hd.sw)
                 a = torch.empty(n, lev.C, ho, wo, device=dev, dtype=torch.float32)
-                sdesc = dict(x_ptr=src.x.data_ptr(), n=n, cx=src.cx, hs=src.hs, ws=src.ws, x_sn_outer=src.sn_outer,
-                             x_sn_inner=src.sn_inner, n_inner=src.n_inner, x_n_off=lo, x_sc=src.sc, x_sy=src.sy,
-                             x_sx=src.sx)
-                ctx = src.ctx
-                if ctx is not None and src.ctx_sn:
-                    ctx = ctx[lo * src.ctx_sn:]
+                sdesc, ctx = _source0(src, lo, n)
                 launch_conv(pk, sdesc, a, ho, wo, circular=hd.circular, stride=(hd.sh, hd.sw), bias=pk.bias, ctx=ctx,
                             cctx=src.cctx, ctx_sn=src.ctx_sn)
             else:
                 ho, wo = conv_out_size(h, hd.kh, hd.sh), conv_out_size(w, hd.kw, hd.sw)
                 a2 = torch.empty(n, lev.C, ho, wo, device=dev, dtype=torch.float32)
+                if save and train:
+                    saved['head_in'][lvl] = a
                 xa = None
                 if ops.MULTIPLY == 'f16x2' and ops.H2_S2 and (hd.sh, hd.sw) == (2, 2) and getattr(pk, 'h2', None) is not None and a.is_contiguous():
                     xa = ops.absmax(a, pk.in_amax)       # (the f16 x 2 parity-plane form needs its input's scale: one streaming read)
@@ -604,20 +657,22 @@ class UNetEngine:
                     saved['tails'][lvl] = (a, mean, rstd)
                 a, h, w = t, hu, wu
             else:
+                if save and train:
+                    saved['tail0_in'] = a
                 launch_conv(pk, planar_source(a), out, h, w, circular=tl.circular, bias=pk.bias)
         if save:
             saved['dims'] = dims
         return saved
 
     # -------------------------------------------------------------------------------- backward-data
-    def _block_bwd(self, blk: _Block, g: Tensor, rec, mod_all, lo, per_image, g_amax_in=None):
+    def _block_bwd(self, blk: _Block, g: Tensor, rec, mod_all, lo, per_image, g_amax_in=None, pg: Optional['ParamGrads'] = None):
         """-> (gradient w.r.t. the block's input, device scalar with its max |.| or None).  g_amax_in: max |g| as its producer reported
         it (an ln_bwd launch of the previous block / tail); None: an ops.absmax pass when the f16 x 2 route needs the scale."""
         a, mean, rstd, z = rec
         n, c, h, w = a.shape
         mod, mod_sn = self._mod_for(blk, mod_all, lo, per_image)
         c1, c2 = blk.conv1, blk.conv2
-        if (c1.circular == c2.circular and (c1.sh, c1.sw, c2.sh, c2.sw) == (1, 1, 1, 1) and
+        if (pg is None and c1.circular == c2.circular and (c1.sh, c1.sw, c2.sh, c2.sw) == (1, 1, 1, 1) and
                 ops.block1d_eligible(c, h, c1.fwd(), c2.fwd())):
             gx = torch.empty_like(a)
             ops.block1d_bwd(g, a, z, mean, rstd, mod, mod_sn, c1.bwd(), c2.bwd(), c1.circular, blk.act, self.unbiased, gx)
@@ -631,6 +686,9 @@ class UNetEngine:
         d2 = launch_conv(pk2, planar_source(g), gz, h, w, circular=c2.circular, dact_z=z, act_d=blk.act, x_amax=g_amax, out_amax=gz_amax)
         if not (d2 is not None and d2.w_h2):
             gz_amax = None
+        if pg is not None:                               # conv2 saw act(z) and produced the block's residual branch (cotangent g)
+            self._wgrad(pg, c2, planar_source(z), g, h, w, act_in=blk.act)
+            self._wgrad(pg, c1, planar_source(a), gz, h, w, mod=mod, mod_sn=mod_sn, ln=(mean, rstd))
         gh = torch.empty_like(a)
         c1 = blk.conv1
         launch_conv(c1.bwd(), planar_source(gz), gh, h, w, circular=c1.circular, x_amax=gz_amax)
@@ -642,11 +700,29 @@ class UNetEngine:
             if gx_amax is None or gx_amax.device != a.device:
                 gx_amax = blk._gx_amax = torch.zeros(1, device=a.device, dtype=torch.float32)
         ops.ln_bwd(gh, a, h, w, mod, mod_sn, mean, rstd, self.unbiased, (1, 1), g, gx, out_amax=gx_amax)
+        if pg is not None and mod is not None:
+            pg.modulation(blk, gx, g, lo, self.mod_total)          # (gx - g: the cotangent at LN's input a + mod)
         return gx, gx_amax
 
-    def backward_chunk(self, saved, g_out: Tensor, src: Source, lo: int, mod_all, per_image: bool, g_in: Tensor):
-        """g_out: (n, out_channels, h, w) -> g_in: (n, src.cx, hs, ws)   (context-channel gradients are not formed)."""
+    def _wgrad(self, pg: 'ParamGrads', cc: _ConvCache, sdesc: dict, g: Tensor, ho: int, wo: int, *, mod=None, mod_sn=0, ln=None,
+               act_in=0, up=(1, 1), ctx=None, cctx=0, ctx_sn=0):
+        """Weight / bias gradient of ``cc`` for the output cotangent ``g``: its forward descriptor rebuilt, the loader as the
+        forward ran it."""
+        d = make_conv_desc(**sdesc, w_ptr=0, cin_pad=0, cout_pad=0, cout=cc.cout, kh=cc.kh, kw=cc.kw, out_ptr=0, ho=ho, wo=wo,
+                           mt=1, stride_h=cc.sh, stride_w=cc.sw, circular=cc.circular, up_h=up[0], up_w=up[1],
+                           ctx_ptr=None if ctx is None else ctx.data_ptr(), cctx=cctx, ctx_sn=ctx_sn,
+                           mod_ptr=None if mod is None else mod.data_ptr(), mod_sn=mod_sn,
+                           ln_mean_ptr=None if ln is None else ln[0].data_ptr(), ln_rstd_ptr=None if ln is None else ln[1].data_ptr(),
+                           act_in=act_in)
+        pg.conv(cc, d, g)
+
+    def backward_chunk(self, saved, g_out: Tensor, src: Source, lo: int, mod_all, per_image: bool, g_in: Optional[Tensor],
+                       pg: Optional['ParamGrads'] = None):
+        """g_out: (n, out_channels, h, w) -> g_in: (n, src.cx, hs, ws)   (context-channel gradients are not formed; g_in None:
+        no input gradient).  pg: also the parameter gradients, each launched as soon as its layer's cotangent exists."""
         if 'net1d' in saved:
+            if pg is not None:
+                raise SdaHipError('the whole-net 1-D kernel forms no parameter gradients (training-route forwards do not use it)')
             return self._net1d_backward(saved, g_out, src, lo, mod_all, per_image, g_in)
         g_out = g_out.contiguous()
         L, D = self.levels, self.depth
@@ -656,6 +732,8 @@ class UNetEngine:
         h, w = dims[0]
         tl = L[0].tail
         g = torch.empty(n, L[0].C, h, w, device=dev, dtype=torch.float32)
+        if pg is not None:
+            self._wgrad(pg, tl, planar_source(saved['tail0_in']), g_out, h, w)
         launch_conv(tl.bwd(), planar_source(g_out), g, h, w, circular=tl.circular)
         g_amax = None                                    # max |g| as reported by g's producer (ln_bwd launches), f16 x 2 route only
         g_skip = {}
@@ -671,6 +749,8 @@ class UNetEngine:
                     raise NotImplementedError('VJP through Upsample is implemented for scale factor 2')
                 tl = lev.tail
                 a, mean, rstd = saved['tails'][lvl]
+                if pg is not None:                       # the tail read LN(a) through the nearest up-sample
+                    self._wgrad(pg, tl, planar_source(a), g, hu, wu, ln=(mean, rstd), up=(uh, uw))
                 # the VJP of Upsample -> conv: the transposed convolution at the fine resolution, summed over the up-sampling
                 # cells -- in ONE launch where the kernel can pool in its epilogue (2 x 2: 7 of the 16 Winograd positions drop out
                 # of the cell sum), else the fine-resolution gradient goes through memory and ln_bwd pools while reading it
@@ -696,12 +776,18 @@ class UNetEngine:
                 else:
                     ops.ln_bwd(ghup, a, h, w, None, 0, mean, rstd, self.unbiased, (uh, uw), None, g, out_amax=g_amax)
             for bi in reversed(range(len(lev.ascent))):
-                g, g_amax = self._block_bwd(lev.ascent[bi], g, saved['blocks'][('a', lvl, bi)], mod_all, lo, per_image, g_amax)
+                g, g_amax = self._block_bwd(lev.ascent[bi], g, saved['blocks'][('a', lvl, bi)], mod_all, lo, per_image, g_amax, pg)
         for lvl in reversed(range(D)):
             lev = L[lvl]
             for bi in reversed(range(len(lev.descent))):
-                g, g_amax = self._block_bwd(lev.descent[bi], g, saved['blocks'][('d', lvl, bi)], mod_all, lo, per_image, g_amax)
+                g, g_amax = self._block_bwd(lev.descent[bi], g, saved['blocks'][('d', lvl, bi)], mod_all, lo, per_image, g_amax, pg)
             hd = lev.head
+            if pg is not None:                           # (g: the cotangent at this level's head output, dims[lvl])
+                if lvl > 0:
+                    self._wgrad(pg, hd, planar_source(saved['head_in'][lvl]), g, *dims[lvl])
+                else:
+                    sdesc, ctx = _source0(src, lo, n)
+                    self._wgrad(pg, hd, sdesc, g, *dims[lvl], ctx=ctx, cctx=src.cctx, ctx_sn=src.ctx_sn)
             if lvl > 0:
                 hu, wu = dims[lvl - 1]
                 if hd.circular and ((hd.sh > 1 and hu % hd.sh) or (hd.sw > 1 and wu % hd.sw)):
@@ -740,19 +826,51 @@ class UNetEngine:
                                 res=skip)
                 g = g2
                 g_amax = None                            # (produced by a convolution of the fp32 families: no report)
-            else:
+            elif g_in is not None:
                 launch_conv(hd.bwd(cin_keep=src.cx), planar_source(g), g_in, src.hs, src.ws, circular=hd.circular,
                             zins=(hd.sh, hd.sw))
 
 
 # ------------------------------------------------------------------------------------------ autograd glue
 
+class ParamGrads:
+    """Gradient buffers of one training-route backward: (dw, db) per convolution and the modulation rows' gradient.  The first
+    chunk that reaches a buffer writes it, later chunks (the recomputed ones) add into it."""
+
+    def __init__(self, mod_all: Optional[Tensor], per_image: bool, need_mod: bool):
+        self.conv_grads = {}                             # id(_ConvCache) -> (dw, db)
+        self.per_image = per_image
+        self.gmod = torch.empty_like(mod_all) if (need_mod and mod_all is not None) else None
+        self._mod_written = set()
+
+    def conv(self, cc: _ConvCache, desc, g: Tensor):
+        hit = self.conv_grads.get(id(cc))
+        accumulate = hit is not None
+        if hit is None:
+            w, b = cc.conv.weight, cc.conv.bias
+            hit = self.conv_grads[id(cc)] = (torch.empty(w.shape, device=g.device, dtype=torch.float32),
+                                             None if b is None else torch.empty(b.shape, device=g.device, dtype=torch.float32))
+        ops.conv_wgrad(desc, g, hit[0], hit[1], accumulate)
+
+    def modulation(self, blk: _Block, gx: Tensor, g: Tensor, lo: int, mod_total: int):
+        """Block ``blk``'s rows: the spatial sums of gx - g (images [lo, lo + n)), summed over the images for a shared row."""
+        if self.gmod is None:
+            return
+        if self.per_image:
+            ops.plane_sum(gx, g, self.gmod[lo:, blk.mod_off:], mod_total, False, False)
+        else:
+            ops.plane_sum(gx, g, self.gmod[:, blk.mod_off:], 0, True, id(blk) in self._mod_written)
+            self._mod_written.add(id(blk))
+
+
 class _UNetFunction(torch.autograd.Function):
-    """out[n] = UNet(src[n], mod) with a hand-written VJP w.r.t. ``x`` only."""
+    """out[n] = UNet(src[n], mod) with a hand-written VJP w.r.t. ``x``; on the training route (``params`` = the engine's
+    train_params(), ``mod_all`` formed differentiably) also w.r.t. the convolution weights / biases and ``mod_all``."""
 
     @staticmethod
-    def forward(ctx, x: Tensor, engine: UNetEngine, src: Source, mod_all, per_image: bool, out_channels: int):
-        need = ctx.needs_input_grad[0]
+    def forward(ctx, x: Tensor, engine: UNetEngine, src: Source, mod_all, per_image: bool, out_channels: int, *params):
+        need = any(ctx.needs_input_grad)
+        train = len(params) > 0
         dev = x.device
         n = src.n
         # output spatial size of level 0
@@ -761,19 +879,23 @@ class _UNetFunction(torch.autograd.Function):
         # a channel-last trajectory (MCScoreWrapper's transposed view of a (B, L, C) tensor) through the whole-net 1-D kernel:
         # the output is laid out channel-last too, so that the wrapper's transpose back is a contiguous tensor -- the kernel
         # writes through strides, no copy kernel on either side (and likewise for the cotangent / input gradient below)
-        ctx.channel_last = bool(src.hs == 1 and src.sc == 1 and src.sx == src.cx and src.cx > 1 and engine.net1d_plan(src) is not None)
+        ctx.channel_last = bool(not train and src.hs == 1 and src.sc == 1 and src.sx == src.cx and src.cx > 1 and
+                                engine.net1d_plan(src) is not None)
         if ctx.channel_last:
             out = torch.empty(n, ho, wo, out_channels, device=dev, dtype=torch.float32).permute(0, 3, 1, 2)
         else:
             out = torch.empty(n, out_channels, ho, wo, device=dev, dtype=torch.float32)
         ctx.engine, ctx.src, ctx.mod_all, ctx.per_image = engine, src, mod_all, per_image
         ctx.x_shape = x.shape
-        ctx.vjp_state = engine.forward_all(src, mod_all, per_image, out, need)
+        ctx.params = params
+        ctx.vjp_state = engine.forward_all(src, mod_all, per_image, out, need, train)
         return out
 
     @staticmethod
     def backward(ctx, g_out: Tensor):
         engine, src = ctx.engine, ctx.src
+        if ctx.params:
+            return _train_backward(ctx, g_out)
         if ctx.channel_last:                             # (strided cotangent in, channel-last gradient out: see forward)
             g_in = torch.empty(src.n, src.hs, src.ws, src.cx, device=g_out.device, dtype=torch.float32).permute(0, 3, 1, 2)
         else:
@@ -783,14 +905,35 @@ class _UNetFunction(torch.autograd.Function):
         return g_in.reshape(ctx.x_shape), None, None, None, None, None
 
 
+def _train_backward(ctx, g_out: Tensor):
+    """_UNetFunction.backward on the training route: input gradient if asked for, convolution weight / bias and modulation-row
+    gradients if asked for (an input-only request launches nothing beyond the sampling path's VJP)."""
+    engine, src = ctx.engine, ctx.src
+    need_x, need_mod = ctx.needs_input_grad[0], ctx.needs_input_grad[3]
+    need_p = any(ctx.needs_input_grad[6:])
+    g_out = g_out.contiguous()
+    g_in = torch.empty(src.n, src.cx, src.hs, src.ws, device=g_out.device, dtype=torch.float32) if need_x else None
+    pg = ParamGrads(ctx.mod_all, ctx.per_image, need_mod) if (need_p or need_mod) else None
+    engine.backward_all(ctx.vjp_state, g_out, src, ctx.mod_all, ctx.per_image, g_in, pg)
+    ctx.vjp_state = None
+    grads = engine.param_grads(pg, list(ctx.params)) if need_p else [None] * len(ctx.params)
+    return (None if g_in is None else g_in.reshape(ctx.x_shape), None, None, None if pg is None else pg.gmod, None, None, *grads)
+
+
 def run_unet(unet, src: Source, emb: Tensor, grad_anchor: Tensor) -> Tensor:
     """Common entry: ``emb`` (T, mod_features) with T in {1, n}; returns (n, out_channels, h, w)."""
     global _warned_training
+    from . import training
     engine = unet.engine()
     T = emb.shape[0]
     if T not in (1, src.n):
         raise SdaHipError(f'time embedding batch {T} does not broadcast against {src.n} images')
     per_image = T != 1
+    if training.active(unet):
+        # training route (sda_amd.training): the modulation rows and the parameters enter the autograd node
+        training.check_supported(unet)
+        mod_all = engine.modulation_train(emb) if engine.mod_total > 0 else None
+        return _UNetFunction.apply(grad_anchor, engine, src, mod_all, per_image, unet.out_channels, *engine.train_params())
     mod_all = engine.modulation(emb) if engine.mod_total > 0 else None
     if torch.is_grad_enabled() and not grad_anchor.requires_grad and not _warned_training:
         if any(p.requires_grad for p in unet.parameters()):

@@ -299,6 +299,65 @@ def pack_conv_weight(w: Tensor, cout: int, cin: int, kh: int, kw: int, transpose
                                                 k_pad, m_pad, _stream()), 'sda_pack_conv_weight')
 
 
+
+# ------------------------------------------------------------------------------------------ parameter gradients (csrc/conv_wgrad.hip)
+
+def wgrad_desc(conv: ConvDesc, g: Tensor, dw: Tensor, db: Optional[Tensor], accumulate: bool, slabs: int = 0):
+    """The sda_wgrad_desc of one layer: ``conv`` is the layer's FORWARD descriptor (how its loader read the input), ``g`` the
+    cotangent at its output, planar contiguous [n][cout][ho][wo]; ``work`` is filled in by conv_wgrad."""
+    d = _lib.WgradDesc()
+    d.conv = conv
+    d.g, d.dw, d.db = g.data_ptr(), dw.data_ptr(), _ptr(db)
+    d.work = 1                                       # (placeholder for planning; conv_wgrad sets the real buffer)
+    d.slabs, d.accumulate = slabs, int(bool(accumulate))
+    return d
+
+
+def wgrad_flops(conv: ConvDesc) -> float:
+    return 2.0 * conv.n * conv.ho * conv.wo * conv.cout * (conv.cx + conv.cctx) * conv.kh * conv.kw
+
+
+def conv_wgrad(conv: ConvDesc, g: Tensor, dw: Tensor, db: Optional[Tensor], accumulate: bool, slabs: int = 0):
+    """dw (+)= the weight gradient of the layer ``conv`` describes for the output cotangent ``g``; db (+)= its bias gradient."""
+    _dev(g, dw, db)
+    if not g.is_contiguous() or tuple(g.shape) != (conv.n, conv.cout, conv.ho, conv.wo):
+        raise _lib.SdaHipError(f'conv_wgrad: cotangent must be planar contiguous {(conv.n, conv.cout, conv.ho, conv.wo)}, got {tuple(g.shape)}')
+    cin = conv.cx + conv.cctx
+    if not dw.is_contiguous() or dw.numel() != conv.cout * cin * conv.kh * conv.kw or (db is not None and db.numel() != conv.cout):
+        raise _lib.SdaHipError('conv_wgrad: dw / db do not match the layer')
+    lib = _lib.load()
+    d = wgrad_desc(conv, g, dw, db, accumulate, slabs)
+    floats = lib.sda_conv_wgrad_work_floats(ctypes.byref(d))
+    _lib.check(int(min(floats, 0)), 'sda_conv_wgrad_work_floats')
+    work = torch.empty(int(floats), device=g.device, dtype=torch.float32)
+    d.work = work.data_ptr()
+    prof = conv_profile
+    if prof is not None:
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        _lib.check(lib.sda_conv_wgrad(ctypes.byref(d), _stream()), 'sda_conv_wgrad')
+        e1.record()
+        prof.records.append((e0, e1, wgrad_flops(conv), 'wgrad'))
+        return
+    _lib.check(lib.sda_conv_wgrad(ctypes.byref(d), _stream()), 'sda_conv_wgrad')
+
+
+def plane_sum(x: Tensor, y: Optional[Tensor], out: Tensor, out_sn: int, sum_images: bool, accumulate: bool):
+    """out[i * out_sn + ch] (+)= sum over the plane of (x - y)[i][ch] (x, y planar [n][c][...]); sum_images: out[ch] (+)= over all i."""
+    _dev(x, y, out)
+    if not x.is_contiguous() or (y is not None and (not y.is_contiguous() or y.shape != x.shape)):
+        raise _lib.SdaHipError('plane_sum: operands must be planar contiguous and alike')
+    n, c = x.shape[0], x.shape[1]
+    hw = x[0, 0].numel()
+
+    def launch():
+        _lib.check(_lib.load().sda_plane_sum(x.data_ptr(), _ptr(y), n, c, hw, out.data_ptr(), out_sn, int(bool(sum_images)),
+                                             int(bool(accumulate)), _stream()), 'sda_plane_sum')
+    if conv_profile is not None:
+        conv_profile.bracket_mem('plane_sum', 4.0 * n * c * hw * (2 if y is not None else 1), launch)
+    else:
+        launch()
+
 class PackedConv:
     """A conv layer's weights repacked for sda_conv_igemm (forward or backward-data form)."""
 

@@ -18,6 +18,7 @@ from torch import Size, Tensor
 from tqdm import tqdm
 
 from . import ops
+from . import training
 from ._lib import SdaHipError
 from .engine import Source, attach_context, run_unet, source_from_tensor
 from .nn import *  # noqa: F401,F403  (the reference re-exports its nn module the same way, score.py:12)
@@ -43,6 +44,12 @@ class TimeEmbedding(nn.Sequential):
     def forward(self, t: Tensor) -> Tensor:
         ops._dev(t)
         shape = t.shape
+        if training.active(self):
+            # training route: (T x 32) x (32 x 256) and (T x 256) x (256 x E) GEMMs under torch autograd, so that the gradient
+            # of the modulation rows reaches these Linears (a sliver of a training step; the sampling path keeps the kernel)
+            ang = t.reshape(-1, 1) * self.freqs
+            h = torch.nn.functional.silu(self[0](torch.cat((torch.cos(ang), torch.sin(ang)), dim=-1)))
+            return self[2](h).reshape(*shape, -1)
         emb = ops.time_embed(t.reshape(-1).contiguous(), self.freqs, self[0].weight.detach(), self[0].bias.detach(),
                              self[2].weight.detach(), self[2].bias.detach())
         return emb.reshape(*shape, -1)
@@ -194,7 +201,9 @@ class _MCScoreFunction(torch.autograd.Function):
     unfold adjoint (the one place overlaps sum)."""
 
     @staticmethod
-    def forward(ctx, x: Tensor, kernel: 'ScoreUNet', order: int, emb: Tensor, c: Optional[Tensor]):
+    def forward(ctx, x: Tensor, kernel: 'ScoreUNet', order: int, emb: Tensor, c: Optional[Tensor], mod_all: Optional[Tensor] = None,
+                *params):
+        # (training route, sda_amd.training: mod_all formed differentiably by the caller, params = the engine's train_params())
         unet = kernel.network
         engine = unet.engine()
         B, L, C = x.shape[0], x.shape[1], x.shape[2]
@@ -211,11 +220,14 @@ class _MCScoreFunction(torch.autograd.Function):
         if T not in (1, src.n):
             raise SdaHipError(f'time embedding batch {T} does not broadcast against {src.n} windows')
         per_image = T != 1
-        mod_all = engine.modulation(emb) if engine.mod_total > 0 else None
-        need = ctx.needs_input_grad[0]
+        train = len(params) > 0
+        if not train:
+            mod_all = engine.modulation(emb) if engine.mod_total > 0 else None
+        need = any(ctx.needs_input_grad)
         dev = x.device
         s = torch.empty(src.n, wl * C, H, W, device=dev, dtype=torch.float32)
-        ctx.vjp_state = engine.forward_all(src, mod_all, per_image, s, need)
+        ctx.vjp_state = engine.forward_all(src, mod_all, per_image, s, need, train)
+        ctx.params, ctx.n_in = params, 6 + len(params)
         out = torch.empty_like(x)
         ops.fold(s, B, nw, order, C, hw, out)
         ctx.engine, ctx.src, ctx.mod_all, ctx.per_image = engine, src, mod_all, per_image
@@ -232,11 +244,32 @@ class _MCScoreFunction(torch.autograd.Function):
         g = g.contiguous()
         g_s = torch.empty(src.n, wl * C, H, W, device=dev, dtype=torch.float32)
         ops.fold_adjoint(g, B, nw, order, C, hw, g_s)
+        if ctx.params:
+            return _MCScoreFunction._train_backward(ctx, g_s)
         g_win = torch.empty(src.n, wl * C, H, W, device=dev, dtype=torch.float32)
         engine.backward_all(ctx.vjp_state, g_s, src, ctx.mod_all, ctx.per_image, g_win)
         g_x = torch.empty(B, nw + 2 * order, C, H, W, device=dev, dtype=torch.float32)
         ops.unfold_adjoint(g_win, B, nw, order, C, hw, wl * C, g_x)
         return g_x.reshape(ctx.x_shape), None, None, None, None
+
+    @staticmethod
+    def _train_backward(ctx, g_s: Tensor):
+        from .engine import ParamGrads
+        engine, src = ctx.engine, ctx.src
+        B, nw, order, C, H, W = ctx.geom
+        hw, wl = H * W, 2 * order + 1
+        need_x, need_mod, need_p = ctx.needs_input_grad[0], ctx.needs_input_grad[5], any(ctx.needs_input_grad[6:])
+        g_win = torch.empty(src.n, wl * C, H, W, device=g_s.device, dtype=torch.float32) if need_x else None
+        pg = ParamGrads(ctx.mod_all, ctx.per_image, need_mod) if (need_p or need_mod) else None
+        engine.backward_all(ctx.vjp_state, g_s, src, ctx.mod_all, ctx.per_image, g_win, pg)
+        ctx.vjp_state = None
+        g_x = None
+        if need_x:
+            g_x = torch.empty(B, nw + 2 * order, C, H, W, device=g_s.device, dtype=torch.float32)
+            ops.unfold_adjoint(g_win, B, nw, order, C, hw, wl * C, g_x)
+            g_x = g_x.reshape(ctx.x_shape)
+        grads = engine.param_grads(pg, list(ctx.params)) if need_p else [None] * len(ctx.params)
+        return (g_x, None, None, None, None, None if pg is None else pg.gmod, *grads)
 
 
 class _FoldFunction(torch.autograd.Function):
@@ -291,6 +324,11 @@ class MCScoreNet(nn.Module):
             ops._dev(ctx_c)
             emb = kernel.embedding(t.reshape(-1))
             xin = x if x.is_contiguous() else x.contiguous()
+            if training.active(kernel.network):
+                training.check_supported(kernel)
+                engine = kernel.network.engine()
+                mod_all = engine.modulation_train(emb) if engine.mod_total > 0 else None
+                return _MCScoreFunction.apply(xin, kernel, self.order, emb, ctx_c, mod_all, *engine.train_params())
             return _MCScoreFunction.apply(xin, kernel, self.order, emb, ctx_c)
         # generic kernel (ScoreNet, or a user subclass overriding forward): unfold as a view + one gather copy
         s = kernel(self.unfold(x, self.order), t, c)
@@ -396,10 +434,15 @@ class VPSDE(nn.Module):
     def loss(self, x: Tensor, c: Tensor = None, w: Tensor = None) -> Tensor:
         r"""The denoising loss (score.py:265-276), as a VALUE: what the reference's validation pass computes under ``no_grad``
         (sda/utils.py ``loop``).  The networks here form input gradients only, so a call that would need parameter gradients
-        (grad mode on, trainable parameters) raises instead of returning a loss whose ``backward()`` trains nothing."""
+        (grad mode on, trainable parameters) raises instead of returning a loss whose ``backward()`` trains nothing -- unless
+        parameter gradients are switched on (``sda_amd.training``) and the network is one they are formed for."""
         if torch.is_grad_enabled() and any(p.requires_grad for p in self.eps.parameters()):
-            raise NotImplementedError('training is outside the sampling hot path: parameter gradients are never formed. '
-                                      'Evaluate the loss under torch.no_grad() (validation), or freeze the parameters')
+            if training.enabled():
+                training.check_supported(self.eps)
+            else:
+                raise NotImplementedError('training is outside the sampling hot path: parameter gradients are never formed. '
+                                          'Evaluate the loss under torch.no_grad() (validation), or freeze the parameters, or '
+                                          'switch parameter gradients on (sda_amd.training.parameter_gradients())')
         t = torch.rand(x.shape[0], dtype=x.dtype, device=x.device)
         x, eps = self.forward(x, t, train=True)
         err = (self.eps(x, t, c) - eps).square()
@@ -582,7 +625,7 @@ def _eps_with_vjp(sde: VPSDE, x: Tensor, t: Tensor, c, detach: bool):
     if detach:
         with torch.no_grad():
             return sde.eps(x, t, c) if c is not None else sde.eps(x, t), None
-    with torch.enable_grad():
+    with torch.enable_grad(), training.input_only():     # (guidance: d/dx only, whatever the training switch says)
         xg = x.detach().requires_grad_(True)
         eps = sde.eps(xg, t, c) if c is not None else sde.eps(xg, t)
 

@@ -2,7 +2,9 @@ r"""Helpers on the sampling path (subset of the reference's ``sda/utils.py``: AC
 sda/utils.py:19-25,40-42; the evaluation metrics ``bpf`` / ``emd`` / ``mmd`` of sda/utils.py:168-263 live in
 ``sda_amd.metrics`` and are re-exported here under the reference's names; the two config writers the reference's
 ``experiments/*/train.py`` reach through ``from sda.utils import *`` -- ``random_config`` / ``save_config``, sda/utils.py:28-37 --
-are plain host code and kept).  Training loop and datasets are out of scope.
+are plain host code and kept).  ``loop`` is the reference's training loop (sda/utils.py:89-165: AdamW, a linear / cosine /
+exponential LambdaLR schedule, ``(loss_train, loss_valid, lr)`` per epoch); it trains with parameter gradients switched on
+(``sda_amd.training``).  The datasets (``TrajectoryDataset``: h5py files) stay out of scope.
 
 ``from sda.utils import *`` in the reference's drivers also hands on that module's own imports (sda/utils.py:3-16:
 ``json``, ``math``, ``torch``, ``Path``, ``Tensor``, the ``typing`` names, everything of ``sda.score`` and, where installed,
@@ -22,6 +24,7 @@ try:
 except ImportError:
     pass
 
+from . import training
 from .score import *  # noqa: F401,F403  (sda/utils.py:16)
 from .metrics import bpf, emd, mmd  # noqa: F401  (sda.utils.bpf / emd / mmd)
 
@@ -51,3 +54,59 @@ def random_config(configs: Dict[str, Sequence[Any]]) -> Dict[str, Any]:
     for key, values in configs.items():
         drawn[key] = random.choice(values)
     return drawn
+
+
+def _to(x: Any, **kwargs) -> Any:
+    """Move a batch (tensor, or nested tuple / list / dict of them) with ``Tensor.to(**kwargs)``."""
+    if torch.is_tensor(x):
+        return x.to(**kwargs)
+    if isinstance(x, (tuple, list)):
+        return type(x)(_to(v, **kwargs) for v in x)
+    if isinstance(x, dict):
+        return {k: _to(v, **kwargs) for k, v in x.items()}
+    return x
+
+
+_SCHEDULES = {
+    'linear': lambda epochs: (lambda t: 1 - t / epochs),
+    'cosine': lambda epochs: (lambda t: (1 + math.cos(math.pi * t / epochs)) / 2),
+    'exponential': lambda epochs: (lambda t: math.exp(-7 * (t / epochs) ** 2)),
+}
+
+
+def loop(sde: 'VPSDE', trainset, validset, epochs: int = 256, batch_size: int = 64, optimizer: str = 'AdamW',
+         learning_rate: float = 1e-3, weight_decay: float = 1e-3, scheduler: str = 'linear', device: str = 'cpu',
+         **absorb) -> Iterator:
+    """Train ``sde`` (its score network) on ``trainset`` and yield ``(loss_train, loss_valid, lr)`` once per epoch.
+
+    As the reference's loop: shuffled DataLoaders whose items are ``(x, kwargs)`` pairs (``kwargs`` go on to ``sde.loss``),
+    AdamW over ``sde.parameters()``, the learning rate scaled per epoch by the ``linear`` / ``cosine`` / ``exponential`` factor,
+    the mean training loss, the mean validation loss (under ``no_grad``) and the learning rate the epoch ran with.  Parameter
+    gradients are switched on (``sda_amd.training.parameter_gradients()``) while the training steps run."""
+    from torch.utils.data import DataLoader
+    loaders = [DataLoader(ds, batch_size=batch_size, shuffle=True) for ds in (trainset, validset)]
+    if optimizer != 'AdamW':
+        raise ValueError(f'optimizer {optimizer!r} (the loop knows AdamW)')
+    opt = torch.optim.AdamW(sde.parameters(), lr=learning_rate, weight_decay=weight_decay)
+    if scheduler not in _SCHEDULES:
+        raise ValueError(f'scheduler {scheduler!r} (expected one of {sorted(_SCHEDULES)})')
+    sched = torch.optim.lr_scheduler.LambdaLR(opt, lr_lambda=_SCHEDULES[scheduler](epochs))
+    for _ in range(epochs):
+        losses_train, losses_valid = [], []
+        sde.train()
+        with training.parameter_gradients():
+            for batch in loaders[0]:
+                x, kwargs = _to(batch, device=device)
+                loss = sde.loss(x, **kwargs)
+                loss.backward()
+                opt.step()
+                opt.zero_grad()
+                losses_train.append(loss.detach())
+        sde.eval()
+        with torch.no_grad():
+            for batch in loaders[1]:
+                x, kwargs = _to(batch, device=device)
+                losses_valid.append(sde.loss(x, **kwargs))
+        lr = opt.param_groups[0]['lr']
+        yield torch.stack(losses_train).mean().item(), torch.stack(losses_valid).mean().item(), lr
+        sched.step()

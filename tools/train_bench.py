@@ -1,0 +1,203 @@
+"""Training-step benchmark of the opt-in parameter-gradient route (sda_amd.training).  bench.py (sampling) is not involved.
+
+    python tools/train_bench.py [--steps 10] [--warmup 3] [--out profiles/train_bench.json]
+
+Reports, per configuration (Kolmogorov training net: LocalScoreUNet (96, 192, 384) x (3, 3, 3), embedding 64, batch 32 of
+10 + 1 x 64 x 64; Lorenz global net: 1-D (64,) x (3,), batch 64 x 3 x 32):
+  * ms per training step: VPSDE.loss + backward + AdamW.step on this package's kernels;
+  * the same step with the oracle's functional net in fp32 under torch autograd on the same GPU (the stated baseline);
+  * per-family kernel time of one step (ops.ConvProfile): forward convolutions, input-VJP convolutions, weight gradients,
+    LayerNorm / modulation reductions, and the share of the torch-autograd modulation / time-embedding GEMMs;
+and, for the Kolmogorov block shapes (96 ch @ 64^2, 192 @ 32^2, 384 @ 16^2, batch 32), the weight-gradient kernel's TFLOP/s and
+its fraction of the fp32 matrix peak (256 CUs x 4 SIMDs x 256 flop/clk x 2.4 GHz = 157.3 TFLOP/s)."""
+import argparse
+import json
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+import torch  # noqa: E402
+
+from oracle import sda_oracle as O  # noqa: E402
+from sda_amd import ops, training  # noqa: E402
+from sda_amd.score import VPSDE  # noqa: E402
+
+PEAK_FP32_MATRIX = 157.3e12
+
+
+def _timed(fn, steps, warmup):
+    for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(steps):
+        fn()
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1) / steps
+
+
+def configs(dev):
+    from sda_amd.experiments.kolmogorov import make_score
+    from sda_amd.experiments.lorenz import make_global_score
+    torch.manual_seed(0)
+    kol = make_score(window=5, embedding=64, hidden_channels=(96, 192, 384), hidden_blocks=(3, 3, 3), size=64).kernel.to(dev)
+    kol_cfg = O.UNetConfig(11, 10, 64, (96, 192, 384), (3, 3, 3), 3, 2, 'SiLU', 2, 'circular')
+    lor = make_global_score(embedding=32, hidden_channels=(64,), hidden_blocks=(3,)).to(dev)
+    lor_cfg = O.UNetConfig(3, 3, 32, (64,), (3,), 3, 2, 'SiLU', 1, 'zeros')
+    return [
+        dict(name='kolmogorov_train', net=kol, shape=(10, 64, 64), batch=32, prefix='',
+             eps=lambda sd, x, t: O.score_unet(sd, '', kol_cfg, x, t, sd['forcing'])),
+        dict(name='lorenz_global_train', net=lor, shape=(32, 3), batch=64, prefix='score.',
+             eps=lambda sd, x, t: O.mc_score_wrapper(lambda xx, tt, c=None: O.score_unet(sd, 'score.', lor_cfg, xx, tt), x, t)),
+    ]
+
+
+def hip_step(cfg, dev):
+    net = cfg['net']
+    sde = VPSDE(net, shape=cfg['shape']).to(dev)
+    opt = torch.optim.AdamW(net.parameters(), lr=1e-4, weight_decay=1e-3)
+    x = torch.randn(cfg['batch'], *cfg['shape'], device=dev)
+
+    def step():
+        with training.parameter_gradients():
+            loss = sde.loss(x)
+            loss.backward()
+        opt.step()
+        opt.zero_grad()
+    return step, sde, x
+
+
+def oracle_step(cfg, dev):
+    """The same step on the oracle's functional net (fp32, torch autograd, the framework's own GPU kernels)."""
+    names = {k for k, _ in cfg['net'].named_parameters()}
+    sd = {k: v.detach().clone().float().to(dev).requires_grad_(k in names) for k, v in cfg['net'].state_dict().items()}
+    opt = torch.optim.AdamW([sd[k] for k in sorted(names)], lr=1e-4, weight_decay=1e-3)
+    sched = O.Schedule()
+    x = torch.randn(cfg['batch'], *cfg['shape'], device=dev)
+
+    def step():
+        with torch.device(dev):                          # (the oracle builds its time-feature frequencies on the default device)
+            t = torch.rand(x.shape[0], device=dev)
+            e = torch.randn_like(x)
+            tb = t.reshape((-1,) + (1,) * (x.dim() - 1))
+            xt = sched.mu(tb) * x + sched.sigma(tb) * e
+            loss = (cfg['eps'](sd, xt, t) - e).square().mean()
+            loss.backward()
+        opt.step()
+        opt.zero_grad()
+    return step
+
+
+def family_profile(sde, x):
+    """One training step under ops.ConvProfile: kernel time by family, forward and backward apart."""
+    prof = ops.ConvProfile()
+    ops.conv_profile = prof
+    try:
+        with training.parameter_gradients():
+            e0, e1, e2 = (torch.cuda.Event(enable_timing=True) for _ in range(3))
+            e0.record()
+            loss = sde.loss(x)
+            e1.record()
+            fwd_n = len(prof.records)
+            fwd_mem = len(prof.mem_records)
+            loss.backward()
+            e2.record()
+        torch.cuda.synchronize()
+    finally:
+        ops.conv_profile = None
+    fam = {}
+    for i, (a, b, flops, f) in enumerate(prof.records):
+        key = ('forward.' if i < fwd_n else ('wgrad' if f == 'wgrad' else 'input_vjp.')) + ('' if f == 'wgrad' else f)
+        r = fam.setdefault(key, dict(launches=0, ms=0.0, tflop=0.0))
+        r['launches'] += 1
+        r['ms'] += a.elapsed_time(b)
+        r['tflop'] += flops / 1e12
+    for i, (a, b, nb, k) in enumerate(prof.mem_records):
+        key = ('forward.' if i < fwd_mem else 'backward.') + k
+        r = fam.setdefault(key, dict(launches=0, ms=0.0, gbytes=0.0))
+        r['launches'] += 1
+        r['ms'] += a.elapsed_time(b)
+        r['gbytes'] += nb / 1e9
+    for r in fam.values():
+        r['ms'] = round(r['ms'], 4)
+        if 'tflop' in r:
+            r['tflop_s'] = round(r['tflop'] / max(r['ms'], 1e-9) * 1e3, 2)
+    wg = fam.get('wgrad')
+    if wg:
+        wg['fraction_of_fp32_peak'] = round(wg['tflop_s'] * 1e12 / PEAK_FP32_MATRIX, 3)
+    return dict(families=fam, loss_ms=round(e0.elapsed_time(e1), 3), backward_ms=round(e1.elapsed_time(e2), 3))
+
+
+def modulation_share(cfg, dev, steps):
+    """Time of the torch-autograd pieces of the route (time embedding + concatenated project Linear, forward and backward)."""
+    net = cfg['net']
+    kernel = net.score if cfg['prefix'] == 'score.' else net
+    engine = kernel.network.engine()
+    t = torch.rand(cfg['batch'], device=dev)
+
+    def run():
+        with training.parameter_gradients():
+            emb = kernel.embedding(t)
+            m = engine.modulation_train(emb)
+            m.sum().backward()
+    return _timed(run, steps, 2)
+
+
+def wgrad_shapes(dev, steps):
+    """The block conv1 weight gradient (modulation + LayerNorm loader, circular) at the three Kolmogorov block shapes."""
+    from sda_amd.ops import make_conv_desc
+    rows = []
+    for c, s in ((96, 64), (192, 32), (384, 16)):
+        n = 32
+        a = torch.randn(n, c, s, s, device=dev)
+        mod = torch.randn(n, c, device=dev)
+        mean = torch.zeros(n * s * s, device=dev)
+        rstd = torch.ones(n * s * s, device=dev)
+        g = torch.randn(n, c, s, s, device=dev)
+        dw = torch.empty(c, c, 3, 3, device=dev)
+        db = torch.empty(c, device=dev)
+        d = make_conv_desc(x_ptr=a.data_ptr(), n=n, cx=c, hs=s, ws=s, x_sc=s * s, x_sy=s, x_sx=1, x_sn_outer=c * s * s, w_ptr=0,
+                           cin_pad=0, cout_pad=0, cout=c, kh=3, kw=3, out_ptr=0, ho=s, wo=s, mt=1, circular=True,
+                           mod_ptr=mod.data_ptr(), mod_sn=c, ln_mean_ptr=mean.data_ptr(), ln_rstd_ptr=rstd.data_ptr())
+        ms = _timed(lambda: ops.conv_wgrad(d, g, dw, db, False), steps, 3)
+        flops = ops.wgrad_flops(d)
+        rows.append(dict(channels=c, size=s, batch=n, ms=round(ms, 4), tflop_s=round(flops / ms / 1e9, 2),
+                         fraction_of_fp32_peak=round(flops / ms / 1e9 * 1e12 / PEAK_FP32_MATRIX, 3)))
+    return rows
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--steps', type=int, default=10)
+    ap.add_argument('--warmup', type=int, default=3)
+    ap.add_argument('--out', default=None)
+    args = ap.parse_args()
+    dev = torch.device('cuda:0')
+    result = dict(device=torch.cuda.get_device_name(dev), steps=args.steps, warmup=args.warmup, configs={})
+    for cfg in configs(dev):
+        step, sde, x = hip_step(cfg, dev)
+        ms = _timed(step, args.steps, args.warmup)
+        prof = family_profile(sde, x)
+        mod_ms = modulation_share(cfg, dev, args.steps)
+        base_ms = _timed(oracle_step(cfg, dev), args.steps, args.warmup)
+        result['configs'][cfg['name']] = dict(
+            batch=cfg['batch'], shape=list(cfg['shape']), ms_per_step=round(ms, 3), oracle_fp32_autograd_ms_per_step=round(base_ms, 3),
+            speedup_vs_oracle=round(base_ms / ms, 3), modulation_autograd_ms=round(mod_ms, 4),
+            modulation_share_of_step=round(mod_ms / ms, 4), profile=prof)
+        print(json.dumps({cfg['name']: result['configs'][cfg['name']]}), flush=True)
+    result['wgrad_block_shapes'] = wgrad_shapes(dev, args.steps)
+    result['time'] = time.strftime('%Y-%m-%dT%H:%M:%S')
+    line = json.dumps(result)
+    print(line)
+    if args.out:
+        with open(args.out, 'w') as f:
+            json.dump(result, f, indent=1)
+
+
+if __name__ == '__main__':
+    main()
