@@ -4,7 +4,7 @@ fixtures without a GPU.
 
 The shim monkeypatches `sda_amd.ops` inside a test:
   * convolutions go through libsda_emu.so -- the host replay of the gfx950 conv tile algorithm (same planner and
-    index helpers as the device kernel);
+    index helpers as the device kernel); so do the training route's weight / bias gradients (csrc/conv_wgrad.hip);
   * the small streaming kernels are replaced by a few lines of torch each.
 Nothing here is reachable from the product: sda_amd itself has no CPU path and raises on CPU tensors.
 """
@@ -15,7 +15,7 @@ import torch
 from sda_amd import build as sbuild
 from sda_amd import engine as E
 from sda_amd import ops
-from sda_amd._lib import ConvDesc
+from sda_amd._lib import ConvDesc, SdaHipError, WgradDesc
 
 _ACT = {1: torch.nn.functional.silu, 2: torch.relu, 3: torch.nn.functional.elu, 4: torch.nn.functional.gelu,
         5: torch.nn.functional.selu}
@@ -26,6 +26,10 @@ def install(monkeypatch):
     emu.sda_conv_igemm_emulate.restype = ctypes.c_int
     emu.sda_conv_igemm_emulate.argtypes = [ctypes.POINTER(ConvDesc)]
     emu.sda_pack_conv_weight_host.restype = None
+    emu.sda_conv_wgrad_emulate.restype = ctypes.c_int
+    emu.sda_conv_wgrad_emulate.argtypes = [ctypes.POINTER(WgradDesc)]
+    emu.sda_conv_wgrad_work_floats.restype = ctypes.c_int64
+    emu.sda_conv_wgrad_work_floats.argtypes = [ctypes.POINTER(WgradDesc)]
 
     def _dev(*ts):
         for t in ts:
@@ -38,6 +42,35 @@ def install(monkeypatch):
     def pack(w, cout, cin, kh, kw, transpose, keep, dst, k_pad, m_pad):
         emu.sda_pack_conv_weight_host(ctypes.c_void_p(w.data_ptr()), cout, cin, kh, kw, int(transpose), keep,
                                       ctypes.c_void_p(dst.data_ptr()), k_pad, m_pad)
+
+    def conv_wgrad(conv, g, dw, db, accumulate, slabs=0):
+        # the training route's weight / bias gradient: the host replay of csrc/conv_wgrad.hip (same refusals as ops.conv_wgrad)
+        _dev(g, dw, db)
+        if not g.is_contiguous() or tuple(g.shape) != (conv.n, conv.cout, conv.ho, conv.wo):
+            raise SdaHipError(f'conv_wgrad: cotangent must be planar contiguous {(conv.n, conv.cout, conv.ho, conv.wo)}, got {tuple(g.shape)}')
+        cin = conv.cx + conv.cctx
+        if not dw.is_contiguous() or dw.numel() != conv.cout * cin * conv.kh * conv.kw or (db is not None and db.numel() != conv.cout):
+            raise SdaHipError('conv_wgrad: dw / db do not match the layer')
+        d = ops.wgrad_desc(conv, g, dw, db, accumulate, slabs)
+        floats = int(emu.sda_conv_wgrad_work_floats(ctypes.byref(d)))
+        assert floats > 0, f'wgrad planner rc={floats}'
+        work = torch.full((floats,), float('nan'))       # (an unwritten slab would show)
+        d.work = work.data_ptr()
+        rc = emu.sda_conv_wgrad_emulate(ctypes.byref(d))
+        assert rc == 0, f'wgrad emulator rc={rc}'
+
+    def plane_sum(x, y, out, out_sn, sum_images, accumulate):
+        # out is a (possibly offset) view whose first element is row 0, channel 0: rows of out_sn floats from there
+        _dev(x, y, out)
+        if not x.is_contiguous() or (y is not None and (not y.is_contiguous() or y.shape != x.shape)):
+            raise SdaHipError('plane_sum: operands must be planar contiguous and alike')
+        n, c = x.shape[:2]
+        s = (x if y is None else x - y).reshape(n, c, -1).sum(-1)
+        rows = 1 if sum_images else n
+        if sum_images:
+            s = s.sum(0, keepdim=True)
+        tgt = torch.as_strided(out, (rows, c), (out_sn, 1))
+        tgt.copy_(tgt + s if accumulate else s)
 
     def _u(x, mod, mod_sn):
         n, c = x.shape[:2]
@@ -172,13 +205,14 @@ def install(monkeypatch):
     def gauss_cotangent(y, ax, std, gamma, mu, sigma):
         return (y - ax) / (std ** 2 + gamma * (torch.as_tensor(sigma) / torch.as_tensor(mu)) ** 2)
 
-    for name, fn in dict(_dev=_dev, randn_rows=randn_rows, gauss_cotangent=gauss_cotangent, conv_igemm=conv_igemm, pack_conv_weight=pack, ln_stats=ln_stats, ln_apply=ln_apply,
+    for name, fn in dict(_dev=_dev, randn_rows=randn_rows, gauss_cotangent=gauss_cotangent, conv_igemm=conv_igemm, conv_wgrad=conv_wgrad, plane_sum=plane_sum, pack_conv_weight=pack, ln_stats=ln_stats, ln_apply=ln_apply,
                          ln_bwd=ln_bwd, time_embed=time_embed, linear_small=linear_small, fold=fold,
                          fold_adjoint=fold_adjoint, unfold_adjoint=unfold_adjoint, pc_predict=pc_predict,
                          sumsq_partial=sumsq_partial, pc_correct=pc_correct, denoise=denoise,
                          guided_combine=guided_combine, linear=linear, row_ln=row_ln, row_ln_bwd=row_ln_bwd).items():
         monkeypatch.setattr(ops, name, fn)
     monkeypatch.setattr(ops, 'WINOGRAD', False)      # the Winograd form has no host replay; the direct form is emulated
+    monkeypatch.setattr(ops, 'WINOGRAD4', False)     # (nor has its second-generation kernel: PackedConv would pack for it through the device library)
     monkeypatch.setattr(ops, 'PARITY4', False)       # (the one-launch parity kernel is a device kernel: the four class launches are emulated)
     monkeypatch.setattr(ops, 'NET1D', False)         # (likewise the whole-net 1-D kernel)
     monkeypatch.setattr(ops, 'POOLED', False)        # (and the pooled-output form of the tails' VJP: plain launch + pooling reader)

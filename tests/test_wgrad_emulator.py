@@ -106,3 +106,37 @@ def test_wgrad_without_bias(emu):
     work = torch.empty(work_floats(emu, d))
     assert emu.sda_conv_wgrad_emulate(ctypes.byref(wgrad_desc(case, dw, None, work))) == 0
     assert rel_err(dw, reference(case)[0]) <= 1e-5
+
+
+def load_wgrad_fuzz():
+    import importlib.util
+    import os
+    spec = importlib.util.spec_from_file_location(
+        'wgrad_fuzz', os.path.join(os.path.dirname(os.path.abspath(__file__)), 'fuzz', 'wgrad_fuzz.py'))
+    fuzz = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(fuzz)
+    return fuzz
+
+
+FUZZ_SEED, FUZZ_CASES = 31, 60        # (tests/test_gpu_training.py runs the same draws on the device)
+
+
+def test_wgrad_fuzz_sample():
+    """A bounded sample of tests/fuzz/wgrad_fuzz.py on the emulator: random descriptors over the source views (planar, channel-last,
+    window view with an image offset), shared / per-image context, every loader mode, kernel sizes 1..7 with kh != kw, explicit
+    padding, ragged cout tiles, slab counts, accumulation and a missing bias gradient.  No case is skipped."""
+    import random
+    fuzz = load_wgrad_fuzz()
+    backend = fuzz.emulator()
+    rng = random.Random(FUZZ_SEED)
+    bad, seen = [], set()
+    for i in range(FUZZ_CASES):
+        cfg, msg = fuzz.one_case(rng, backend, i)
+        seen |= {cfg['mode'], 'window_off' if cfg['window'] and cfg['lo'] else '', 'chan_last' if cfg['chan_last'] else '',
+                 'ctx_per_image' if cfg['ctx_per_image'] else '', 'pad' if cfg['pad'] else '', 'mt4_ragged' if cfg['cout'] in (97, 100, 130) else '',
+                 'khkw' if cfg['kh'] != cfg['kw'] and not cfg['one_d'] else '', 'cx1' if cfg['cx'] == 1 else ''}
+        if msg:
+            bad.append((i, msg, cfg))
+    assert not bad, '\n'.join(f'case {i}: {m}\n    {c}' for i, m, c in bad)
+    # the sample reaches every corner it is there for
+    assert seen >= set(fuzz.MODES) | {'window_off', 'chan_last', 'ctx_per_image', 'pad', 'mt4_ragged', 'khkw', 'cx1'}, seen

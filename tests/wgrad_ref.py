@@ -24,11 +24,16 @@ def _stats(v):
     return mean.float().reshape(-1).contiguous(), (1.0 / torch.sqrt(var + O.LN_EPS)).float().reshape(-1).contiguous()
 
 
-def make_case(kind, dev, *, cin=8, cout=8, n=2, h=6, w=6, k=3, circular=True, one_d=False, act='SiLU', seed=0):
-    """-> dict(conv=ConvDesc, g, keep, v64 (the conv's virtual input, float64, (n, cin_total, hv, wv)), stride, circular, kh, kw)."""
+def make_case(kind, dev, *, cin=8, cout=8, n=2, h=6, w=6, k=3, circular=True, one_d=False, act='SiLU', seed=0, ksize=None, pad=None,
+              n_off=0):
+    """-> dict(conv=ConvDesc, g, keep, v64 (the conv's virtual input, float64, (n, cin_total, hv, wv)), stride, circular, kh, kw).
+    ksize: (kh, kw) instead of k x k; pad: explicit (pad_h, pad_w) instead of k // 2; n_off ('head0_window'): the layer reads the
+    windows from n_off on (a recomputed chunk's view of the trajectory)."""
     gen = torch.Generator().manual_seed(seed)
     rnd = lambda *s: torch.randn(*s, generator=gen)
     kh, kw = (1, k) if one_d else (k, k)
+    if ksize is not None:
+        kh, kw = ksize
     if one_d:
         h = 1
     keep = []
@@ -42,16 +47,16 @@ def make_case(kind, dev, *, cin=8, cout=8, n=2, h=6, w=6, k=3, circular=True, on
         X = rnd(B, L, C, h, w)
         nw = L - 2 * order
         cx = wl * C
-        n = B * nw
+        n = B * nw - n_off
         ctx = rnd(1, h, w)
         x = X.to(dev)
         cx_tot = cx + 1
-        v = torch.stack([X[b, i:i + wl].reshape(cx, h, w) for b in range(B) for i in range(nw)])
+        v = torch.stack([X[b, i:i + wl].reshape(cx, h, w) for b in range(B) for i in range(nw)])[n_off:]
         v = torch.cat([v, ctx.expand(n, 1, h, w)], dim=1)
         ctxd = ctx.reshape(-1).contiguous().to(dev)
         keep += [x, ctxd]
         src = dict(x_ptr=x.data_ptr(), n=n, cx=cx, hs=h, ws=w, x_sn_outer=L * C * h * w, x_sn_inner=C * h * w, n_inner=nw,
-                   x_sc=h * w, x_sy=w, x_sx=1)
+                   x_n_off=n_off, x_sc=h * w, x_sy=w, x_sx=1)
         extra = dict(ctx_ptr=ctxd.data_ptr(), cctx=1, ctx_sn=0)
         cin = cx_tot
     elif kind == 'head0_ctx':
@@ -97,11 +102,13 @@ def make_case(kind, dev, *, cin=8, cout=8, n=2, h=6, w=6, k=3, circular=True, on
             raise ValueError(kind)
     hv, wv = v.shape[2], v.shape[3]
     ho, wo = conv_out_size(hv, kh, stride[0]), conv_out_size(wv, kw, stride[1])
+    if pad is not None:
+        ho, wo = (hv + 2 * pad[0] - kh) // stride[0] + 1, (wv + 2 * pad[1] - kw) // stride[1] + 1
     g = rnd(n, cout, ho, wo).to(dev).contiguous()
-    conv = make_conv_desc(**src, w_ptr=0, cin_pad=0, cout_pad=0, cout=cout, kh=kh, kw=kw, out_ptr=0, ho=ho, wo=wo, mt=1,
+    conv = make_conv_desc(pad=pad, **src, w_ptr=0, cin_pad=0, cout_pad=0, cout=cout, kh=kh, kw=kw, out_ptr=0, ho=ho, wo=wo, mt=1,
                           stride_h=stride[0], stride_w=stride[1], circular=circular, up_h=up[0], up_w=up[1], **extra)
     return dict(conv=conv, g=g, keep=keep, v64=v.double(), stride=stride, circular=circular, kh=kh, kw=kw, cin=cin, cout=cout,
-                one_d=one_d)
+                one_d=one_d, pad=pad)
 
 
 def reference(case):
@@ -109,6 +116,8 @@ def reference(case):
     v = case['v64']
     cout, cin, kh, kw = case['cout'], v.shape[1], case['kh'], case['kw']
     g = case['g'].detach().double().cpu()
+    if case.get('pad') is not None:
+        return reference_general(v, g, cout, kh, kw, case['stride'], case['circular'], case['pad'])
     W = torch.zeros(cout, cin, kh, kw, dtype=torch.float64, requires_grad=True)
     b = torch.zeros(cout, dtype=torch.float64, requires_grad=True)
     mode = 'circular' if case['circular'] else 'zeros'
@@ -132,3 +141,20 @@ def wgrad_desc(case, dw, db, work=None, slabs=0, accumulate=False):
 
 def work_floats(lib, d) -> int:
     return int(lib.sda_conv_wgrad_work_floats(ctypes.byref(d)))
+
+
+def reference_general(v64, g64, cout, kh, kw, stride, circular, pad=None):
+    """float64 (dW, db) for a 2-D layer over the virtual input ``v64`` (n, cin, hv, wv) with any (kh, kw) and stride.  ``pad``
+    None: the oracle's convolution (padding k // 2).  ``pad`` = (ph, pw): the explicit padding of the descriptor, applied by
+    hand (zeros or wrap-around) in front of a valid convolution."""
+    import torch.nn.functional as F
+    W = torch.zeros(cout, v64.shape[1], kh, kw, dtype=torch.float64, requires_grad=True)
+    b = torch.zeros(cout, dtype=torch.float64, requires_grad=True)
+    if pad is None:
+        out = O._conv(v64, W, b, 2, tuple(stride), 'circular' if circular else 'zeros')
+    else:
+        ph, pw = pad
+        vp = F.pad(v64, (pw, pw, ph, ph), mode='circular') if circular else F.pad(v64, (pw, pw, ph, ph))
+        out = F.conv2d(vp, W, b, stride=tuple(stride))
+    assert out.shape == g64.shape, (tuple(out.shape), tuple(g64.shape))
+    return torch.autograd.grad(out, (W, b), g64)
