@@ -396,17 +396,23 @@ int sda_row_ln_bwd(const float* gh, const float* x, int rows, int f, const float
 /* A whole ResMLP (sda/nn.py:31-71: per width step an optional Linear, then x + Lin2(act(Lin1(LN(x))))) in ONE launch, and its
  * input VJP in one more (csrc/mlp1d.hip; ABI v7) -- the Lorenz local score kernel of experiments/lorenz/utils.py:45-59.
  * The network is a list of GEMMs in forward order: kind 0 = nn.Linear; kind 1 = first half of a residual block (LayerNorm -> Linear ->
- * activation), always followed by kind 2 = its second half (Linear + residual).  Widths <= 128.
- *   w:    per GEMM one SLAB at float offset w_off[g] (a multiple of 4): the matrix Wp = W zero padded to [16 mf][16 kq] (mf = 1 if out <= 16
- *         else 8 output fragments; kq = 1 / 4 / 8 K quads for in <= 16 / 64 / 128) in MFMA A-operand order [m mf][sq kq][lane 64][4] --
- *         element e of lane (k = lane >> 4, li = lane & 15) = Wp[16 m + li][16 sq + 4 k + e] --, zero padded to a multiple of 4096 floats;
- *         sda_mlp_slab_floats(in, out) = its length.  sda_mlp_fwd: W = torch's [out][in] weight; sda_mlp_bwd: W = its transpose (the slab
- *         of (out -> in)), same offsets table;
- *   bias: [16 mf] zero padded at float offset b_off[g] (a multiple of 4; forward only);
+ * activation), always followed by kind 2 = its second half (Linear + residual).  Widths <= 256 (ABI v13; <= 128 before: a net whose
+ * widths are all <= 128 runs the same kernels on the same bytes as then).
+ *   w:    per GEMM one SLAB at float offset w_off[g] (a multiple of 4).  Both sides <= 128: the matrix Wp = W zero padded to
+ *         [16 mf][16 kq] (mf = 1 if out <= 16 else 8 output fragments; kq = 1 / 4 / 8 K quads for in <= 16 / 64 / 128) in MFMA A-operand
+ *         order [m mf][sq kq][lane 64][4] -- element e of lane (k = lane >> 4, li = lane & 15) = Wp[16 m + li][16 sq + 4 k + e] --, zero
+ *         padded to a multiple of 4096 floats (one UNIT).  A side above 128 pads to 256 (mf = 16 / kq = 16) and splits in two halves of
+ *         128: the slab is then the units of Wp's quarters Wp[128 nh ..][128 kh ..] (halves, when the other side is <= 128 -- that side
+ *         keeps its own padding 16 / (64) / 128), each laid out and padded as above, in the order [output half nh][input half kh]:
+ *         256 x 256 = 4 x 16384 floats, 47 -> 256 = 2 x 8192, 256 -> 15 = 2 x 4096.  sda_mlp_slab_floats(in, out) = the slab's length
+ *         (SDA_E_UNSUPPORTED above 256).  sda_mlp_fwd: W = torch's [out][in] weight; sda_mlp_bwd: W = its transpose (the slab of
+ *         (out -> in)), same offsets table;
+ *   bias: [16 mf] zero padded at float offset b_off[g] (a multiple of 4; forward only).  All padded biases together: <= 4096 floats (they
+ *         stay in LDS for the launch -- sixteen 256-wide GEMMs), else SDA_E_UNSUPPORTED;
  *   x / out: row-major (rows, features) with row strides x_ld / out_ld (sda_mlp_bwd: x = cotangent rows of width out_f[last], out =
  *         input-gradient rows of width in_f[0]).
- *   a_save / z_save [nres][rows][save_ld >= 128], mean_save / rstd_save [nres][rows] (block strides save_stride / stat_stride): written by
- *         the forward when non-NULL (all four or none), read by the VJP.
+ *   a_save / z_save [nres][rows][save_ld >= 128; >= 256 when a residual block is wider than 128], mean_save / rstd_save [nres][rows]
+ *         (block strides save_stride / stat_stride): written by the forward when non-NULL (all four or none), read by the VJP.
  * SDA_E_UNSUPPORTED outside the kernel's range (callers run the per-layer kernels sda_linear / sda_row_ln). */
 #define SDA_MLP_MAXG 32
 typedef struct sda_mlp_desc {

@@ -16,7 +16,25 @@
 //     fragments lane-linearly (conflict free), one 16-byte read per four MFMAs; ONE workgroup barrier per GEMM (slab hand-off);
 //   * LayerNorm is wave private: a row's 128 features sit in 4 lanes x 32 registers -- lane-local sums + two shuffles;
 //   * saved for the VJP (16-byte stores): block inputs, pre-activations, mean / rstd -- as the per-layer path saved.
-// Widths are padded: outputs to 16 or 128 features, contraction lengths to 16 / 64 / 128.
+// Widths are padded: outputs to 16 / 128 / 256 features, contraction lengths to 16 / 64 / 128 / 256.
+// Wide nets (a GEMM side in 129 .. 256: the reference's TRAINED local nets are 256 wide, experiments/lorenz/train.py:30-44) run the
+// mlp_fwd_kernel_wide / mlp_bwd_kernel_wide kernels at the end of this file; nets whose GEMMs are all <= 128 run the kernels above them,
+// untouched.  The plan:
+//   * still row private, 16 rows x ALL 256 features per wave: sixteen D fragments = 64 registers per activation array, and a GEMM's D
+//     fragments are still the next GEMM's B operands as they stand.  LayerNorm: 4 lanes x 64 registers, the same two passes + two shuffles;
+//   * a wide GEMM is streamed through LDS as UNITS: a side above 128 pads to 256 and splits in two halves of 128, so a 256 x 256 layer is
+//     four ordinary 128 x 128 slabs, in memory in the order [output half][input half]; the second input half accumulates on the first
+//     (its C operand is the accumulator).  Units pass through the two slab buffers exactly as whole GEMMs do above: unit u multiplies
+//     (ml_mm, shared with the narrow kernels) while unit u + 1 is copied into the other buffer.  ONE barrier per unit: four per
+//     256 x 256 GEMM, i.e. still one per 256 MFMAs of a wave;
+//   * registers (one wave per SIMD: 512, architectural + accumulation unified on gfx950): forward a (residual stream), h (GEMM input),
+//     acc = 192, + 64 of A fragments (ml_mm's double buffer) + 16-32 staging; VJP gacc, h, acc likewise.  What differs from the narrow
+//     kernels to stay inside the file: the bias is added from LDS behind the GEMM (not 32 registers of C operand under the first
+//     MFMAs), both saved streams are stored behind the block's first GEMM (no copy of z rides the second), the VJP reads the saved
+//     streams behind the multiply, the pre-activations in groups of four fragments.  Compiled: no spill, no scratch instruction
+//     (tests/test_isa_guard_mlp.py holds that);
+//   * LDS: 2 x 64 KiB unit buffers + 16 KiB of biases = 144 KiB of 160, as the narrow kernels.  The bias region holds every GEMM's
+//     padded bias: sixteen 256-wide GEMMs; beyond that SDA_E_UNSUPPORTED.
 // Roofline: the Lorenz local net is 0.34 MFLOP per window and direction; at 62 464 windows (eval.py's batch) 21.5 GFLOP = 0.14 ms of
 // fp32 MFMA time per direction.
 #include "sda_common.hpp"
@@ -187,12 +205,66 @@ __device__ __forceinline__ float ml_rowsum(float s) {
     return s;
 }
 
-// the wave's rows x `width` features of a row-major source -> D-layout registers h[m][r] = x[row][16 m + 4 kq + r] (zero beyond)
-__device__ __forceinline__ void ml_load_rows(const float* src, int64_t ld, int width, const MlCtx& c, ml_f32x4 (&h)[8]) {
-    const float* xr = src + (c.rowok ? c.row : 0) * ld;
-    const int nm = width <= 16 ? 1 : (width <= 64 ? 4 : 8);
+// LayerNorm over a row's features (4 lanes x 4 NF registers): h = (a - mean) rstd, two passes.  FULL: the width fills its fragments (256 of
+// 256): no per-value masks.  TWIN of the `ln` lambda of mlp_fwd_kernel (and ml_ln_bwd of the `lnb` lambda of mlp_bwd_kernel): the narrow
+// kernels keep their inline text so that their machine code stays what it was (tests/test_isa_guard_mlp.py pins it) -- a change to one
+// of a pair belongs in the other.
+template <bool FULL, int NF>
+__device__ __forceinline__ void ml_ln(const ml_f32x4 (&a)[NF], ml_f32x4 (&h)[NF], int cw, const MlCtx& c, float inv_c, float inv_v, float eps,
+                                      float& mean, float& rstd) {
+    float s = 0.f;
 #pragma unroll
-    for (int m = 0; m < 8; ++m) {
+    for (int m = 0; m < NF; ++m)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) s += (FULL || 16 * m + 4 * c.kq + r < cw) ? a[m][r] : 0.f;
+    mean = ml_rowsum(s) * inv_c;
+    s = 0.f;
+#pragma unroll
+    for (int m = 0; m < NF; ++m)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const float dl = a[m][r] - mean;
+            h[m][r] = dl;
+            s += (FULL || 16 * m + 4 * c.kq + r < cw) ? dl * dl : 0.f;
+        }
+    rstd = __builtin_amdgcn_rsqf(ml_rowsum(s) * inv_v + eps);
+#pragma unroll
+    for (int m = 0; m < NF; ++m)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) h[m][r] = (FULL || 16 * m + 4 * c.kq + r < cw) ? h[m][r] * rstd : 0.f;
+}
+// its adjoint: g += LN^T(gh) = rstd (gh - mean_c(gh) - x_hat mean'_c(gh x_hat)); sv = the block input on entry, x_hat on return
+template <bool FULL, int NF>
+__device__ __forceinline__ void ml_ln_bwd(ml_f32x4 (&sv)[NF], const ml_f32x4 (&acc)[NF], ml_f32x4 (&gacc)[NF], int cw, const MlCtx& c,
+                                          float inv_c, float inv_v, float mean, float rs) {
+    float s1 = 0.f, s2 = 0.f;
+#pragma unroll
+    for (int m = 0; m < NF; ++m)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const bool fok = FULL || 16 * m + 4 * c.kq + r < cw;
+            const float xh = fok ? (sv[m][r] - mean) * rs : 0.f;
+            sv[m][r] = xh;
+            const float gv = fok ? acc[m][r] : 0.f;
+            s1 += gv; s2 += gv * xh;
+        }
+    const float av_ = ml_rowsum(s1) * inv_c, bv_ = ml_rowsum(s2) * inv_v;
+#pragma unroll
+    for (int m = 0; m < NF; ++m)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const bool fok = FULL || 16 * m + 4 * c.kq + r < cw;
+            gacc[m][r] += fok ? rs * (acc[m][r] - av_ - sv[m][r] * bv_) : 0.f;
+        }
+}
+
+// the wave's rows x `width` features of a row-major source -> D-layout registers h[m][r] = x[row][16 m + 4 kq + r] (zero beyond)
+template <int NF>
+__device__ __forceinline__ void ml_load_rows(const float* src, int64_t ld, int width, const MlCtx& c, ml_f32x4 (&h)[NF]) {
+    const float* xr = src + (c.rowok ? c.row : 0) * ld;
+    const int nm = width <= 16 ? 1 : (width <= 64 ? 4 : ((NF == 8 || width <= 128) ? 8 : 16));
+#pragma unroll
+    for (int m = 0; m < NF; ++m) {
         h[m] = ml_f32x4{0.f, 0.f, 0.f, 0.f};
         if (m < nm) {                                      // (wave uniform)
 #pragma unroll
@@ -205,12 +277,13 @@ __device__ __forceinline__ void ml_load_rows(const float* src, int64_t ld, int w
     }
 }
 
-__device__ __forceinline__ void ml_store_rows(float* dst, int64_t ld, int width, const MlCtx& c, const ml_f32x4 (&v)[8]) {
+template <int NF>
+__device__ __forceinline__ void ml_store_rows(float* dst, int64_t ld, int width, const MlCtx& c, const ml_f32x4 (&v)[NF]) {
     if (!c.rowok) return;
     float* o = dst + c.row * ld;
-    const int nm = width <= 16 ? 1 : 8;
+    const int nm = width <= 16 ? 1 : ((NF == 8 || width <= 128) ? 8 : 16);
 #pragma unroll
-    for (int m = 0; m < 8; ++m)
+    for (int m = 0; m < NF; ++m)
         if (m < nm) {
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
@@ -233,6 +306,80 @@ __device__ __forceinline__ MlWinRow ml_win_row(const sda_mlp_win& w, const MlCtx
 }
 // does `fold` read slot j of this window?  (the centre always; the leading slots of a trajectory's first window, the trailing ones of its last)
 __device__ __forceinline__ bool ml_win_sel(const MlWinRow& r, int j, int k) { return j == k || (r.first && j < k) || (r.lastw && j > k); }
+
+// Window mode's loader, epilogue and VJP loader for the wide kernels.  TWINS of the inline text of mlp_fwd_kernel<true> / mlp_bwd_kernel<true>
+// (kept inline there for the same reason as the LayerNorm pair above): a change to one of a pair belongs in the other.
+// the forward loader of window mode: the wave's rows in D layout
+template <int NF>
+__device__ __forceinline__ void ml_win_load(const sda_mlp_win& w, const MlCtx& c, ml_f32x4 (&a)[NF]) {
+    // row (b, i): features [0, WC) = x[b][i .. i + 2k][:] -- WC consecutive floats of the trajectory --, then the time embedding
+    const MlWinRow wr = ml_win_row(w, c);
+    const int wc = (w.len - w.nw + 1) * w.c;
+    const float* xr = w.x + ((int64_t)wr.b * w.len + wr.i) * w.c;
+#pragma unroll
+    for (int m = 0; m < NF; ++m) {
+        if (NF > 8 && 16 * m >= wc + w.emb_n) { a[m] = ml_f32x4{0.f, 0.f, 0.f, 0.f}; continue; }   // (wave uniform; the wide kernels only)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int f = 16 * m + 4 * c.kq + r;
+            const bool isx = f < wc, ise = !isx && f < wc + w.emb_n;
+            const float xv = xr[isx ? f : 0], ev = w.emb[ise ? f - wc : 0];
+            a[m][r] = !c.rowok ? 0.f : (isx ? xv : (ise ? ev : 0.f));
+        }
+    }
+}
+// the forward epilogue of window mode; a0 = the wave's output fragment (the window values of a row live in one D fragment)
+__device__ __forceinline__ void ml_win_fold(const sda_mlp_win& w, const MlCtx& c, const ml_f32x4& a0) {
+    // fold (score.py:155-164) + eps = (cx0 + cx1 sigma) x + cn s + the likelihood cotangent, as sda_net1d_fwd_fused's epilogue
+    if (c.rowok) {
+        const MlWinRow wr = ml_win_row(w, c);
+        const int k = (w.len - w.nw) / 2, wc = (2 * k + 1) * w.c;
+        const float mu = w.coef[0], sg = w.coef[1];
+        const bool bare = w.cx0 == 0.f && w.cx1 == 0.f && w.cn == 1.f;
+        const float cx = w.cx0 + w.cx1 * sg;
+        const float rr = __fdiv_rn(sg, mu);
+        const float var = __fadd_rn(__fmul_rn(w.std, w.std), __fmul_rn(w.gamma, __fmul_rn(rr, rr)));
+        const int n_oc = (w.c_stop - w.c_start + w.c_step - 1) / w.c_step;
+        const float* yb = w.y + (int64_t)wr.b * w.y_sn;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int f = 4 * c.kq + r;
+            if (f >= wc) continue;
+            const int j = f / w.c, ch = f - j * w.c;
+            if (!ml_win_sel(wr, j, k)) continue;
+            const int ps = wr.i + j;
+            const int64_t o = ((int64_t)wr.b * w.len + ps) * w.c + ch;
+            const float xv = w.x[o];
+            const float ov = a0[r];
+            const float e = bare ? ov : (xv * cx) + (w.cn * ov);
+            w.eps[o] = e;
+            const int crel = ch - w.c_start, prel = ps - w.p_start;
+            float gv = 0.f;
+            if (crel >= 0 && ch < w.c_stop && crel % w.c_step == 0 && prel >= 0 && ps < w.p_stop && prel % w.p_step == 0) {
+                const float xh = (xv - sg * e) / mu;
+                gv = __fdiv_rn(yb[(prel / w.p_step) * n_oc + crel / w.c_step] - xh, var);
+            }
+            w.ghat[o] = gv;
+        }
+    }
+}
+// the VJP's loader of window mode
+template <int NF>
+__device__ __forceinline__ void ml_win_cot(const sda_mlp_win& w, const MlCtx& c, ml_f32x4 (&gacc)[NF]) {
+    // the cotangent of the window outputs = fold's adjoint of cn ghat: slot j of window (b, i) receives ghat[b][i + j] where fold reads it
+    const MlWinRow wr = ml_win_row(w, c);
+    const int k = (w.len - w.nw) / 2, wc = (2 * k + 1) * w.c;
+#pragma unroll
+    for (int m = 0; m < NF; ++m) gacc[m] = ml_f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        const int f = 4 * c.kq + r, fc = f < wc ? f : 0;
+        const int j = fc / w.c, ch = fc - j * w.c;
+        const bool sel = c.rowok && f < wc && ml_win_sel(wr, j, k);
+        const float gv = w.ghat[sel ? ((int64_t)wr.b * w.len + wr.i + j) * w.c + ch : 0];
+        gacc[0][r] = sel ? gv * w.cn : 0.f;
+    }
+}
 
 // ------------------------------------------------------------------------------------------------------------ forward
 template <bool WIN>
@@ -539,28 +686,270 @@ __global__ __launch_bounds__(256) void mlp_bwd_kernel(const sda_mlp_desc d, cons
     }
 }
 
-static int mlp_check(const sda_mlp_desc* d, bool bwd, bool win) {
+// ------------------------------------------------------------------------------------------------------------ wide nets (a width in 129 .. 256)
+// See the file header ("Wide nets").  A GEMM is NH x KH UNITS -- ordinary slabs of at most 128 x 128 -- that follow each other in memory in the
+// order [n half][k half] and through the two LDS buffers exactly as whole GEMMs do in the kernels above: unit u multiplies out of buffer u & 1
+// while ml_mm copies unit u + 1 into the other one; one barrier per unit.
+__host__ __device__ __forceinline__ int mlw_mf(int out_f) { return out_f <= 128 ? ml_mf(out_f) : 16; }
+__host__ __device__ __forceinline__ int mlw_kq(int in_f) { return in_f <= 128 ? ml_kq(in_f) : 16; }
+// floats of one unit of GEMM (in_f -> out_f) in memory (all units of a GEMM have one shape), and of the whole GEMM
+__host__ __device__ __forceinline__ int mlw_unit_floats(int in_f, int out_f) { return ml_slab_floats(in_f > 128 ? 128 : in_f, out_f > 128 ? 128 : out_f); }
+__host__ __device__ __forceinline__ int mlw_slab_floats(int in_f, int out_f) {
+    return (in_f > 128 ? 2 : 1) * (out_f > 128 ? 2 : 1) * mlw_unit_floats(in_f, out_f);
+}
+
+// unit (NH, KH) of a GEMM: acc[8 NH ..] (+)= A h[8 KH ..]; `mfu` / `kqu` = the unit's fragment / K-quad counts (8 wherever the GEMM has a
+// second half on that axis: 12 instantiations of ml_mm in all)
+template <int NH, int KH>
+__device__ __forceinline__ void mlw_unit(const float* wl, int mfu, int kqu, const ml_f32x4 (&h)[16], ml_f32x4 (&acc)[16],
+                                         const ml_f32x4 (&cinit)[8], MlStage& st, const MlCtx& c) {
+    const ml_f32x4 (&hk)[8] = *reinterpret_cast<const ml_f32x4 (*)[8]>(&h[8 * KH]);
+    ml_f32x4 (&an)[8] = *reinterpret_cast<ml_f32x4 (*)[8]>(&acc[8 * NH]);
+    if (NH == 1 || mfu == 8) {
+        if (KH == 1 || kqu == 8) ml_mm<8, 8>(wl, hk, an, cinit, st, c, nullptr, hk);
+        else if (kqu == 4) ml_mm<8, 4>(wl, hk, an, cinit, st, c, nullptr, hk);
+        else ml_mm<8, 1>(wl, hk, an, cinit, st, c, nullptr, hk);
+    } else {
+        if (KH == 1 || kqu == 8) ml_mm<1, 8>(wl, hk, an, cinit, st, c, nullptr, hk);
+        else if (kqu == 4) ml_mm<1, 4>(wl, hk, an, cinit, st, c, nullptr, hk);
+        else ml_mm<1, 1>(wl, hk, an, cinit, st, c, nullptr, hk);
+    }
+}
+
+// one GEMM (in_f -> out_f, slab at `ws`): acc = W h.  `nsrc` / `npieces` = the first unit of the NEXT GEMM (staged under this one's last
+// unit); `buf` = the LDS buffer that holds this GEMM's first unit.
+__device__ __forceinline__ void mlw_gemm(float* lds, int& buf, const float* ws, int in_f, int out_f, const float* nsrc, int npieces,
+                                         const ml_f32x4 (&h)[16], ml_f32x4 (&acc)[16], MlStage& st, const MlCtx& c) {
+    const int nhn = out_f > 128 ? 2 : 1, khn = in_f > 128 ? 2 : 1;
+    const int mfu = nhn == 2 ? 8 : ml_mf(out_f), kqu = khn == 2 ? 8 : ml_kq(in_f);
+    const int usz = mlw_unit_floats(in_f, out_f);
+    ml_static_for<0, 4>([&](auto U_) {
+        constexpr int NH = decltype(U_)::value >> 1, KH = decltype(U_)::value & 1;
+        if (NH < nhn && KH < khn) {                        // (wave uniform)
+            const bool lastu = NH == nhn - 1 && KH == khn - 1;
+            st.src = ml_rsrc(lastu ? nsrc : ws + (NH * khn + KH + 1) * usz);
+            st.dst = reinterpret_cast<ml_f32x4*>(lds + (buf ^ 1) * ML_SLAB) + c.tid;
+            st.npieces = lastu ? npieces : usz / ML_PIECE;
+            const float* wl = lds + buf * ML_SLAB;
+            if constexpr (KH == 0) {
+                const ml_f32x4 zero[8] = {};
+                mlw_unit<NH, KH>(wl, mfu, kqu, h, acc, zero, st, c);
+            } else {
+                // the second K half accumulates on the first one's sums
+                mlw_unit<NH, KH>(wl, mfu, kqu, h, acc, *reinterpret_cast<const ml_f32x4 (*)[8]>(&acc[8 * NH]), st, c);
+            }
+            __syncthreads();                               // unit hand-off: the next unit is complete, this one's buffer is free
+            buf ^= 1;
+        }
+    });
+    if (nhn == 1) {
+#pragma unroll
+        for (int m = 8; m < 16; ++m) acc[m] = ml_f32x4{0.f, 0.f, 0.f, 0.f};
+    }
+}
+
+template <bool WIN>
+__global__ __launch_bounds__(256) void mlp_fwd_kernel_wide(const sda_mlp_desc d, const sda_mlp_win w) {
+    extern __shared__ __attribute__((aligned(16))) float ml_lds[];         // two unit buffers + the biases
+    MlCtx c;
+    ml_ctx(c, d);
+    MlMeta mc = ml_meta(d, 0), mn = ml_meta(d, 1);
+    MlStage st;
+    st.src = ml_rsrc(d.w + mc.w_off); st.toff = 16u * c.tid;
+    st.dst = reinterpret_cast<ml_f32x4*>(ml_lds) + c.tid;
+    st.npieces = mlw_unit_floats(mc.in_f, mc.out_f) / ML_PIECE;
+    for (int p = 0; p < st.npieces; ++p) { ml_f32x4 t[4]; st.issue(t, p); st.commit(t, p); }
+    float* const bl = ml_lds + 2 * ML_SLAB;
+    {
+        const int nb = d.b_off[d.ngemm - 1] + 16 * mlw_mf(d.out_f[d.ngemm - 1]);
+        for (int i = c.tid; i < nb; i += 256) bl[i] = d.bias[i];
+    }
+    // a = the residual stream, h = a GEMM's input, acc = its output: 3 x 64 registers (+ 64 of A fragments and the staging ones)
+    ml_f32x4 h[16], a[16], acc[16];
+    if constexpr (WIN) ml_win_load(w, c, a);
+    else ml_load_rows(d.x, d.x_ld, d.in_f[0], c, a);
+    __syncthreads();
+    const bool silu = d.act == SDA_ACT_SILU;
+    int rb = 0, buf = 0;
+    for (int g = 0; g < d.ngemm; ++g) {
+        const MlMeta mm = ml_meta(d, g + 2);
+        const bool last = g + 1 == d.ngemm;
+        const int cw = mc.in_f;
+        if (mc.kind == 1) {
+            const float inv_c = 1.f / (float)cw, inv_v = 1.f / (float)(d.unbiased ? cw - 1 : cw);
+            float mean, rstd;
+            if (cw == 256) ml_ln<true>(a, h, cw, c, inv_c, inv_v, d.eps, mean, rstd);
+            else ml_ln<false>(a, h, cw, c, inv_c, inv_v, d.eps, mean, rstd);
+            if (d.mean_save && c.kq == 0 && c.rowok) {
+                d.mean_save[(int64_t)rb * d.stat_stride + c.row] = mean;
+                d.rstd_save[(int64_t)rb * d.stat_stride + c.row] = rstd;
+            }
+        } else if (mc.kind == 0) {
+#pragma unroll
+            for (int m = 0; m < 16; ++m) h[m] = a[m];
+        }
+        mlw_gemm(ml_lds, buf, d.w + mc.w_off, mc.in_f, mc.out_f, d.w + (last ? 0 : mn.w_off),
+                 last ? 0 : mlw_unit_floats(mn.in_f, mn.out_f) / ML_PIECE, h, acc, st, c);
+        {
+            // + the bias, from LDS (as the C operand of the first MFMAs, the narrow kernel's way, its 32 registers come on top of a, h, acc and
+            // the A fragments: spills)
+            const float* bg = bl + mc.b_off + 4 * c.kq;
+            const int nm = mlw_mf(mc.out_f);
+#pragma unroll
+            for (int m = 0; m < 16; ++m)
+                if (m < nm) acc[m] += *reinterpret_cast<const ml_f32x4*>(bg + 16 * m);
+        }
+        if (mc.kind == 0) {
+#pragma unroll
+            for (int m = 0; m < 16; ++m) a[m] = acc[m];
+        } else if (mc.kind == 1) {
+            // z = W1 LN(a) + b1; both saved streams leave here, behind the GEMM (see the narrow kernel); h = act(z)
+            if (d.z_save && c.rowok) {
+                const int nm = mlw_mf(mc.out_f);
+                float* zp = d.z_save + (int64_t)rb * d.save_stride + c.row * d.save_ld + 4 * c.kq;
+                float* as = d.a_save + (int64_t)rb * d.save_stride + c.row * d.save_ld + 4 * c.kq;
+#pragma unroll
+                for (int m = 0; m < 16; ++m)
+                    if (m < nm) {
+                        *reinterpret_cast<ml_f32x4*>(zp + 16 * m) = acc[m];
+                        *reinterpret_cast<ml_f32x4*>(as + 16 * m) = a[m];
+                    }
+            }
+            auto epi = [&](auto SILU_) {
+#pragma unroll
+                for (int m = 0; m < 16; ++m) {
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) h[m][r] = decltype(SILU_)::value ? sda_act(SDA_ACT_SILU, acc[m][r]) : sda_act(d.act, acc[m][r]);
+                    // (64 independent chains: left free, the scheduler interleaves them all and their temporaries spill)
+                    if (m & 1) __builtin_amdgcn_sched_barrier(0);
+                }
+            };
+            if (silu) epi(std::true_type{});
+            else epi(std::false_type{});
+        } else {
+#pragma unroll
+            for (int m = 0; m < 16; ++m) a[m] += acc[m];
+            ++rb;
+        }
+        mc = mn; mn = mm;
+    }
+    if constexpr (WIN) ml_win_fold(w, c, a[0]);
+    else ml_store_rows(d.out, d.out_ld, d.out_f[d.ngemm - 1], c, a);
+}
+
+template <bool WIN>
+__global__ __launch_bounds__(256) void mlp_bwd_kernel_wide(const sda_mlp_desc d, const sda_mlp_win w) {
+    extern __shared__ __attribute__((aligned(16))) float ml_lds[];
+    MlCtx c;
+    ml_ctx(c, d);
+    const int gl = d.ngemm - 1;
+    MlMeta mc = ml_meta(d, gl), mn = ml_meta(d, gl - 1);
+    MlStage st;
+    st.src = ml_rsrc(d.w + mc.w_off); st.toff = 16u * c.tid;
+    st.dst = reinterpret_cast<ml_f32x4*>(ml_lds) + c.tid;
+    st.npieces = mlw_unit_floats(mc.out_f, mc.in_f) / ML_PIECE;
+    for (int p = 0; p < st.npieces; ++p) { ml_f32x4 t[4]; st.issue(t, p); st.commit(t, p); }
+    // gacc = the cotangent of the residual stream, h = a GEMM's input, acc = its output
+    ml_f32x4 h[16], gacc[16], acc[16];
+    if constexpr (WIN) ml_win_cot(w, c, gacc);
+    else ml_load_rows(d.x, d.x_ld, d.out_f[gl], c, gacc);
+    __syncthreads();
+    const bool silu = d.act == SDA_ACT_SILU;
+    int rb = 0, buf = 0;
+    for (int g = 0; g < d.ngemm; ++g) rb += d.kind[g] == 2;
+    for (int g = gl; g >= 0; --g) {
+        const MlMeta mm = ml_meta(d, g - 2);
+        const bool last = g == 0;
+        if (mc.kind == 2) --rb;
+        const int cw = mc.in_f, nm = mlw_mf(cw);
+        const int64_t srow = c.rowok ? c.row : 0;
+        if (mc.kind != 1) {
+#pragma unroll
+            for (int m = 0; m < 16; ++m) h[m] = gacc[m];
+        }
+        mlw_gemm(ml_lds, buf, d.w + mc.w_off, mc.out_f, mc.in_f, d.w + (last ? 0 : mn.w_off),
+                 last ? 0 : mlw_unit_floats(mn.out_f, mn.in_f) / ML_PIECE, h, acc, st, c);
+        // What the epilogue reads from the forward is fetched BEHIND the multiply (in front of it, as the narrow kernel does, its 64 registers
+        // would be live under 1024 MFMAs next to gacc, h, acc and the A fragments).  The vector ALU reads the 256 architectural registers
+        // only: with gacc, acc and h in them the pre-activations come in groups of four fragments, one group ahead of its use.
+        const int64_t soff = (int64_t)rb * d.save_stride + srow * d.save_ld + 4 * c.kq;
+        if (mc.kind == 0) {
+#pragma unroll
+            for (int m = 0; m < 16; ++m) gacc[m] = acc[m];
+        } else if (mc.kind == 2) {
+            const float* sp = d.z_save + soff;
+            // q = W2^T g, x act'(z)   (features beyond the width: acc = 0 there, so q = 0 x act'(0) = 0)
+            auto dact = [&](auto SILU_) {
+                ml_f32x4 zb[2][4];
+                auto fetch = [&](int grp) {
+#pragma unroll
+                    for (int i = 0; i < 4; ++i)
+                        zb[grp & 1][i] = 4 * grp + i < nm ? *reinterpret_cast<const ml_f32x4*>(sp + 16 * (4 * grp + i)) : ml_f32x4{0.f, 0.f, 0.f, 0.f};
+                };
+                fetch(0);
+#pragma unroll
+                for (int grp = 0; grp < 4; ++grp) {
+                    if (grp < 3) fetch(grp + 1);
+#pragma unroll
+                    for (int i = 0; i < 4; ++i)
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) {
+                            const float z = zb[grp & 1][i][r];
+                            h[4 * grp + i][r] = acc[4 * grp + i][r] * (decltype(SILU_)::value ? sda_dact(SDA_ACT_SILU, z) : sda_dact(d.act, z));
+                        }
+                    __builtin_amdgcn_sched_barrier(0);
+                }
+            };
+            if (silu) dact(std::true_type{});
+            else dact(std::false_type{});
+        } else {
+            // gh = W1^T q; g += LN^T(gh)
+            const float* sp = d.a_save + soff;
+            ml_f32x4 sv[16];                               // the block input
+#pragma unroll
+            for (int m = 0; m < 16; ++m) sv[m] = m < nm ? *reinterpret_cast<const ml_f32x4*>(sp + 16 * m) : ml_f32x4{0.f, 0.f, 0.f, 0.f};
+            const float mean = d.mean_save[(int64_t)rb * d.stat_stride + srow], rs = d.rstd_save[(int64_t)rb * d.stat_stride + srow];
+            const float inv_c = 1.f / (float)cw, inv_v = 1.f / (float)(d.unbiased ? cw - 1 : cw);
+            if (cw == 256) ml_ln_bwd<true>(sv, acc, gacc, cw, c, inv_c, inv_v, mean, rs);
+            else ml_ln_bwd<false>(sv, acc, gacc, cw, c, inv_c, inv_v, mean, rs);
+        }
+        mc = mn; mn = mm;
+    }
+    if constexpr (WIN) {
+        if (c.rowok) *reinterpret_cast<ml_f32x4*>(w.gwin + c.row * 16 + 4 * c.kq) = gacc[0];
+    } else {
+        ml_store_rows(d.out, d.out_ld, d.in_f[0], c, gacc);
+    }
+}
+
+// `wide`: a width above 128 -- the net runs the _wide kernels
+static int mlp_check(const sda_mlp_desc* d, bool bwd, bool win, bool* wide) {
     if (!d || d->rows < 1 || d->ngemm < 1 || d->ngemm > SDA_MLP_MAXG) return SDA_E_UNSUPPORTED;
     if ((!win && (!d->x || !d->out)) || !d->w || (!bwd && !d->bias)) return SDA_E_BADARG;
-    int nres = 0;
+    int nres = 0, wmax = 0, wres = 0;
     for (int g = 0; g < d->ngemm; ++g) {
-        if (d->in_f[g] < 1 || d->out_f[g] < 1 || d->in_f[g] > 128 || d->out_f[g] > 128 || d->kind[g] < 0 || d->kind[g] > 2) return SDA_E_UNSUPPORTED;
+        if (d->in_f[g] < 1 || d->out_f[g] < 1 || d->in_f[g] > 256 || d->out_f[g] > 256 || d->kind[g] < 0 || d->kind[g] > 2) return SDA_E_UNSUPPORTED;
         if (g > 0 && d->in_f[g] != d->out_f[g - 1]) return SDA_E_BADARG;
         if (d->kind[g] == 1) {
             if (g + 1 >= d->ngemm || d->kind[g + 1] != 2 || d->in_f[g] != d->out_f[g] || d->out_f[g + 1] != d->in_f[g]) return SDA_E_BADARG;
             if (d->unbiased && d->in_f[g] < 2) return SDA_E_UNSUPPORTED;
             ++nres;
+            if (d->in_f[g] > wres) wres = d->in_f[g];
         }
+        if (d->in_f[g] > wmax) wmax = d->in_f[g];
+        if (d->out_f[g] > wmax) wmax = d->out_f[g];
         if (d->kind[g] == 2 && (g == 0 || d->kind[g - 1] != 1)) return SDA_E_BADARG;
         if ((d->w_off[g] & 3) || (d->b_off[g] & 3)) return SDA_E_BADARG;
     }
     if ((reinterpret_cast<uintptr_t>(d->w) & 15) || (!bwd && (reinterpret_cast<uintptr_t>(d->bias) & 15))) return SDA_E_BADARG;
-    if (!bwd && d->b_off[d->ngemm - 1] + 16 * ml_mf(d->out_f[d->ngemm - 1]) > ML_BIAS) return SDA_E_UNSUPPORTED;
+    *wide = wmax > 128;
+    // (every GEMM's padded bias sits in LDS for the whole launch: 4096 floats -- sixteen 256-wide GEMMs)
+    if (!bwd && d->b_off[d->ngemm - 1] + 16 * mlw_mf(d->out_f[d->ngemm - 1]) > ML_BIAS) return SDA_E_UNSUPPORTED;
     const bool saves = d->a_save && d->z_save && d->mean_save && d->rstd_save;
     if (nres > 0) {
         if (bwd && !saves) return SDA_E_BADARG;
         if (!bwd && (d->a_save || d->z_save || d->mean_save || d->rstd_save) && !saves) return SDA_E_BADARG;
-        if (saves && (d->save_ld < 128 || (d->save_ld & 3) || (reinterpret_cast<uintptr_t>(d->a_save) & 15) ||
+        if (saves && (d->save_ld < (wres > 128 ? 256 : 128) || (d->save_ld & 3) || (reinterpret_cast<uintptr_t>(d->a_save) & 15) ||
                       (reinterpret_cast<uintptr_t>(d->z_save) & 15) || (d->save_stride & 3)))
             return SDA_E_BADARG;
     }
@@ -586,15 +975,17 @@ static int mlp_win_check(const sda_mlp_desc* d, const sda_mlp_win* w, bool bwd) 
 
 template <bool BWD, bool WIN>
 static int mlp_launch(const sda_mlp_desc* d, const sda_mlp_win* w, hipStream_t stream) {
-    int rc = mlp_check(d, BWD, WIN);
+    bool wide = false;
+    int rc = mlp_check(d, BWD, WIN, &wide);
     if (rc != SDA_OK) return rc;
     if (WIN && (rc = mlp_win_check(d, w, BWD)) != SDA_OK) return rc;
     const int64_t tiles = ((int64_t)d->rows + 63) / 64;
     if (tiles > 0x7fffffffLL) return SDA_E_UNSUPPORTED;
     constexpr int lds = (2 * ML_SLAB + ML_BIAS) * 4;
-    static bool raised[SDA_MAX_DEVICES];
-    const void* kern = BWD ? reinterpret_cast<const void*>(mlp_bwd_kernel<WIN>) : reinterpret_cast<const void*>(mlp_fwd_kernel<WIN>);
-    const int rr = sda_raise_dyn_lds(kern, lds, raised);
+    static bool raised[2][SDA_MAX_DEVICES];
+    const void* kern = wide ? (BWD ? reinterpret_cast<const void*>(mlp_bwd_kernel_wide<WIN>) : reinterpret_cast<const void*>(mlp_fwd_kernel_wide<WIN>))
+                            : (BWD ? reinterpret_cast<const void*>(mlp_bwd_kernel<WIN>) : reinterpret_cast<const void*>(mlp_fwd_kernel<WIN>));
+    const int rr = sda_raise_dyn_lds(kern, lds, raised[wide]);
     if (rr != SDA_OK) return rr;
     sda_mlp_win wv = {};
     if (WIN) wv = *w;
@@ -608,7 +999,10 @@ static int mlp_launch(const sda_mlp_desc* d, const sda_mlp_win* w, hipStream_t s
     }
     d = &dd;
 #endif
-    if (BWD) hipLaunchKernelGGL(mlp_bwd_kernel<WIN>, dim3((unsigned)tiles), dim3(256), lds, stream, *d, wv);
+    if (wide) {
+        if (BWD) hipLaunchKernelGGL(mlp_bwd_kernel_wide<WIN>, dim3((unsigned)tiles), dim3(256), lds, stream, *d, wv);
+        else hipLaunchKernelGGL(mlp_fwd_kernel_wide<WIN>, dim3((unsigned)tiles), dim3(256), lds, stream, *d, wv);
+    } else if (BWD) hipLaunchKernelGGL(mlp_bwd_kernel<WIN>, dim3((unsigned)tiles), dim3(256), lds, stream, *d, wv);
     else hipLaunchKernelGGL(mlp_fwd_kernel<WIN>, dim3((unsigned)tiles), dim3(256), lds, stream, *d, wv);
     return sda_launch_status();
 }
@@ -619,6 +1013,6 @@ extern "C" int sda_mlp_fwd_win(const sda_mlp_desc* d, const sda_mlp_win* w, void
 extern "C" int sda_mlp_bwd_win(const sda_mlp_desc* d, const sda_mlp_win* w, void* stream) { return mlp_launch<true, true>(d, w, (hipStream_t)stream); }
 // floats of GEMM (in_f -> out_f)'s slab, for the packer
 extern "C" int sda_mlp_slab_floats(int in_f, int out_f) {
-    if (in_f < 1 || out_f < 1 || in_f > 128 || out_f > 128) return SDA_E_UNSUPPORTED;
-    return ml_slab_floats(in_f, out_f);
+    if (in_f < 1 || out_f < 1 || in_f > 256 || out_f > 256) return SDA_E_UNSUPPORTED;
+    return mlw_slab_floats(in_f, out_f);
 }

@@ -174,7 +174,7 @@ class FusedLocal:
         self.out = torch.empty_like(self.eps)
         self.gwin = torch.empty(self.rows, 16, device=dev, dtype=torch.float32)
         nres = max(mplan.nres, 1)
-        self.a_s = torch.empty(nres, self.rows, mlp._MLP_W, device=dev, dtype=torch.float32)
+        self.a_s = torch.empty(nres, self.rows, mplan.save_ld, device=dev, dtype=torch.float32)
         self.z_s = torch.empty_like(self.a_s)
         self.m_s = torch.empty(nres, self.rows, device=dev, dtype=torch.float32)
         self.r_s = torch.empty_like(self.m_s)
@@ -204,7 +204,7 @@ class FusedLocal:
     def _desc(self, backward: bool):
         from . import mlp
         d = self.mplan.desc(self.rows, backward)
-        d.a_save, d.z_save, d.save_stride, d.save_ld = self.a_s.data_ptr(), self.z_s.data_ptr(), self.rows * mlp._MLP_W, mlp._MLP_W
+        d.a_save, d.z_save, d.save_stride, d.save_ld = self.a_s.data_ptr(), self.z_s.data_ptr(), self.rows * self.mplan.save_ld, self.mplan.save_ld
         d.mean_save, d.rstd_save, d.stat_stride = self.m_s.data_ptr(), self.r_s.data_ptr(), self.rows
         return d
 

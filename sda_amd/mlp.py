@@ -31,31 +31,39 @@ def _is_res_block(block) -> bool:
 
 # ---------------------------------------------------------------------------------------------- whole-MLP kernels (csrc/mlp1d.hip)
 FUSED = os.environ.get('SDA_MLP_FUSED', '1') != '0'
-_MLP_W = 128
+_MLP_W = 256          # the widest GEMM side the kernels take (above 128: the _wide kernels, GEMMs streamed as 128 x 128 units)
 
 
 def _mf(out_f: int) -> int:
-    """D fragments (16 features each) of an output width: padded to 16 or 128 features."""
-    return 1 if out_f <= 16 else 8
+    """D fragments (16 features each) of an output width: padded to 16 / 128 / 256 features."""
+    return 1 if out_f <= 16 else (8 if out_f <= 128 else 16)
 
 
 def _kq(in_f: int) -> int:
-    """K quads (16 values each) of a contraction length: padded to 16 / 64 / 128."""
-    return 1 if in_f <= 16 else (4 if in_f <= 64 else 8)
+    """K quads (16 values each) of a contraction length: padded to 16 / 64 / 128 / 256."""
+    return 1 if in_f <= 16 else (4 if in_f <= 64 else (8 if in_f <= 128 else 16))
 
 
+_BIAS = 4096           # floats of the kernel's bias region in LDS
 _PIECE = 4096          # floats per staging piece of the kernel (slabs are zero padded to whole pieces in memory)
 
 
+def _unit(Wp: Tensor) -> Tensor:
+    """One LDS slab, Wp [16 mf][16 kq]: [fragment m][k quad sq][lane = 16 kq + li][4] with element e of lane (kq, li) =
+    Wp[16 m + li][16 sq + 4 kq + e]; padded with zeros to whole staging pieces."""
+    mf, kq = Wp.shape[0] // 16, Wp.shape[1] // 16
+    mat = Wp.view(mf, 16, kq, 4, 4).permute(0, 2, 3, 1, 4).contiguous().reshape(-1)
+    return torch.nn.functional.pad(mat, (0, -mat.numel() % _PIECE))
+
+
 def _slab(W: Tensor) -> Tensor:
-    """The LDS slab of one GEMM y = W x, W [out][in] (csrc/mlp1d.hip): [fragment m][k quad sq][lane = 16 kq + li][4] with element e of lane
-    (kq, li) = Wp[16 m + li][16 sq + 4 kq + e], Wp zero padded; padded with zeros to whole staging pieces."""
+    """The slab of one GEMM y = W x, W [out][in] (csrc/mlp1d.hip), Wp = W zero padded to [16 mf][16 kq]: one unit (see :func:`_unit`) when
+    both sides are <= 128; otherwise the units of Wp's 128 x 128 quarters (halves, when one side is <= 128) in the order [row half][column half]."""
     o, i = W.shape
     mf, kq = _mf(o), _kq(i)
     Wp = torch.zeros(16 * mf, 16 * kq, device=W.device, dtype=torch.float32)
     Wp[:o, :i] = W
-    mat = Wp.view(mf, 16, kq, 4, 4).permute(0, 2, 3, 1, 4).contiguous().reshape(-1)
-    return torch.nn.functional.pad(mat, (0, -mat.numel() % _PIECE))
+    return torch.cat([_unit(Wp[r:r + 128, c:c + 128].contiguous()) for r in range(0, 16 * mf, 128) for c in range(0, 16 * kq, 128)])
 
 
 class _FusedPlan:
@@ -77,6 +85,7 @@ class _FusedPlan:
                 self.gemms.append((2, l2.in_features, l2.out_features, l2))
         self.ok = (1 <= len(self.gemms) <= _lib.MLP_MAXG and len(acts) <= 1 and len(epss) <= 1 and
                    all(i <= _MLP_W and o <= _MLP_W and lin.bias is not None for _, i, o, lin in self.gemms) and
+                   sum(16 * _mf(o) for _, _i, o, _ in self.gemms) <= _BIAS and     # (every GEMM's padded bias stays in LDS for the launch)
                    all(i == o for k, i, o, _ in self.gemms if k) and
                    all(i >= 2 for k, i, _o, _ in self.gemms if k == 1 and LN_UNBIASED) and   # (unbiased LayerNorm of one feature: C ABI says UNSUPPORTED)
                    all(self.gemms[j][1] == self.gemms[j - 1][2] for j in range(1, len(self.gemms))))
@@ -84,6 +93,8 @@ class _FusedPlan:
         self.eps = epss.pop() if epss else 1e-5
         self.unbiased = LN_UNBIASED
         self.nres = sum(1 for k, *_ in self.gemms if k == 2)
+        # row length of the saved streams (block inputs, pre-activations): the widest residual block, padded as the kernel pads it
+        self.save_ld = max([16 * _mf(i) for k, i, _o, _ in self.gemms if k == 1] + [128])
         self._key = None
 
     def _pack(self):
@@ -142,11 +153,11 @@ class _FusedMLPFunction(torch.autograd.Function):
         d.x, d.x_ld, d.out, d.out_ld = x.data_ptr(), x.stride(0), out.data_ptr(), out.stride(0)
         saves = None
         if need and plan.nres:
-            a_s = torch.empty(plan.nres, rows, _MLP_W, device=x.device, dtype=torch.float32)
+            a_s = torch.empty(plan.nres, rows, plan.save_ld, device=x.device, dtype=torch.float32)
             z_s = torch.empty_like(a_s)
             m_s = torch.empty(plan.nres, rows, device=x.device, dtype=torch.float32)
             r_s = torch.empty_like(m_s)
-            d.a_save, d.z_save, d.save_stride, d.save_ld = a_s.data_ptr(), z_s.data_ptr(), rows * _MLP_W, _MLP_W
+            d.a_save, d.z_save, d.save_stride, d.save_ld = a_s.data_ptr(), z_s.data_ptr(), rows * plan.save_ld, plan.save_ld
             d.mean_save, d.rstd_save, d.stat_stride = m_s.data_ptr(), r_s.data_ptr(), rows
             saves = (a_s, z_s, m_s, r_s)
         ops.mlp_launch(d, False)
@@ -162,7 +173,7 @@ class _FusedMLPFunction(torch.autograd.Function):
         d.x, d.x_ld, d.out, d.out_ld = g.data_ptr(), g.stride(0), gx.data_ptr(), gx.stride(0)
         if ctx.saves is not None:
             a_s, z_s, m_s, r_s = ctx.saves
-            d.a_save, d.z_save, d.save_stride, d.save_ld = a_s.data_ptr(), z_s.data_ptr(), rows * _MLP_W, _MLP_W
+            d.a_save, d.z_save, d.save_stride, d.save_ld = a_s.data_ptr(), z_s.data_ptr(), rows * plan.save_ld, plan.save_ld
             d.mean_save, d.rstd_save, d.stat_stride = m_s.data_ptr(), r_s.data_ptr(), rows
         ops.mlp_launch(d, True)
         return gx, None
