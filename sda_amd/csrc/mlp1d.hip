@@ -18,8 +18,9 @@
 //   * saved for the VJP (16-byte stores): block inputs, pre-activations, mean / rstd -- as the per-layer path saved.
 // Widths are padded: outputs to 16 / 128 / 256 features, contraction lengths to 16 / 64 / 128 / 256.
 // Wide nets (a GEMM side in 129 .. 256: the reference's TRAINED local nets are 256 wide, experiments/lorenz/train.py:30-44) run the
-// mlp_fwd_kernel_wide / mlp_bwd_kernel_wide kernels at the end of this file; nets whose GEMMs are all <= 128 run the kernels above them,
-// untouched.  The plan:
+// mlp_fwd_kernel_wide / mlp_bwd_kernel_wide kernels at the end of this file; nets whose GEMMs are all <= 128 run the kernels above them.
+// Both sets call ONE copy of the multiply (ml_mm), the LayerNorm and its adjoint (ml_ln, ml_ln_bwd) and window mode's fold epilogue
+// (ml_win_fold); window mode's two loaders exist twice (see ml_win_load).  The plan:
 //   * still row private, 16 rows x ALL 256 features per wave: sixteen D fragments = 64 registers per activation array, and a GEMM's D
 //     fragments are still the next GEMM's B operands as they stand.  LayerNorm: 4 lanes x 64 registers, the same two passes + two shuffles;
 //   * a wide GEMM is streamed through LDS as UNITS: a side above 128 pads to 256 and splits in two halves of 128, so a 256 x 256 layer is
@@ -169,18 +170,23 @@ __device__ __forceinline__ void ml_mm(const float* wl, const ml_f32x4 (&h)[8], m
     for (int m = MF; m < 8; ++m) acc[m] = ml_f32x4{0.f, 0.f, 0.f, 0.f};
 }
 
-__device__ __forceinline__ void ml_gemm(const float* wl, int in_f, int out_f, const ml_f32x4 (&h)[8], ml_f32x4 (&acc)[8],
-                                        const ml_f32x4 (&cinit)[8], MlStage& st, const MlCtx& c, float* sp, const ml_f32x4 (&sreg)[8]) {
-    const int mf = ml_mf(out_f), kq = ml_kq(in_f);
+// the one run-time (mf, kq) -> ml_mm<MF, KQ> choice (fragment / K-quad counts as ml_mf / ml_kq pad them).  The save stream `sp` is honoured
+// by <8, 8> alone, the only shape that takes one: callers pass it only for 128 -> 128
+__device__ __forceinline__ void ml_mm_pick(int mf, int kq, const float* wl, const ml_f32x4 (&h)[8], ml_f32x4 (&acc)[8], const ml_f32x4 (&cinit)[8],
+                                           MlStage& st, const MlCtx& c, float* sp, const ml_f32x4 (&sreg)[8]) {
     if (mf == 8) {
-        if (kq == 8) ml_mm<8, 8>(wl, h, acc, cinit, st, c, sp, sreg);      // (the only shape that takes a save stream: callers pass
-        else if (kq == 4) ml_mm<8, 4>(wl, h, acc, cinit, st, c, nullptr, sreg);   //  sp only for 128 -> 128)
+        if (kq == 8) ml_mm<8, 8>(wl, h, acc, cinit, st, c, sp, sreg);
+        else if (kq == 4) ml_mm<8, 4>(wl, h, acc, cinit, st, c, nullptr, sreg);
         else ml_mm<8, 1>(wl, h, acc, cinit, st, c, nullptr, sreg);
     } else {
         if (kq == 8) ml_mm<1, 8>(wl, h, acc, cinit, st, c, nullptr, sreg);
         else if (kq == 4) ml_mm<1, 4>(wl, h, acc, cinit, st, c, nullptr, sreg);
         else ml_mm<1, 1>(wl, h, acc, cinit, st, c, nullptr, sreg);
     }
+}
+__device__ __forceinline__ void ml_gemm(const float* wl, int in_f, int out_f, const ml_f32x4 (&h)[8], ml_f32x4 (&acc)[8],
+                                        const ml_f32x4 (&cinit)[8], MlStage& st, const MlCtx& c, float* sp, const ml_f32x4 (&sreg)[8]) {
+    ml_mm_pick(ml_mf(out_f), ml_kq(in_f), wl, h, acc, cinit, st, c, sp, sreg);
 }
 
 // a GEMM's descriptor entries.  They are read from the kernel-argument segment by a run-time index -- scalar loads, ~300 cycles each time
@@ -205,10 +211,10 @@ __device__ __forceinline__ float ml_rowsum(float s) {
     return s;
 }
 
-// LayerNorm over a row's features (4 lanes x 4 NF registers): h = (a - mean) rstd, two passes.  FULL: the width fills its fragments (256 of
-// 256): no per-value masks.  TWIN of the `ln` lambda of mlp_fwd_kernel (and ml_ln_bwd of the `lnb` lambda of mlp_bwd_kernel): the narrow
-// kernels keep their inline text so that their machine code stays what it was (tests/test_isa_guard_mlp.py pins it) -- a change to one
-// of a pair belongs in the other.
+// LayerNorm over a row's features (4 lanes x 4 NF registers): h = (a - mean) rstd, two passes.  FULL: the width fills its fragments (128 of
+// 128, 256 of 256): no per-value masks -- vector-ALU instructions are what these kernels' time outside the MFMAs is made of (2.4 per MFMA in
+// the first version, rocprofv3 SQ_INSTS_VALU).  The kernels pick FULL through a generic lambda (`ln`, `lnb`, as `epi` / `dact` pick the
+// activation): called bare from the narrow kernels' loops, the same helper compiled to 184-264 more instructions per forward kernel.
 template <bool FULL, int NF>
 __device__ __forceinline__ void ml_ln(const ml_f32x4 (&a)[NF], ml_f32x4 (&h)[NF], int cw, const MlCtx& c, float inv_c, float inv_v, float eps,
                                       float& mean, float& rstd) {
@@ -307,9 +313,9 @@ __device__ __forceinline__ MlWinRow ml_win_row(const sda_mlp_win& w, const MlCtx
 // does `fold` read slot j of this window?  (the centre always; the leading slots of a trajectory's first window, the trailing ones of its last)
 __device__ __forceinline__ bool ml_win_sel(const MlWinRow& r, int j, int k) { return j == k || (r.first && j < k) || (r.lastw && j > k); }
 
-// Window mode's loader, epilogue and VJP loader for the wide kernels.  TWINS of the inline text of mlp_fwd_kernel<true> / mlp_bwd_kernel<true>
-// (kept inline there for the same reason as the LayerNorm pair above): a change to one of a pair belongs in the other.
-// the forward loader of window mode: the wave's rows in D layout
+// the forward loader of window mode: the wave's rows in D layout.  (The wide kernels' only: mlp_fwd_kernel<true> keeps an inline copy of it, as
+// mlp_bwd_kernel<true> does of ml_win_cot below -- called from there these two compile to 3 and 43 instructions more than the copies, and no
+// timing of that exists.  An edit of one belongs in its copy.)
 template <int NF>
 __device__ __forceinline__ void ml_win_load(const sda_mlp_win& w, const MlCtx& c, ml_f32x4 (&a)[NF]) {
     // row (b, i): features [0, WC) = x[b][i .. i + 2k][:] -- WC consecutive floats of the trajectory --, then the time embedding
@@ -405,7 +411,7 @@ __global__ __launch_bounds__(256) void mlp_fwd_kernel(const sda_mlp_desc d, cons
 #pragma unroll
     for (int m = 0; m < 8; ++m) zs[m] = ml_f32x4{0.f, 0.f, 0.f, 0.f};
     if constexpr (WIN) {
-        // row (b, i): features [0, WC) = x[b][i .. i + 2k][:] -- WC consecutive floats of the trajectory --, then the time embedding
+        // (inline copy of ml_win_load, see there)  row (b, i): features [0, WC) = x[b][i .. i + 2k][:] -- WC consecutive floats of the trajectory --, then the time embedding
         const MlWinRow wr = ml_win_row(w, c);
         const int wc = (w.len - w.nw + 1) * w.c;
         const float* xr = w.x + ((int64_t)wr.b * w.len + wr.i) * w.c;
@@ -445,31 +451,7 @@ __global__ __launch_bounds__(256) void mlp_fwd_kernel(const sda_mlp_desc d, cons
             // ---- residual block, first half: save a; h = LN(a)
             const float inv_c = 1.f / (float)cw, inv_v = 1.f / (float)(d.unbiased ? cw - 1 : cw);
             float mean, rstd;
-            // FULL: the width fills its fragments (128 of 128): no per-value masks -- vector-ALU instructions are what this kernel's time
-            // outside the MFMAs is made of (2.4 per MFMA in the first version, rocprofv3 SQ_INSTS_VALU)
-            auto ln = [&](auto FULL_) {
-                constexpr bool FULL = decltype(FULL_)::value;
-                float s = 0.f;
-#pragma unroll
-                for (int m = 0; m < 8; ++m)
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) s += (FULL || 16 * m + 4 * c.kq + r < cw) ? a[m][r] : 0.f;
-                mean = ml_rowsum(s) * inv_c;
-                s = 0.f;
-#pragma unroll
-                for (int m = 0; m < 8; ++m)
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        const float dl = a[m][r] - mean;
-                        h[m][r] = dl;
-                        s += (FULL || 16 * m + 4 * c.kq + r < cw) ? dl * dl : 0.f;
-                    }
-                rstd = __builtin_amdgcn_rsqf(ml_rowsum(s) * inv_v + d.eps);
-#pragma unroll
-                for (int m = 0; m < 8; ++m)
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) h[m][r] = (FULL || 16 * m + 4 * c.kq + r < cw) ? h[m][r] * rstd : 0.f;
-            };
+            auto ln = [&](auto FULL_) { ml_ln<decltype(FULL_)::value>(a, h, cw, c, inv_c, inv_v, d.eps, mean, rstd); };
             if (cw == 128) ln(std::true_type{});
             else ln(std::false_type{});
             if (d.mean_save && c.kq == 0 && c.rowok) {
@@ -528,42 +510,8 @@ __global__ __launch_bounds__(256) void mlp_fwd_kernel(const sda_mlp_desc d, cons
         ML_STAMP(4);                                       // epilogue
         mc = mn; mn = mm;
     }
-    if constexpr (WIN) {
-        // fold (score.py:155-164) + eps = (cx0 + cx1 sigma) x + cn s + the likelihood cotangent, as sda_net1d_fwd_fused's epilogue
-        if (c.rowok) {
-            const MlWinRow wr = ml_win_row(w, c);
-            const int k = (w.len - w.nw) / 2, wc = (2 * k + 1) * w.c;
-            const float mu = w.coef[0], sg = w.coef[1];
-            const bool bare = w.cx0 == 0.f && w.cx1 == 0.f && w.cn == 1.f;
-            const float cx = w.cx0 + w.cx1 * sg;
-            const float rr = __fdiv_rn(sg, mu);
-            const float var = __fadd_rn(__fmul_rn(w.std, w.std), __fmul_rn(w.gamma, __fmul_rn(rr, rr)));
-            const int n_oc = (w.c_stop - w.c_start + w.c_step - 1) / w.c_step;
-            const float* yb = w.y + (int64_t)wr.b * w.y_sn;
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int f = 4 * c.kq + r;
-                if (f >= wc) continue;
-                const int j = f / w.c, ch = f - j * w.c;
-                if (!ml_win_sel(wr, j, k)) continue;
-                const int ps = wr.i + j;
-                const int64_t o = ((int64_t)wr.b * w.len + ps) * w.c + ch;
-                const float xv = w.x[o];
-                const float ov = a[0][r];
-                const float e = bare ? ov : (xv * cx) + (w.cn * ov);
-                w.eps[o] = e;
-                const int crel = ch - w.c_start, prel = ps - w.p_start;
-                float gv = 0.f;
-                if (crel >= 0 && ch < w.c_stop && crel % w.c_step == 0 && prel >= 0 && ps < w.p_stop && prel % w.p_step == 0) {
-                    const float xh = (xv - sg * e) / mu;
-                    gv = __fdiv_rn(yb[(prel / w.p_step) * n_oc + crel / w.c_step] - xh, var);
-                }
-                w.ghat[o] = gv;
-            }
-        }
-    } else {
-        ml_store_rows(d.out, d.out_ld, d.out_f[d.ngemm - 1], c, a);
-    }
+    if constexpr (WIN) ml_win_fold(w, c, a[0]);
+    else ml_store_rows(d.out, d.out_ld, d.out_f[d.ngemm - 1], c, a);
     ML_STAMP(6);                                           // output
     ML_DUMP();
 }
@@ -586,7 +534,7 @@ __global__ __launch_bounds__(256) void mlp_bwd_kernel(const sda_mlp_desc d, cons
 #pragma unroll
     for (int m = 0; m < 8; ++m) zero[m] = ml_f32x4{0.f, 0.f, 0.f, 0.f};
     if constexpr (WIN) {
-        // the cotangent of the window outputs = fold's adjoint of cn ghat: slot j of window (b, i) receives ghat[b][i + j] where fold reads it
+        // (inline copy of ml_win_cot, see ml_win_load)  the cotangent of the window outputs = fold's adjoint of cn ghat: slot j of window (b, i) receives ghat[b][i + j] where fold reads it
         const MlWinRow wr = ml_win_row(w, c);
         const int k = (w.len - w.nw) / 2, wc = (2 * k + 1) * w.c;
 #pragma unroll
@@ -651,28 +599,7 @@ __global__ __launch_bounds__(256) void mlp_bwd_kernel(const sda_mlp_desc d, cons
         } else {
             // gh = W1^T q; g += LN^T(gh) = rstd (gh - mean_c(gh) - x_hat mean'_c(gh x_hat))
             const float inv_c = 1.f / (float)cw, inv_v = 1.f / (float)(d.unbiased ? cw - 1 : cw);
-            auto lnb = [&](auto FULL_) {
-                constexpr bool FULL = decltype(FULL_)::value;
-                float s1 = 0.f, s2 = 0.f;
-#pragma unroll
-                for (int m = 0; m < 8; ++m)
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        const bool fok = FULL || 16 * m + 4 * c.kq + r < cw;
-                        const float xh = fok ? (sv[m][r] - mean) * rs : 0.f;
-                        sv[m][r] = xh;
-                        const float gv = fok ? acc[m][r] : 0.f;
-                        s1 += gv; s2 += gv * xh;
-                    }
-                const float av_ = ml_rowsum(s1) * inv_c, bv_ = ml_rowsum(s2) * inv_v;
-#pragma unroll
-                for (int m = 0; m < 8; ++m)
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        const bool fok = FULL || 16 * m + 4 * c.kq + r < cw;
-                        gacc[m][r] += fok ? rs * (acc[m][r] - av_ - sv[m][r] * bv_) : 0.f;
-                    }
-            };
+            auto lnb = [&](auto FULL_) { ml_ln_bwd<decltype(FULL_)::value>(sv, acc, gacc, cw, c, inv_c, inv_v, mean, rs); };
             if (cw == 128) lnb(std::true_type{});
             else lnb(std::false_type{});
         }
@@ -699,21 +626,13 @@ __host__ __device__ __forceinline__ int mlw_slab_floats(int in_f, int out_f) {
 }
 
 // unit (NH, KH) of a GEMM: acc[8 NH ..] (+)= A h[8 KH ..]; `mfu` / `kqu` = the unit's fragment / K-quad counts (8 wherever the GEMM has a
-// second half on that axis: 12 instantiations of ml_mm in all)
+// second half on that axis -- a compile-time 8 for NH / KH = 1: 12 inlined ml_mm bodies over the four unit positions)
 template <int NH, int KH>
 __device__ __forceinline__ void mlw_unit(const float* wl, int mfu, int kqu, const ml_f32x4 (&h)[16], ml_f32x4 (&acc)[16],
                                          const ml_f32x4 (&cinit)[8], MlStage& st, const MlCtx& c) {
     const ml_f32x4 (&hk)[8] = *reinterpret_cast<const ml_f32x4 (*)[8]>(&h[8 * KH]);
     ml_f32x4 (&an)[8] = *reinterpret_cast<ml_f32x4 (*)[8]>(&acc[8 * NH]);
-    if (NH == 1 || mfu == 8) {
-        if (KH == 1 || kqu == 8) ml_mm<8, 8>(wl, hk, an, cinit, st, c, nullptr, hk);
-        else if (kqu == 4) ml_mm<8, 4>(wl, hk, an, cinit, st, c, nullptr, hk);
-        else ml_mm<8, 1>(wl, hk, an, cinit, st, c, nullptr, hk);
-    } else {
-        if (KH == 1 || kqu == 8) ml_mm<1, 8>(wl, hk, an, cinit, st, c, nullptr, hk);
-        else if (kqu == 4) ml_mm<1, 4>(wl, hk, an, cinit, st, c, nullptr, hk);
-        else ml_mm<1, 1>(wl, hk, an, cinit, st, c, nullptr, hk);
-    }
+    ml_mm_pick(NH == 1 ? 8 : mfu, KH == 1 ? 8 : kqu, wl, hk, an, cinit, st, c, nullptr, hk);
 }
 
 // one GEMM (in_f -> out_f, slab at `ws`): acc = W h.  `nsrc` / `npieces` = the first unit of the NEXT GEMM (staged under this one's last
@@ -983,9 +902,9 @@ static int mlp_launch(const sda_mlp_desc* d, const sda_mlp_win* w, hipStream_t s
     if (tiles > 0x7fffffffLL) return SDA_E_UNSUPPORTED;
     constexpr int lds = (2 * ML_SLAB + ML_BIAS) * 4;
     static bool raised[2][SDA_MAX_DEVICES];
-    const void* kern = wide ? (BWD ? reinterpret_cast<const void*>(mlp_bwd_kernel_wide<WIN>) : reinterpret_cast<const void*>(mlp_fwd_kernel_wide<WIN>))
-                            : (BWD ? reinterpret_cast<const void*>(mlp_bwd_kernel<WIN>) : reinterpret_cast<const void*>(mlp_fwd_kernel<WIN>));
-    const int rr = sda_raise_dyn_lds(kern, lds, raised[wide]);
+    void (*const kern)(sda_mlp_desc, sda_mlp_win) = wide ? (BWD ? mlp_bwd_kernel_wide<WIN> : mlp_fwd_kernel_wide<WIN>)
+                                                         : (BWD ? mlp_bwd_kernel<WIN> : mlp_fwd_kernel<WIN>);
+    const int rr = sda_raise_dyn_lds(reinterpret_cast<const void*>(kern), lds, raised[wide]);
     if (rr != SDA_OK) return rr;
     sda_mlp_win wv = {};
     if (WIN) wv = *w;
@@ -999,11 +918,7 @@ static int mlp_launch(const sda_mlp_desc* d, const sda_mlp_win* w, hipStream_t s
     }
     d = &dd;
 #endif
-    if (wide) {
-        if (BWD) hipLaunchKernelGGL(mlp_bwd_kernel_wide<WIN>, dim3((unsigned)tiles), dim3(256), lds, stream, *d, wv);
-        else hipLaunchKernelGGL(mlp_fwd_kernel_wide<WIN>, dim3((unsigned)tiles), dim3(256), lds, stream, *d, wv);
-    } else if (BWD) hipLaunchKernelGGL(mlp_bwd_kernel<WIN>, dim3((unsigned)tiles), dim3(256), lds, stream, *d, wv);
-    else hipLaunchKernelGGL(mlp_fwd_kernel<WIN>, dim3((unsigned)tiles), dim3(256), lds, stream, *d, wv);
+    hipLaunchKernelGGL(kern, dim3((unsigned)tiles), dim3(256), lds, stream, *d, wv);
     return sda_launch_status();
 }
 

@@ -188,12 +188,12 @@ def test_whole_sequence_tiles_forward_and_vjp_vs_oracle(dev, B, L, C, blocks):
     assert_close(vjp[:3].cpu(), v3.cpu(), 1e-5, what='whole-sequence vs halo tiles (vjp)')
 
 
-def _build_local(dev, features, window, affine, seed=90):
+def _build_local(dev, features, window, affine, seed=90, width=128):
     import bench
     from sda_amd.experiments.lorenz import make_local_score
     from sda_amd.score import VPSDE
     torch.manual_seed(seed)
-    net = make_local_score(window=window, features=features).to(dev)
+    net = make_local_score(window=window, features=features, width=width).to(dev)
     if affine:
         score = bench.SyntheticScore(net)
         inner = VPSDE(score, shape=())
@@ -204,13 +204,14 @@ def _build_local(dev, features, window, affine, seed=90):
 
 
 LOCAL_CASES = [
-    # B, L, C, window, slices, per-sample y, affine
-    (5, 65, 3, 5, (slice(None, None, 8), slice(0, 1)), False, True),       # eval.py "lo" (experiments/lorenz/eval.py:50-53)
-    (1100, 65, 3, 5, (slice(None, None, 1), slice(0, 1)), False, False),   # eval.py "hi" at its batch size, bare network
-    (9, 17, 3, 5, (slice(3, 15, 5), slice(1, 3)), True, False),            # offsets, stops, two observed channels
-    (1, 5, 3, 5, (slice(0, None, 2),), False, True),                        # one window per trajectory, channel slice only
-    (70, 30, 5, 3, (slice(None, None, 4), slice(0, 5, 2)), True, True),     # window 3 of five states
-    (33, 12, 2, 5, (slice(None, None, 3), slice(0, 1)), True, False),       # two states
+    # B, L, C, window, slices, per-sample y, affine, width
+    (5, 65, 3, 5, (slice(None, None, 8), slice(0, 1)), False, True, 128),       # eval.py "lo" (experiments/lorenz/eval.py:50-53)
+    (1100, 65, 3, 5, (slice(None, None, 1), slice(0, 1)), False, False, 128),   # eval.py "hi" at its batch size, bare network
+    (9, 17, 3, 5, (slice(3, 15, 5), slice(1, 3)), True, False, 128),            # offsets, stops, two observed channels
+    (1, 5, 3, 5, (slice(0, None, 2),), False, True, 128),                        # one window per trajectory, channel slice only
+    (70, 30, 5, 3, (slice(None, None, 4), slice(0, 5, 2)), True, True, 128),     # window 3 of five states
+    (33, 12, 2, 5, (slice(None, None, 3), slice(0, 1)), True, False, 128),       # two states
+    (10, 17, 3, 5, (slice(None, None, 4), slice(0, 2)), True, False, 100),  # width 100 (the masked LayerNorm), 130 windows: a partial last tile
 ]
 
 
@@ -220,8 +221,8 @@ def test_fused_local_evaluation_equals_general_path_and_oracle(dev, case, monkey
     sda_mlp_bwd_win, sda_mc_finish) against the general path (unfold + cat + whole-MLP kernels + fold + the guidance kernels) and the oracle."""
     from sda_amd import fused1d, observe as Ob
     from sda_amd.score import GaussianScore
-    B, L, C, window, sl, per_sample, affine = case
-    net, inner = _build_local(dev, C, window, affine)
+    B, L, C, window, sl, per_sample, affine, width = case
+    net, inner = _build_local(dev, C, window, affine, width=width)
     torch.manual_seed(91)
     x = torch.randn(B, L, C)
     t = torch.tensor(0.41)
