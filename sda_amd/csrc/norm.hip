@@ -224,61 +224,6 @@ __global__ __launch_bounds__(LN_THREADS) void ln_stats_wave_kernel(const float* 
     if (lane == 0) { mean[idx] = m; rstd[idx] = 1.0f / sqrtf(var + eps); }
 }
 
-// below this many pixels the wave-per-pixel kernels are used (measured on the Lorenz-96 net, 8192 pixels x 64 channels:
-// statistics 6.4 us wave-per-pixel vs 9.5 us register kernel; backward 15 us wave-per-pixel vs 6.2 us quad kernel)
-#define LN_SMALL_PIXELS 16384
-#define LN_BWD_SMALL_PIXELS 4096
-
-extern "C" int sda_ln_stats(const float* x, int n, int c, int hw, const float* mod, int64_t mod_sn, float eps,
-                            int unbiased, float* mean, float* rstd, void* stream) {
-    if (!x || !mean || !rstd || n <= 0 || c <= 0 || hw <= 0) return SDA_E_BADARG;
-    if (unbiased && c < 2) return SDA_E_UNSUPPORTED;
-    const int64_t npix = (int64_t)n * hw;
-    if (npix < LN_SMALL_PIXELS) {
-        hipLaunchKernelGGL(ln_stats_wave_kernel, dim3((unsigned)((npix + 3) / 4)), dim3(LN_THREADS), 0, (hipStream_t)stream, x,
-                           npix, c, hw, mod, mod_sn, eps, unbiased, mean, rstd);
-        return sda_launch_status();
-    }
-    const int64_t blocks = (npix + LN_THREADS - 1) / LN_THREADS;
-    if (blocks > 0x7fffffffLL) return SDA_E_UNSUPPORTED;
-    static const int quad_mode = getenv("SDA_LN_STATS_QUAD") ? atoi(getenv("SDA_LN_STATS_QUAD")) : 1;
-    if (quad_mode && hw % 4 == 0 && c > 48 && c <= 384 &&
-        ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(mean) | reinterpret_cast<uintptr_t>(rstd)) & 15) == 0) {
-        const int64_t nquad = npix / 4;
-        hipStream_t st = (hipStream_t)stream;
-        dim3 bl(LN_THREADS);
-        // round 6: exact-fit layouts for the 64 / 128 / 256-channel levels of the reference's default widths (the 96 / 192 / 384 layouts
-        // served them with a third of every lane's channel slots empty -- loads of channel 0 that are thrown away).  SDA_LN_FIT=0: A/B
-        static const bool fit = !(getenv("SDA_LN_FIT") && atoi(getenv("SDA_LN_FIT")) == 0);
-        if (fit && c <= 64) hipLaunchKernelGGL((ln_stats_quad_kernel<8, 8>), dim3((unsigned)((nquad + 31) / 32)), bl, 0, st, x, nquad, c, hw, mod, mod_sn, eps, unbiased, mean, rstd);
-        else if (fit && c > 96 && c <= 128 && quad_mode != 3 && quad_mode != 4) hipLaunchKernelGGL((ln_stats_quad_kernel<8, 16>), dim3((unsigned)((nquad + 31) / 32)), bl, 0, st, x, nquad, c, hw, mod, mod_sn, eps, unbiased, mean, rstd);
-        else if (fit && c > 192 && c <= 256 && quad_mode != 3) hipLaunchKernelGGL((ln_stats_quad_kernel<8, 8, 4>), dim3((unsigned)((nquad + 7) / 8)), bl, 0, st, x, nquad, c, hw, mod, mod_sn, eps, unbiased, mean, rstd);
-        else if (c <= 96) hipLaunchKernelGGL((ln_stats_quad_kernel<8, 12>), dim3((unsigned)((nquad + 31) / 32)), bl, 0, st, x, nquad, c, hw, mod, mod_sn, eps, unbiased, mean, rstd);
-        // 192 channels as 8 lanes x 24 channels (128-byte runs, non-temporal): 0.298 -> 0.233 ms at 120 windows, 5.1 -> 6.5 TB/s
-        // (SDA_LN_STATS_QUAD=3: the 16 x 12 layout, for A/B); 384 channels as 8 x 48 (297 registers) lose: 4.65 vs 5.1 TB/s
-        else if (c <= 192 && quad_mode == 4) hipLaunchKernelGGL((ln_stats_quad_kernel<8, 12, 2>), dim3((unsigned)((nquad + 15) / 16)), bl, 0, st, x, nquad, c, hw, mod, mod_sn, eps, unbiased, mean, rstd);
-        // 384 channels: four cooperating wavefronts on the 96-channel layout, partial sums through LDS: 0.148 -> 0.132 ms, 5.1 -> 5.7 TB/s
-        // (for 192 channels two cooperating wavefronts measure 6.3 TB/s against 8 x 24's 6.5; ln_bwd gains nothing from either: 5.2 / 5.75)
-        else if (c > 192 && quad_mode != 3) hipLaunchKernelGGL((ln_stats_quad_kernel<8, 12, 4>), dim3((unsigned)((nquad + 7) / 8)), bl, 0, st, x, nquad, c, hw, mod, mod_sn, eps, unbiased, mean, rstd);
-        else if (c <= 192 && quad_mode != 3) hipLaunchKernelGGL((ln_stats_quad_kernel<8, 24>), dim3((unsigned)((nquad + 31) / 32)), bl, 0, st, x, nquad, c, hw, mod, mod_sn, eps, unbiased, mean, rstd);
-        else if (c <= 192) hipLaunchKernelGGL((ln_stats_quad_kernel<16, 12>), dim3((unsigned)((nquad + 15) / 16)), bl, 0, st, x, nquad, c, hw, mod, mod_sn, eps, unbiased, mean, rstd);
-        else hipLaunchKernelGGL((ln_stats_quad_kernel<16, 24>), dim3((unsigned)((nquad + 15) / 16)), bl, 0, st, x, nquad, c, hw, mod, mod_sn, eps, unbiased, mean, rstd);
-        return sda_launch_status();
-    }
-    if (c > LN_REG_C / 2 && c <= 4 * LN_REG_C && blocks * 4 <= 0x7fffffffLL) {
-        const int split = c <= LN_REG_C ? 1 : (c <= 2 * LN_REG_C ? 2 : 4);
-        dim3 gr((unsigned)((npix * split + LN_THREADS - 1) / LN_THREADS)), bl(LN_THREADS);
-        hipStream_t st = (hipStream_t)stream;
-        if (split == 1) hipLaunchKernelGGL(ln_stats_reg_kernel<1>, gr, bl, 0, st, x, npix, c, hw, mod, mod_sn, eps, unbiased, mean, rstd);
-        else if (split == 2) hipLaunchKernelGGL(ln_stats_reg_kernel<2>, gr, bl, 0, st, x, npix, c, hw, mod, mod_sn, eps, unbiased, mean, rstd);
-        else hipLaunchKernelGGL(ln_stats_reg_kernel<4>, gr, bl, 0, st, x, npix, c, hw, mod, mod_sn, eps, unbiased, mean, rstd);
-        return sda_launch_status();
-    }
-    hipLaunchKernelGGL(ln_stats_kernel, dim3((unsigned)blocks), dim3(LN_THREADS), 0, (hipStream_t)stream, x, npix, c, hw,
-                       mod, mod_sn, eps, unbiased, mean, rstd);
-    return sda_launch_status();
-}
-
 __global__ __launch_bounds__(LN_THREADS) void ln_apply_kernel(const float* __restrict__ x, int64_t npix, int c, int hw,
                                                               const float* __restrict__ mod, int64_t mod_sn,
                                                               const float* __restrict__ mean,
@@ -430,7 +375,7 @@ __global__ __launch_bounds__(LN_THREADS) void ln_bwd_split_kernel(const float* _
 // SPLIT-th channel; a wavefront covers 64 / SPLIT pixel quads, so each channel plane is touched in contiguous runs of
 // (64 / SPLIT) * 16 bytes -- a whole 128-byte line for SPLIT = 8 (the dword version above moves 64-byte runs with four times
 // the instructions).  The SPLIT lanes of a quad sit 64 / SPLIT apart and combine their partial sums with cross-lane adds.
-template <int SPLIT, int CPL, int POOL = 1, int NW = 1>   // POOL == 2: gh at twice the resolution, summed over 2 x 2 cells (w = row length); NW: see ln_stats_quad_kernel
+template <int SPLIT, int CPL, int POOL = 1>   // POOL == 2: gh at twice the resolution, summed over 2 x 2 cells (w = row length)
 __global__ __launch_bounds__(LN_THREADS) void ln_bwd_quad_kernel(const float* __restrict__ gh, const float* __restrict__ x,
                                                                  int64_t nquad, int c, int hw, int w, const float* __restrict__ mod,
                                                                  int64_t mod_sn, const float* __restrict__ mean,
@@ -438,14 +383,10 @@ __global__ __launch_bounds__(LN_THREADS) void ln_bwd_quad_kernel(const float* __
                                                                  const float* __restrict__ res, float* __restrict__ gx,
                                                                  float* __restrict__ amax) {
     constexpr int QW = 64 / SPLIT;                          // quads per wavefront
-    constexpr int WPB = LN_THREADS / 64;
-    static_assert(WPB % NW == 0, "cooperating wavefronts must tile the workgroup");
     const int lane = threadIdx.x & 63;
-    const int wib = threadIdx.x >> 6, cw = wib % NW;
-    const int64_t wave = NW > 1 ? (int64_t)blockIdx.x * (WPB / NW) + wib / NW : ((int64_t)blockIdx.x * LN_THREADS + threadIdx.x) >> 6;
+    const int64_t wave = ((int64_t)blockIdx.x * LN_THREADS + threadIdx.x) >> 6;
     const int64_t quad = wave * QW + (lane & (QW - 1));
-    const int sub = cw * (SPLIT * CPL) + lane / QW;          // first channel of this lane
-    __shared__ float4 part[2][NW > 1 ? WPB : 1][QW];
+    const int sub = lane / QW;                              // first channel of this lane
     const bool live = quad < nquad;
     const int64_t pix = (live ? quad : 0) * 4;
     const int64_t n = pix / hw;
@@ -502,17 +443,6 @@ __global__ __launch_bounds__(LN_THREADS) void ln_bwd_quad_kernel(const float* __
     for (int o = QW; o < 64; o <<= 1) {
         s1.x += __shfl_xor(s1.x, o, 64); s1.y += __shfl_xor(s1.y, o, 64); s1.z += __shfl_xor(s1.z, o, 64); s1.w += __shfl_xor(s1.w, o, 64);
         s2.x += __shfl_xor(s2.x, o, 64); s2.y += __shfl_xor(s2.y, o, 64); s2.z += __shfl_xor(s2.z, o, 64); s2.w += __shfl_xor(s2.w, o, 64);
-    }
-    if constexpr (NW > 1) {
-        if (lane < QW) { part[0][wib][lane] = s1; part[1][wib][lane] = s2; }
-        __syncthreads();
-        s1 = part[0][wib - cw][lane & (QW - 1)]; s2 = part[1][wib - cw][lane & (QW - 1)];
-#pragma unroll
-        for (int i = 1; i < NW; ++i) {
-            const float4 t1 = part[0][wib - cw + i][lane & (QW - 1)], t2 = part[1][wib - cw + i][lane & (QW - 1)];
-            s1.x += t1.x; s1.y += t1.y; s1.z += t1.z; s1.w += t1.w;
-            s2.x += t2.x; s2.y += t2.y; s2.z += t2.z; s2.w += t2.w;
-        }
     }
     if (!live && !amax) return;
     float am = 0.f;
@@ -590,9 +520,169 @@ __global__ __launch_bounds__(LN_THREADS) void ln_bwd_wave_kernel(const float* __
 
 __global__ void ln_amax_zero_kernel(float* __restrict__ amax) { amax[0] = 0.f; }
 
+// ---- launch code: one launcher per kernel family (each derives its grid from its template arguments), one width -> layout table
+
+// below this many pixels the wave-per-pixel kernels are used (measured on the Lorenz-96 net, 8192 pixels x 64 channels:
+// statistics 6.4 us wave-per-pixel vs 9.5 us register kernel; backward 15 us wave-per-pixel vs 6.2 us quad kernel)
+#define LN_SMALL_PIXELS 16384
+#define LN_BWD_SMALL_PIXELS 4096
+#define LN_WPB (LN_THREADS / 64)                     // wavefronts per workgroup
+
+struct ln_stats_args {
+    const float* x; int64_t npix; int c, hw; const float* mod; int64_t mod_sn; float eps; int unbiased; float *mean, *rstd; hipStream_t st;
+};
+struct ln_bwd_args {
+    const float *gh, *x; int64_t npix; int c, h, w; const float* mod; int64_t mod_sn; const float *mean, *rstd; int unbiased;
+    const float* res; float *gx, *amax; bool* amax_served; hipStream_t st;
+};
+
+static inline dim3 ln_grid(int64_t units, int64_t per_block) { return dim3((unsigned)((units + per_block - 1) / per_block)); }
+template <typename... P>
+static inline bool ln_aligned16(const P*... p) { return ((reinterpret_cast<uintptr_t>(p) | ...) & 15) == 0; }
+// SDA_LN_STATS_QUAD=0 / SDA_LN_BWD_QUAD=0 keep the one-pixel-per-lane kernels reachable on aligned shapes; any other value is the default
+static bool ln_env_on(const char* name) { const char* v = getenv(name); return !v || atoi(v) != 0; }
+
+template <int SPLIT, int CPL, int NW = 1>
+static void ln_stats_quad_launch(const ln_stats_args& a) {
+    constexpr int QPB = (64 / SPLIT) * LN_WPB / NW;  // quads per workgroup
+    const int64_t nquad = a.npix / 4;
+    hipLaunchKernelGGL((ln_stats_quad_kernel<SPLIT, CPL, NW>), ln_grid(nquad, QPB), dim3(LN_THREADS), 0, a.st, a.x, nquad, a.c, a.hw, a.mod,
+                       a.mod_sn, a.eps, a.unbiased, a.mean, a.rstd);
+}
+template <int SPLIT>
+static void ln_stats_reg_launch(const ln_stats_args& a) {
+    hipLaunchKernelGGL(ln_stats_reg_kernel<SPLIT>, ln_grid(a.npix * SPLIT, LN_THREADS), dim3(LN_THREADS), 0, a.st, a.x, a.npix, a.c, a.hw,
+                       a.mod, a.mod_sn, a.eps, a.unbiased, a.mean, a.rstd);
+}
+// few pixels: a wavefront per pixel (wave); otherwise the generic thread-per-pixel loop
+static void ln_stats_plain_launch(const ln_stats_args& a, bool wave) {
+    if (wave)
+        hipLaunchKernelGGL(ln_stats_wave_kernel, ln_grid(a.npix, LN_WPB), dim3(LN_THREADS), 0, a.st, a.x, a.npix, a.c, a.hw, a.mod, a.mod_sn,
+                           a.eps, a.unbiased, a.mean, a.rstd);
+    else
+        hipLaunchKernelGGL(ln_stats_kernel, ln_grid(a.npix, LN_THREADS), dim3(LN_THREADS), 0, a.st, a.x, a.npix, a.c, a.hw, a.mod, a.mod_sn,
+                           a.eps, a.unbiased, a.mean, a.rstd);
+}
+
+template <int SPLIT, int CPL, int POOL = 1>
+static void ln_bwd_quad_launch(const ln_bwd_args& a) {
+    constexpr int QPB = (64 / SPLIT) * LN_WPB;       // quads per workgroup
+    const int64_t nquad = a.npix / 4;
+    hipLaunchKernelGGL((ln_bwd_quad_kernel<SPLIT, CPL, POOL>), ln_grid(nquad, QPB), dim3(LN_THREADS), 0, a.st, a.gh, a.x, nquad, a.c, a.h * a.w,
+                       a.w, a.mod, a.mod_sn, a.mean, a.rstd, a.unbiased, a.res, a.gx, a.amax);
+    *a.amax_served = a.amax != nullptr;              // (the only family that reports max |gx| from its own epilogue)
+}
+template <int SPLIT, int CPL, int POOL>
+static void ln_bwd_split_launch(const ln_bwd_args& a) {
+    hipLaunchKernelGGL((ln_bwd_split_kernel<SPLIT, CPL, POOL>), ln_grid(a.npix * SPLIT, LN_THREADS), dim3(LN_THREADS), 0, a.st, a.gh, a.x,
+                       a.npix, a.c, a.h * a.w, a.w, a.mod, a.mod_sn, a.mean, a.rstd, a.unbiased, a.res, a.gx);
+}
+// lanes per pixel x channels per lane, picked per width from measurements on the Kolmogorov net's three levels
+// (c = 96: 4 x 24 1.57 ms vs 2 x 48 2.43, 8 x 12 1.85;  c = 192: 8 x 24 0.86 vs 4 x 48 1.13;  c = 384: 8 x 48 0.59 vs 16 x 24 0.82)
+template <int POOL>
+static void ln_bwd_split_pick(const ln_bwd_args& a) {
+    if (a.c <= 96) ln_bwd_split_launch<4, 24, POOL>(a);
+    else if (a.c <= 192) ln_bwd_split_launch<8, 24, POOL>(a);
+    else ln_bwd_split_launch<8, 48, POOL>(a);
+}
+// as ln_stats_plain_launch
+template <int POOL_H, int POOL_W>
+static void ln_bwd_plain_launch(const ln_bwd_args& a, bool wave) {
+    if (wave)
+        hipLaunchKernelGGL((ln_bwd_wave_kernel<POOL_H, POOL_W>), ln_grid(a.npix, LN_WPB), dim3(LN_THREADS), 0, a.st, a.gh, a.x, a.npix, a.c,
+                           a.h, a.w, a.mod, a.mod_sn, a.mean, a.rstd, a.unbiased, a.res, a.gx);
+    else
+        hipLaunchKernelGGL((ln_bwd_kernel<POOL_H, POOL_W>), ln_grid(a.npix, LN_THREADS), dim3(LN_THREADS), 0, a.st, a.gh, a.x, a.npix, a.c,
+                           a.h, a.w, a.mod, a.mod_sn, a.mean, a.rstd, a.unbiased, a.res, a.gx);
+}
+
+// Which quad kernel serves a width: the first row with c <= cmax (every quad path has 48 < c <= 384, 16-byte aligned pointers and
+// whole quads per row or image).  Template arguments: <lanes per quad, channels per lane[, cooperating wavefronts | POOL]>; 8 lanes
+// move 128-byte runs per channel plane (non-temporal), 16 lanes 64-byte runs.
+//   stats  : sda_ln_stats from LN_SMALL_PIXELS pixels, hw % 4 == 0
+//   bwd    : ln_bwd_launch without pooling from LN_BWD_SMALL_PIXELS pixels, hw % 4 == 0
+//   bwd_up : ln_bwd_launch through a 2 x 2 up-sample (the up-sampling tails: gh at twice the resolution), w % 4 == 0: 2 w floats per
+//            row keep every 16-byte load aligned.  No exact-fit layouts here.
+// stats and bwd agree up to 192 channels and differ above: cooperating wavefronts pay for ln_stats only.
+static const struct ln_quad_row {
+    int cmax;
+    void (*stats)(const ln_stats_args&);
+    void (*bwd)(const ln_bwd_args&);
+    void (*bwd_up)(const ln_bwd_args&);
+} LN_QUAD[] = {
+    // round 6, rows 64 / 128 / 256: exact-fit layouts for the reference's default widths (the 96 / 192 / 384 layouts served them with a
+    // third of every lane's channel slots empty -- loads of channel 0 that are thrown away): at 960 windows ln_bwd 6.1 -> 6.35 /
+    // 5.4 -> 6.2 / 4.66 -> 4.74 TB/s, ln_stats 5.8 -> 6.1 / 5.2 -> 5.75 / 5.5 -> 5.8 TB/s
+    {64, ln_stats_quad_launch<8, 8>, ln_bwd_quad_launch<8, 8>, ln_bwd_quad_launch<8, 12, 2>},
+    {96, ln_stats_quad_launch<8, 12>, ln_bwd_quad_launch<8, 12>, ln_bwd_quad_launch<8, 12, 2>},
+    {128, ln_stats_quad_launch<8, 16>, ln_bwd_quad_launch<8, 16>, ln_bwd_quad_launch<16, 12, 2>},
+    // 192 channels as 8 lanes x 24 channels against 16 x 12, at 120 windows.  ln_stats: 0.298 -> 0.233 ms, 5.1 -> 6.5 TB/s (two
+    // cooperating wavefronts of 8 x 12 measure 6.3).  ln_bwd: one wavefront per SIMD -- 376 registers -- but with the residual loads
+    // ahead of the reduction it beats 16 x 12's 64-byte runs: 1.21 -> 1.07 ms, 5.0 -> 5.65 TB/s (before that change it lost, 4.48 vs
+    // 4.87; two cooperating wavefronts: 5.75, level)
+    {192, ln_stats_quad_launch<8, 24>, ln_bwd_quad_launch<8, 24>, ln_bwd_quad_launch<16, 12, 2>},
+    // ln_stats above 192 channels: four cooperating wavefronts on the 64 / 96-channel layout, partial sums through LDS: at 384
+    // channels 0.148 -> 0.132 ms, 5.1 -> 5.7 TB/s against 16 x 24 (8 x 48, 297 registers, loses: 4.65 vs 5.1).  ln_bwd gains nothing
+    // from them (5.2 at 384 channels, level) and stays on 16 lanes; 384 channels as 32 x 12: 3.8 vs 5.0 TB/s
+    {256, ln_stats_quad_launch<8, 8, 4>, ln_bwd_quad_launch<16, 16>, ln_bwd_quad_launch<16, 24, 2>},
+    {384, ln_stats_quad_launch<8, 12, 4>, ln_bwd_quad_launch<16, 24>, ln_bwd_quad_launch<16, 24, 2>},
+};
+#define LN_QUAD_CMIN 48
+#define LN_QUAD_CMAX 384
+static const ln_quad_row& ln_quad_pick(int c) {         // LN_QUAD_CMIN < c <= LN_QUAD_CMAX
+    const ln_quad_row* r = LN_QUAD;
+    while (c > r->cmax) ++r;
+    return *r;
+}
+
+extern "C" int sda_ln_stats(const float* x, int n, int c, int hw, const float* mod, int64_t mod_sn, float eps,
+                            int unbiased, float* mean, float* rstd, void* stream) {
+    if (!x || !mean || !rstd || n <= 0 || c <= 0 || hw <= 0) return SDA_E_BADARG;
+    if (unbiased && c < 2) return SDA_E_UNSUPPORTED;
+    const int64_t npix = (int64_t)n * hw;
+    const ln_stats_args a = {x, npix, c, hw, mod, mod_sn, eps, unbiased, mean, rstd, (hipStream_t)stream};
+    if (npix < LN_SMALL_PIXELS) {
+        ln_stats_plain_launch(a, true);
+        return sda_launch_status();
+    }
+    const int64_t blocks = (npix + LN_THREADS - 1) / LN_THREADS;
+    if (blocks > 0x7fffffffLL) return SDA_E_UNSUPPORTED;
+    static const bool quad_on = ln_env_on("SDA_LN_STATS_QUAD");
+    if (quad_on && hw % 4 == 0 && c > LN_QUAD_CMIN && c <= LN_QUAD_CMAX && ln_aligned16(x, mean, rstd)) ln_quad_pick(c).stats(a);
+    else if (c > LN_REG_C / 2 && c <= 4 * LN_REG_C && blocks * 4 <= 0x7fffffffLL) {
+        if (c <= LN_REG_C) ln_stats_reg_launch<1>(a);
+        else if (c <= 2 * LN_REG_C) ln_stats_reg_launch<2>(a);
+        else ln_stats_reg_launch<4>(a);
+    } else ln_stats_plain_launch(a, false);
+    return sda_launch_status();
+}
+
 static int ln_bwd_launch(const float* gh, const float* x, int n, int c, int h, int w, const float* mod, int64_t mod_sn,
                          const float* mean, const float* rstd, int unbiased, int pool_h, int pool_w, const float* res,
-                         float* gx, float* amax, bool* amax_served, void* stream);
+                         float* gx, float* amax, bool* amax_served, void* stream) {
+    if (!gh || !x || !mean || !rstd || !gx || n <= 0 || c <= 0 || h <= 0 || w <= 0) return SDA_E_BADARG;
+    // (zeroed by a kernel, not a 4-byte memset: see sda_absmax)
+    if (amax) hipLaunchKernelGGL(ln_amax_zero_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, amax);
+    const int shape = pool_h * 10 + pool_w;          // 11: no pooling, 12: 1-D nets (length axis only), 22: 2-D nets
+    if (shape != 11 && shape != 12 && shape != 22) return SDA_E_UNSUPPORTED;
+    const int64_t npix = (int64_t)n * h * w;
+    const int64_t blocks = (npix + LN_THREADS - 1) / LN_THREADS;
+    if (blocks > 0x7fffffffLL) return SDA_E_UNSUPPORTED;
+    const ln_bwd_args a = {gh, x, npix, c, h, w, mod, mod_sn, mean, rstd, unbiased, res, gx, amax, amax_served, (hipStream_t)stream};
+    static const bool quad_on = ln_env_on("SDA_LN_BWD_QUAD");
+    const bool small = npix < LN_BWD_SMALL_PIXELS;
+    const bool wide = shape != 12 && c > LN_QUAD_CMIN && c <= LN_QUAD_CMAX;       // the widths and pool shapes of the quad and split kernels
+    if (!small && wide && quad_on && (shape == 11 ? (h * w) % 4 == 0 : w % 4 == 0) && ln_aligned16(gh, x, gx, mean, rstd, res)) {
+        const ln_quad_row& r = ln_quad_pick(c);
+        (shape == 11 ? r.bwd : r.bwd_up)(a);
+    } else if (!small && wide && blocks * 8 <= 0x7fffffffLL) {
+        if (shape == 11) ln_bwd_split_pick<1>(a);
+        else ln_bwd_split_pick<2>(a);
+    } else if (shape == 11) ln_bwd_plain_launch<1, 1>(a, small);
+    else if (shape == 12) ln_bwd_plain_launch<1, 2>(a, small);
+    else ln_bwd_plain_launch<2, 2>(a, small);
+    return sda_launch_status();
+}
 
 extern "C" int sda_ln_bwd(const float* gh, const float* x, int n, int c, int h, int w, const float* mod, int64_t mod_sn,
                           const float* mean, const float* rstd, int unbiased, int pool_h, int pool_w, const float* res,
@@ -612,116 +702,4 @@ extern "C" int sda_ln_bwd_amax(const float* gh, const float* x, int n, int c, in
     if (rc != SDA_OK || served) return rc;
     if (reinterpret_cast<uintptr_t>(gx) & 15) return SDA_E_UNSUPPORTED;
     return sda_absmax(gx, (int64_t)n * c * h * w, amax, stream);
-}
-
-static int ln_bwd_launch(const float* gh, const float* x, int n, int c, int h, int w, const float* mod, int64_t mod_sn,
-                         const float* mean, const float* rstd, int unbiased, int pool_h, int pool_w, const float* res,
-                         float* gx, float* amax, bool* amax_served, void* stream) {
-    if (!gh || !x || !mean || !rstd || !gx || n <= 0 || c <= 0 || h <= 0 || w <= 0) return SDA_E_BADARG;
-    // (zeroed by a kernel, not a 4-byte memset: see sda_absmax)
-    if (amax) hipLaunchKernelGGL(ln_amax_zero_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, amax);
-    const int shape = pool_h * 10 + pool_w;          // 11: no pooling, 12: 1-D nets (length axis only), 22: 2-D nets
-    if (shape != 11 && shape != 12 && shape != 22) return SDA_E_UNSUPPORTED;
-    const int64_t npix = (int64_t)n * h * w;
-    const int64_t blocks = (npix + LN_THREADS - 1) / LN_THREADS;
-    if (blocks > 0x7fffffffLL) return SDA_E_UNSUPPORTED;
-    dim3 grid((unsigned)blocks), block(LN_THREADS);
-    hipStream_t s = (hipStream_t)stream;
-    if (npix < LN_BWD_SMALL_PIXELS) {
-        dim3 gs((unsigned)((npix + 3) / 4));
-        if (shape == 11)
-            hipLaunchKernelGGL((ln_bwd_wave_kernel<1, 1>), gs, block, 0, s, gh, x, npix, c, h, w, mod, mod_sn, mean, rstd,
-                               unbiased, res, gx);
-        else if (shape == 12)
-            hipLaunchKernelGGL((ln_bwd_wave_kernel<1, 2>), gs, block, 0, s, gh, x, npix, c, h, w, mod, mod_sn, mean, rstd,
-                               unbiased, res, gx);
-        else
-            hipLaunchKernelGGL((ln_bwd_wave_kernel<2, 2>), gs, block, 0, s, gh, x, npix, c, h, w, mod, mod_sn, mean, rstd,
-                               unbiased, res, gx);
-        return sda_launch_status();
-    }
-    const bool quad_ok = shape == 11 && (h * w) % 4 == 0 && c > 48 && c <= 384 &&
-                         ((reinterpret_cast<uintptr_t>(gh) | reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(gx) |
-                           reinterpret_cast<uintptr_t>(mean) | reinterpret_cast<uintptr_t>(rstd) |
-                           reinterpret_cast<uintptr_t>(res)) & 15) == 0;
-    static const int quad_mode = getenv("SDA_LN_BWD_QUAD") ? atoi(getenv("SDA_LN_BWD_QUAD")) : 1;
-    if (quad_ok && quad_mode) {
-        const int hw = h * w;
-        const int64_t nquad = npix / 4;
-        // (lanes per quad x channels per lane: c = 96: 8 x 12, 128-byte runs; c = 192 / 384: 16 x 12 / 16 x 24, 64-byte runs)
-        static const bool fit = !(getenv("SDA_LN_FIT") && atoi(getenv("SDA_LN_FIT")) == 0);      // (exact-fit layouts: see sda_ln_stats)
-        if (fit && c <= 64) {
-            dim3 gr((unsigned)((nquad + 31) / 32));
-            hipLaunchKernelGGL((ln_bwd_quad_kernel<8, 8>), gr, block, 0, s, gh, x, nquad, c, hw, w, mod, mod_sn, mean, rstd, unbiased, res, gx, amax); *amax_served = amax != nullptr;
-        } else if (fit && c > 96 && c <= 128 && quad_mode != 3 && quad_mode != 4) {
-            dim3 gr((unsigned)((nquad + 31) / 32));
-            hipLaunchKernelGGL((ln_bwd_quad_kernel<8, 16>), gr, block, 0, s, gh, x, nquad, c, hw, w, mod, mod_sn, mean, rstd, unbiased, res, gx, amax); *amax_served = amax != nullptr;
-        } else if (fit && c > 192 && c <= 256 && quad_mode != 4) {
-            dim3 gr((unsigned)((nquad + 15) / 16));
-            hipLaunchKernelGGL((ln_bwd_quad_kernel<16, 16>), gr, block, 0, s, gh, x, nquad, c, hw, w, mod, mod_sn, mean, rstd, unbiased, res, gx, amax); *amax_served = amax != nullptr;
-        } else if (c <= 96) {
-            dim3 gr((unsigned)((nquad + 31) / 32));         // 8 quads per wavefront, 4 wavefronts per workgroup
-            hipLaunchKernelGGL((ln_bwd_quad_kernel<8, 12>), gr, block, 0, s, gh, x, nquad, c, hw, w, mod, mod_sn, mean, rstd, unbiased, res, gx, amax); *amax_served = amax != nullptr;
-        } else if (c <= 192 && quad_mode == 4) {            // (A/B: two cooperating wavefronts, 8 lanes x 12 channels each)
-            dim3 gr((unsigned)((nquad + 15) / 16));
-            hipLaunchKernelGGL((ln_bwd_quad_kernel<8, 12, 1, 2>), gr, block, 0, s, gh, x, nquad, c, hw, w, mod, mod_sn, mean, rstd, unbiased, res, gx, amax); *amax_served = amax != nullptr;
-        } else if (c > 192 && quad_mode == 4) {             // (A/B: four cooperating wavefronts)
-            dim3 gr((unsigned)((nquad + 7) / 8));
-            hipLaunchKernelGGL((ln_bwd_quad_kernel<8, 12, 1, 4>), gr, block, 0, s, gh, x, nquad, c, hw, w, mod, mod_sn, mean, rstd, unbiased, res, gx, amax); *amax_served = amax != nullptr;
-        } else if (c <= 192 && quad_mode != 3) {
-            // 8 lanes x 24 channels: 128-byte runs like the 96-channel level (one wavefront per SIMD -- 376 registers -- but with the
-            // residual loads ahead of the reduction it beats 16 x 12's 64-byte runs: 1.21 -> 1.07 ms at 120 windows, 5.0 -> 5.65 TB/s;
-            // before that change it lost, 4.48 vs 4.87.  SDA_LN_BWD_QUAD=3 keeps 16 x 12 for A/B.  384 channels as 32 x 12: 3.8 vs 5.0 TB/s)
-            dim3 gr((unsigned)((nquad + 31) / 32));
-            hipLaunchKernelGGL((ln_bwd_quad_kernel<8, 24>), gr, block, 0, s, gh, x, nquad, c, hw, w, mod, mod_sn, mean, rstd, unbiased, res, gx, amax); *amax_served = amax != nullptr;
-        } else if (c <= 192) {
-            dim3 gr((unsigned)((nquad + 15) / 16));
-            hipLaunchKernelGGL((ln_bwd_quad_kernel<16, 12>), gr, block, 0, s, gh, x, nquad, c, hw, w, mod, mod_sn, mean, rstd, unbiased, res, gx, amax); *amax_served = amax != nullptr;
-        } else {
-            dim3 gr((unsigned)((nquad + 15) / 16));
-            hipLaunchKernelGGL((ln_bwd_quad_kernel<16, 24>), gr, block, 0, s, gh, x, nquad, c, hw, w, mod, mod_sn, mean, rstd, unbiased, res, gx, amax); *amax_served = amax != nullptr;
-        }
-    } else if (shape == 11 && c > 48 && c <= 384 && blocks * 8 <= 0x7fffffffLL) {
-        // lanes per pixel x channels per lane, picked per width from measurements on the Kolmogorov net's three levels
-        // (c = 96: 4 x 24 1.57 ms vs 2 x 48 2.43, 8 x 12 1.85;  c = 192: 8 x 24 0.86 vs 4 x 48 1.13;  c = 384: 8 x 48 0.59 vs 16 x 24 0.82)
-        const int hw = h * w;
-        const int split = c <= 96 ? 4 : 8;
-        dim3 gr((unsigned)((npix * split + LN_THREADS - 1) / LN_THREADS));
-        if (c <= 96) hipLaunchKernelGGL((ln_bwd_split_kernel<4, 24>), gr, block, 0, s, gh, x, npix, c, hw, w, mod, mod_sn, mean, rstd, unbiased, res, gx);
-        else if (c <= 192) hipLaunchKernelGGL((ln_bwd_split_kernel<8, 24>), gr, block, 0, s, gh, x, npix, c, hw, w, mod, mod_sn, mean, rstd, unbiased, res, gx);
-        else hipLaunchKernelGGL((ln_bwd_split_kernel<8, 48>), gr, block, 0, s, gh, x, npix, c, hw, w, mod, mod_sn, mean, rstd, unbiased, res, gx);
-    } else if (shape == 22 && quad_mode && w % 4 == 0 && c > 48 && c <= 384 &&
-               ((reinterpret_cast<uintptr_t>(gh) | reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(gx) |
-                 reinterpret_cast<uintptr_t>(mean) | reinterpret_cast<uintptr_t>(rstd) | reinterpret_cast<uintptr_t>(res)) & 15) == 0) {
-        // (the up-sampling tails: gh at twice the resolution; 2 w floats per row keep every 16-byte load aligned)
-        const int hw = h * w;
-        const int64_t nquad = npix / 4;
-        if (c <= 96) {
-            dim3 gr((unsigned)((nquad + 31) / 32));
-            hipLaunchKernelGGL((ln_bwd_quad_kernel<8, 12, 2>), gr, block, 0, s, gh, x, nquad, c, hw, w, mod, mod_sn, mean, rstd, unbiased, res, gx, amax); *amax_served = amax != nullptr;
-        } else if (c <= 192) {
-            dim3 gr((unsigned)((nquad + 15) / 16));
-            hipLaunchKernelGGL((ln_bwd_quad_kernel<16, 12, 2>), gr, block, 0, s, gh, x, nquad, c, hw, w, mod, mod_sn, mean, rstd, unbiased, res, gx, amax); *amax_served = amax != nullptr;
-        } else {
-            dim3 gr((unsigned)((nquad + 15) / 16));
-            hipLaunchKernelGGL((ln_bwd_quad_kernel<16, 24, 2>), gr, block, 0, s, gh, x, nquad, c, hw, w, mod, mod_sn, mean, rstd, unbiased, res, gx, amax); *amax_served = amax != nullptr;
-        }
-    } else if (shape == 22 && c > 48 && c <= 384 && blocks * 8 <= 0x7fffffffLL) {
-        const int hw = h * w;
-        const int split = c <= 96 ? 4 : 8;
-        dim3 gr((unsigned)((npix * split + LN_THREADS - 1) / LN_THREADS));
-        if (c <= 96) hipLaunchKernelGGL((ln_bwd_split_kernel<4, 24, 2>), gr, block, 0, s, gh, x, npix, c, hw, w, mod, mod_sn, mean, rstd, unbiased, res, gx);
-        else if (c <= 192) hipLaunchKernelGGL((ln_bwd_split_kernel<8, 24, 2>), gr, block, 0, s, gh, x, npix, c, hw, w, mod, mod_sn, mean, rstd, unbiased, res, gx);
-        else hipLaunchKernelGGL((ln_bwd_split_kernel<8, 48, 2>), gr, block, 0, s, gh, x, npix, c, hw, w, mod, mod_sn, mean, rstd, unbiased, res, gx);
-    } else if (shape == 11) {
-        hipLaunchKernelGGL((ln_bwd_kernel<1, 1>), grid, block, 0, s, gh, x, npix, c, h, w, mod, mod_sn, mean, rstd,
-                           unbiased, res, gx);
-    } else if (shape == 12) {
-        hipLaunchKernelGGL((ln_bwd_kernel<1, 2>), grid, block, 0, s, gh, x, npix, c, h, w, mod, mod_sn, mean, rstd,
-                           unbiased, res, gx);
-    } else {
-        hipLaunchKernelGGL((ln_bwd_kernel<2, 2>), grid, block, 0, s, gh, x, npix, c, h, w, mod, mod_sn, mean, rstd,
-                           unbiased, res, gx);
-    }
-    return sda_launch_status();
 }

@@ -180,6 +180,49 @@ def test_ln_stats_apply_bwd(dev):
         assert_close(gx.cpu(), gx_ref + res, TOL, what=f'ln_bwd pool={pool}')
 
 
+def _ln_case(dev, shape, pool):
+    """One shape through ln_stats, ln_apply and ln_bwd, as in test_ln_stats_apply_bwd (same reference, same TOL)."""
+    from sda_amd import ops
+    n, c, h, w_ = shape
+    x = (torch.randn(n, c, h, w_) * 3 + 1).requires_grad_(True)
+    mod = torch.randn(n, c)
+    xd, md = x.detach().to(dev), mod.to(dev)
+    mean = torch.empty(n * h * w_, device=dev); rstd = torch.empty_like(mean)
+    ops.ln_stats(xd, md, c, 1e-5, True, mean, rstd)
+    y = torch.empty_like(xd)
+    ops.ln_apply(xd, md, c, mean, rstd, y)
+    href = O.layer_norm(x + mod[:, :, None, None], dim=1)
+    assert_close(y.cpu(), href, TOL, what=f'ln_apply {shape}')
+    hup = href.repeat_interleave(pool[1], -1).repeat_interleave(pool[0], -2)
+    g = torch.randn_like(hup)
+    res = torch.randn(n, c, h, w_)
+    gx_ref, = torch.autograd.grad(hup, x, g)
+    gx = torch.empty_like(xd)
+    ops.ln_bwd(g.to(dev), xd, h, w_, md, c, mean, rstd, True, pool, res.to(dev), gx)
+    assert_close(gx.cpu(), gx_ref + res, TOL, what=f'ln_bwd {shape} pool={pool}')
+
+
+@pytest.mark.parametrize('c', [48, 49, 64, 65, 96, 97, 128, 129, 192, 193, 256, 257, 384, 385])
+def test_ln_layout_table_boundaries(dev, c):
+    """Every boundary of the width -> layout table of csrc/norm.hip (LN_QUAD) and its neighbour, on the smallest shapes that reach the
+    quad kernels: 16384 pixels for the statistics (and the backward), 4096 for the backward alone, with and without a 2 x 2
+    up-sample, and 2048 (cotangent at 64 x 128), where the wave-per-pixel kernel takes the up-sample at every width.  48 and 385
+    channels are the first widths on either side that no quad kernel serves."""
+    torch.manual_seed(100 + c)
+    _ln_case(dev, (1, c, 128, 128), (1, 1))
+    _ln_case(dev, (1, c, 64, 64), (1, 1))
+    _ln_case(dev, (1, c, 64, 64), (2, 2))
+    _ln_case(dev, (1, c, 32, 64), (2, 2))
+
+
+@pytest.mark.parametrize('shape', [(1, 128, 127, 130), (1, 128, 64, 65)])
+def test_ln_fallbacks_beside_the_quad_path(dev, shape):
+    """h w % 4 != 0 above the statistics threshold (16510 pixels: the register and split kernels must still be picked where
+    the quad path is not eligible), and a shape below it (4160 pixels: wave-per-pixel statistics)."""
+    torch.manual_seed(13)
+    _ln_case(dev, shape, (1, 1))
+
+
 def test_time_embed_and_projection(dev):
     from sda_amd import ops
     torch.manual_seed(12)
