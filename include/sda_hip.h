@@ -633,6 +633,77 @@ int64_t sda_conv_h2_rows_packed_bytes(int rows, int k, int ntap);
 float sda_conv_h2_scale(float amax);
 int sda_absmax(const float* x, int64_t numel, float* amax, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Markov chains and the bootstrap particle filter (csrc/chain.hip; additive, ABI stays v13): the simulators of sda/mcs.py:85-241
+ * (DiscreteODE.transition = `steps` RK4 sub-steps of dt / steps, k1..k4 in the reference's operation order, fp32) and the filter
+ * of sda/utils.py:168-200 as one launch per PHASE -- advance (+ log-weights), cdf, resample, and one traceback at the end.  No
+ * kernel waits for another workgroup.
+ *
+ * sda_chain_advance: m particle states [m][d] (particle stride in_sp floats, components contiguous), optionally read through an
+ *   ancestor vector (x_in[anc[j]]), advanced `transitions` >= 1 times in ONE launch.  every = 0: out[j * out_sp + c] = the last
+ *   state; every = 1: out[t * out_st + j * out_sp + c] = the state after transition t (so a caller gets (length, m, d) or
+ *   (m, length, d) by its choice of strides).  model.noise_std > 0 adds noise_std * z after every transition, where the z of particle
+ *   slot j at transition t is BY DEFINITION row j of sda_randn_rows(out[m][d], seed, row0, draw = draw0 + t): same counters, same
+ *   Box-Muller, so it does not depend on the launch geometry.  obs != NULL (kinds 0 and 1 only): the log-weights of
+ *   sda_bpf_logweights for the LAST state, in the same launch.
+ *   Lorenz-63 / Lotka-Volterra: one particle per lane, state in registers.  Lorenz-96 (4 <= d <= 64): a particle's components on the
+ *   lanes of a sub-group of a wave (width = next power of two >= d), the rolls are cross-lane shuffles with the index modulo d.
+ * sda_chain_log_prob: out[b] = sum_i sum_c log N(x[b][i+1][c]; RK4(x[b][i])[c], model.noise_std) (NoisyLorenz63.log_prob summed over
+ *   the trajectory, experiments/lorenz/utils.py:82-88); x strides sb (trajectory) / sl (time) floats; the sum is float64.
+ * sda_bpf_logweights: logw[j] = sum_k log N(y[k]; (x[j][idx[k]] - shift[k]) / scale[k], sigma) and pmax[workgroup] = the maximum over
+ *   the workgroup's 256 particles (sda_bpf_logweights_blocks(m) values).
+ * sda_bpf_cdf: w[j] = expf(logw[j] - max logw) (fp32) and cdf[j] = w[0] + ... + w[j] in float64, un-normalised; any m >= 1 (one
+ *   workgroup walks the vector in chunks).  pmax may be NULL (the maximum is then taken over logw).  status[0] = 0, or 1 when every
+ *   logw is -inf or any is NaN (cdf is then the uniform j + 1, so that a later resample stays defined); read it once, at the end.
+ * sda_bpf_resample: anc[j] = the smallest i with cdf[i] > u cdf[m - 1], clamped to m - 1 (binary search), u in (0, 1) = (2 v + 1) / 2^53
+ *   with v = the 52 bits (w0 >> 6) * 2^26 + (w1 >> 6) of the Philox counter {j_lo, obs_lo, 0x80000000 | j_hi, 'RESA'} under the
+ *   key `seed`: i.i.d. categorical draws with replacement (torch.multinomial(w, m, replacement=True)).  Noise counters have bit
+ *   31 of word 2 clear for t < 2^31 (csrc/philox.hpp), so the two streams never meet.
+ * sda_bpf_traceback: S[t][slot][d] (strides s_st / s_sp) = the UN-resampled states t = 0 .. n_obs * step, anc[k][m] = the ancestors drawn
+ *   at observation k; out[j][t][d] (contiguous) = the trajectory the reference obtains by re-gathering the whole history at every
+ *   observation: i_N = j, i_k = anc[k][i_{k+1}], times k step + 1 .. (k + 1) step from S[t][i_k], time 0 from S[0][i_0].
+ * ------------------------------------------------------------------------------------------ */
+#define SDA_CHAIN_LORENZ63 0        /* p = {sigma, rho, beta}          d = 3 */
+#define SDA_CHAIN_LOTKA_VOLTERRA 1  /* p = {alpha, beta, delta, gamma} d = 2 */
+#define SDA_CHAIN_LORENZ96 2        /* p = {F}                         4 <= d <= 64 */
+#define SDA_CHAIN_MAXOBS 64
+typedef struct {
+    int32_t kind, d, steps;
+    float h;                /* dt / steps, rounded to fp32 */
+    float p[4];
+    float noise_std;        /* 0: deterministic */
+} sda_chain_model;
+typedef struct {
+    int32_t k;              /* observed components, 1 <= k <= d */
+    int32_t idx[SDA_CHAIN_MAXOBS];
+    float shift[SDA_CHAIN_MAXOBS], scale[SDA_CHAIN_MAXOBS];
+    float sigma;
+    const float* y;         /* device, [k] */
+} sda_chain_obs;
+typedef struct {
+    sda_chain_model model;
+    const float* x_in;
+    int64_t in_sp;
+    const int32_t* anc;     /* NULL: particle j reads x_in[j] */
+    float* out;
+    int64_t out_st, out_sp;
+    int32_t every;
+    int32_t m, transitions;
+    uint64_t seed;
+    int64_t row0, draw0;
+    const sda_chain_obs* obs;   /* HOST pointer; NULL: no weights */
+    float* logw;
+    float* pmax;
+} sda_chain_adv;
+int sda_chain_advance(const sda_chain_adv* a, void* stream);
+int sda_chain_log_prob(const sda_chain_model* model, const float* x, int b, int len, int64_t sb, int64_t sl, double* out, void* stream);
+int sda_bpf_logweights(const float* x, int m, int64_t sp, int d, const sda_chain_obs* obs, float* logw, float* pmax, void* stream);
+int sda_bpf_logweights_blocks(int m);
+int sda_bpf_cdf(const float* logw, int m, const float* pmax, int npmax, float* w, double* cdf, int32_t* status, void* stream);
+int sda_bpf_resample(const double* cdf, int m, uint64_t seed, int64_t obs_index, int32_t* anc, void* stream);
+int sda_bpf_traceback(const float* S, int64_t s_st, int64_t s_sp, const int32_t* anc, int m, int n_obs, int step, int d, float* out,
+                      void* stream);
+
 #ifdef __cplusplus
 }
 #endif

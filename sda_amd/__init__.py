@@ -24,7 +24,7 @@ def __getattr__(name):
     raise AttributeError(f'module {__name__!r} has no attribute {name!r}')
 
 
-def install_as_sda() -> None:
+def install_as_sda(native_chains: bool = False) -> None:
     """Make ``import sda`` / ``from sda.{mcs,nn,score,utils} import *`` resolve to this package, so that the reference's driver
     files (experiments/lorenz/utils.py:8-10, experiments/kolmogorov/utils.py:11-13, lorenz/eval.py:9-11) run unchanged:
 
@@ -32,13 +32,18 @@ def install_as_sda() -> None:
         from utils import *            # the reference's experiments/<name>/utils.py, unmodified
 
     Every submodule is registered under its ``sda.`` name explicitly -- a bare ``sys.modules['sda'] = sda_amd`` would make
-    the import system load second copies of the submodules (distinct classes) on ``import sda.<name>``."""
+    the import system load second copies of the submodules (distinct classes) on ``import sda.<name>``.
+
+    ``native_chains=True`` also rebinds the chain classes of ``sda.mcs`` (placeholders by default, or the user's own sda/mcs.py)
+    to the device implementations of ``sda_amd.chains``, so that ``make_chain()`` / ``posterior()`` of a driver run here."""
     me = sys.modules[__name__]
     sys.modules['sda'] = me
     # every public submodule is imported BEFORE aliasing: a later `import sda.parallel` must find the one copy, not load a second
-    for sub in ('mcs', 'nn', 'score', 'utils', 'observe', 'training', 'parallel', 'metrics', 'ops', 'engine', 'mlp', 'fused1d', 'experiments',
+    for sub in ('mcs', 'chains', 'nn', 'score', 'utils', 'observe', 'training', 'parallel', 'metrics', 'ops', 'engine', 'mlp', 'fused1d', 'experiments',
                 'experiments.kolmogorov', 'experiments.lorenz'):
         importlib.import_module('.' + sub, __name__)
     for full, mod in list(sys.modules.items()):
         if full.startswith(__name__ + '.') and mod is not None:
             sys.modules['sda.' + full[len(__name__) + 1:]] = mod
+    if native_chains:
+        sys.modules[__name__ + '.chains'].install()

@@ -176,6 +176,35 @@ class WgradDesc(Structure):
     ]
 
 
+CHAIN_KINDS = {'lorenz63': 0, 'lotka_volterra': 1, 'lorenz96': 2}
+CHAIN_MAXOBS = 64
+
+
+class ChainModel(Structure):
+    """Mirror of `struct sda_chain_model` (include/sda_hip.h)."""
+    _fields_ = [('kind', c_int32), ('d', c_int32), ('steps', c_int32), ('h', c_float), ('p', c_float * 4), ('noise_std', c_float)]
+
+
+class ChainObs(Structure):
+    """Mirror of `struct sda_chain_obs` (include/sda_hip.h)."""
+    _fields_ = [('k', c_int32), ('idx', c_int32 * CHAIN_MAXOBS), ('shift', c_float * CHAIN_MAXOBS), ('scale', c_float * CHAIN_MAXOBS),
+                ('sigma', c_float), ('y', c_fp)]
+
+
+class ChainAdv(Structure):
+    """Mirror of `struct sda_chain_adv` (include/sda_hip.h)."""
+    _fields_ = [
+        ('model', ChainModel),
+        ('x_in', c_fp), ('in_sp', c_int64), ('anc', c_fp),
+        ('out', c_fp), ('out_st', c_int64), ('out_sp', c_int64),
+        ('every', c_int32),
+        ('m', c_int32), ('transitions', c_int32),
+        ('seed', c_uint64), ('row0', c_int64), ('draw0', c_int64),
+        ('obs', POINTER(ChainObs)),
+        ('logw', c_fp), ('pmax', c_fp),
+    ]
+
+
 SIGNATURES = {
     'sda_abi_version': (c_int, []),
     'sda_conv_igemm': (c_int, [POINTER(ConvDesc), c_void_p]),
@@ -262,6 +291,13 @@ SIGNATURES = {
     'sda_conv3d': (c_int, [POINTER(Conv3dDesc), c_void_p]),
     'sda_conv3d_packed_floats': (c_int64, [c_int, c_int, c_int, c_int, c_int, c_int]),
     'sda_pack_conv3d_weight': (c_int, [c_fp, c_int, c_int, c_int, c_int, c_int, c_int, c_fp, c_void_p]),
+    'sda_chain_advance': (c_int, [POINTER(ChainAdv), c_void_p]),
+    'sda_chain_log_prob': (c_int, [POINTER(ChainModel), c_fp, c_int, c_int, c_int64, c_int64, c_fp, c_void_p]),
+    'sda_bpf_logweights': (c_int, [c_fp, c_int, c_int64, c_int, POINTER(ChainObs), c_fp, c_fp, c_void_p]),
+    'sda_bpf_logweights_blocks': (c_int, [c_int]),
+    'sda_bpf_cdf': (c_int, [c_fp, c_int, c_fp, c_int, c_fp, c_fp, c_fp, c_void_p]),
+    'sda_bpf_resample': (c_int, [c_fp, c_int, c_uint64, c_int64, c_fp, c_void_p]),
+    'sda_bpf_traceback': (c_int, [c_fp, c_int64, c_int64, c_fp, c_int, c_int, c_int, c_int, c_fp, c_void_p]),
     'sda_pool3d_sum': (c_int, [c_fp, c_int64, c_int, c_int, c_int, c_int, c_int, c_int, c_fp, c_void_p]),
 }
 

@@ -1,0 +1,352 @@
+r"""Markov chains of the reference (sda/mcs.py:22-241) on the device, and the fused bootstrap particle filter.
+
+``MarkovChain``, ``DiscreteODE``, ``Lorenz63``, ``NoisyLorenz63``, ``Lorenz96`` and ``LotkaVolterra`` keep the reference's
+constructor arguments and methods.  ``transition`` and ``trajectory`` of the three built-in systems are ONE launch of
+``sda_chain_advance`` (csrc/chain.hip) whatever the length; a user subclass of ``DiscreteODE`` with its own ``f`` -- and any input
+that requires grad -- runs the reference's torch-ops ``rk4`` instead (correct, not fused).  ``DampedSpring`` and
+``KolmogorovFlow`` are not rebuilt.
+
+Noise.  The noisy chain draws one 63-bit seed per call from torch's default CPU generator (``torch.manual_seed`` reproduces a
+run) unless ``seed=`` is given, and advances a draw counter by the number of transitions, so successive calls never reuse
+noise.  The normal added to particle ``r`` at draw ``t`` is row ``r`` of ``ops.randn_rows(.., seed, row0, draw=t)``.
+
+``sda_amd.mcs`` keeps handing out placeholders by default; ``install()`` (or ``sda_amd.install_as_sda(native_chains=True)``)
+rebinds the chain names inside that module to the classes of this one.
+"""
+import abc
+from typing import Callable, Optional, Tuple
+
+import torch
+from torch import Size, Tensor
+from torch.distributions import MultivariateNormal, Normal
+
+from . import ops
+from ._lib import CHAIN_MAXOBS, SdaHipError
+
+__all__ = ['MarkovChain', 'DiscreteODE', 'Lorenz63', 'NoisyLorenz63', 'Lorenz96', 'LotkaVolterra', 'AffineObservation',
+           'probe_affine', 'bpf_fused', 'install']
+
+
+def _draw_seed() -> int:
+    return int(torch.randint(0, 2 ** 63 - 1, (), dtype=torch.int64))
+
+
+class MarkovChain(abc.ABC):
+    r"""Abstract first-order time-invariant Markov chain (sda/mcs.py:22-57)."""
+
+    @abc.abstractmethod
+    def prior(self, shape: Size = (), *, device=None) -> Tensor:
+        r""" x_0 ~ p(x_0) """
+
+    @abc.abstractmethod
+    def transition(self, x: Tensor) -> Tensor:
+        r""" x_i ~ p(x_i | x_{i-1}) """
+
+    def trajectory(self, x: Tensor, length: int, last: bool = False) -> Tensor:
+        r""" (x_1, ..., x_n) ~ \prod_i p(x_i | x_{i-1}) """
+        if last:
+            for _ in range(length):
+                x = self.transition(x)
+            return x
+        X = []
+        for _ in range(length):
+            x = self.transition(x)
+            X.append(x)
+        return torch.stack(X)
+
+
+class DiscreteODE(MarkovChain):
+    r"""Discretized ordinary differential equation (sda/mcs.py:85-122): ``steps`` RK4 sub-steps of ``dt / steps`` per transition."""
+
+    #: (kernel kind, f of the class the kernel implements); None: torch-ops rk4
+    _KERNEL: Optional[Tuple[str, Callable]] = None
+
+    def __init__(self, dt: float = 0.01, steps: int = 1):
+        super().__init__()
+        self.dt, self.steps = dt, steps
+        self._draw = 0
+
+    @staticmethod
+    def rk4(f: Callable[[Tensor], Tensor], x: Tensor, dt: float) -> Tensor:
+        k1 = f(x)
+        k2 = f(x + dt * k1 / 2)
+        k3 = f(x + dt * k2 / 2)
+        k4 = f(x + dt * k3)
+        return x + dt * (k1 + 2 * k2 + 2 * k3 + k4) / 6
+
+    @abc.abstractmethod
+    def f(self, x: Tensor) -> Tensor:
+        r""" f(x) = \frac{dx}{dt} """
+
+    # ---- what the kernel needs; the built-in systems fill these in
+    def _params(self):
+        raise NotImplementedError
+
+    def _noise_std(self) -> float:
+        return 0.0
+
+    def _fused(self, x: Tensor) -> bool:
+        """The kernel serves this call: a built-in system whose ``f`` was not overridden, no autograd through x."""
+        k = type(self)._KERNEL
+        return k is not None and type(self).f is k[1] and not (torch.is_grad_enabled() and x.requires_grad)
+
+    def model(self):
+        kind = type(self)._KERNEL[0]
+        d, params = self._params()
+        return ops.chain_model(kind, d, self.dt, self.steps, params, self._noise_std())
+
+    def _rk4_transition(self, x: Tensor) -> Tensor:
+        for _ in range(self.steps):
+            x = self.rk4(self.f, x, self.dt / self.steps)
+        return x
+
+    def _advance(self, x: Tensor, length: int, every: bool, seed: Optional[int] = None) -> Tensor:
+        model = self.model()
+        if x.shape[-1:] != (model.d,):
+            raise SdaHipError(f'{type(self).__name__}: states of shape {tuple(x.shape)}, expected (..., {model.d})')
+        batch = x.shape[:-1]
+        flat = x.reshape(-1, model.d)
+        if flat.stride(-1) != 1:
+            flat = flat.contiguous()
+        m = flat.shape[0]
+        if length < 1 or m < 1:
+            raise SdaHipError(f'{type(self).__name__}: length {length}, {m} states')
+        draw0 = self._draw
+        if model.noise_std > 0:
+            seed = _draw_seed() if seed is None else int(seed)
+            self._draw += length
+        out = torch.empty((length, m, model.d) if every else (m, model.d), device=x.device, dtype=torch.float32)
+        ops.chain_advance(model, flat, out, length, every=every, out_st=m * model.d, seed=seed or 0, draw0=draw0)
+        return out.reshape((length, *batch, model.d) if every else (*batch, model.d))
+
+    def transition(self, x: Tensor) -> Tensor:
+        if self._fused(x):
+            return self._advance(x, 1, False)
+        return self._rk4_transition(x)
+
+    def trajectory(self, x: Tensor, length: int, last: bool = False) -> Tensor:
+        if self._fused(x) and length >= 1:
+            return self._advance(x, length, not last)
+        return super().trajectory(x, length, last)
+
+
+class Lorenz63(DiscreteODE):
+    r"""Lorenz 1963 dynamics (sda/mcs.py:125-172)."""
+
+    def __init__(self, sigma: float = 10.0, rho: float = 28.0, beta: float = 8 / 3, **kwargs):
+        super().__init__(**kwargs)
+        self.sigma, self.rho, self.beta = sigma, rho, beta
+
+    def prior(self, shape: Size = (), *, device=None) -> Tensor:
+        mu = torch.tensor([0.0, 0.0, 25.0])
+        sigma = torch.tensor([
+            [64.0, 50.0, 0.0],
+            [50.0, 81.0, 0.0],
+            [0.0, 0.0, 75.0],
+        ])
+        return MultivariateNormal(mu, sigma).sample(shape).to(device)
+
+    def f(self, x: Tensor) -> Tensor:
+        return torch.stack((
+            self.sigma * (x[..., 1] - x[..., 0]),
+            x[..., 0] * (self.rho - x[..., 2]) - x[..., 1],
+            x[..., 0] * x[..., 1] - self.beta * x[..., 2],
+        ), dim=-1)
+
+    def _params(self):
+        return 3, (self.sigma, self.rho, self.beta)
+
+    @staticmethod
+    def preprocess(x: Tensor) -> Tensor:
+        mu = x.new_tensor([0.0, 0.0, 25.0])
+        sigma = x.new_tensor([8.0, 9.0, 8.6])
+        return (x - mu) / sigma
+
+    @staticmethod
+    def postprocess(x: Tensor) -> Tensor:
+        mu = x.new_tensor([0.0, 0.0, 25.0])
+        sigma = x.new_tensor([8.0, 9.0, 8.6])
+        return mu + sigma * x
+
+
+Lorenz63._KERNEL = ('lorenz63', Lorenz63.f)
+
+
+class NoisyLorenz63(Lorenz63):
+    r"""Noisy Lorenz 1963 dynamics (sda/mcs.py:175-185): N(RK4(x), sqrt(dt)) transitions."""
+
+    def _noise_std(self) -> float:
+        return self.dt ** 0.5
+
+    def moments(self, x: Tensor) -> Tuple[Tensor, float]:
+        if self._fused(x):
+            model = self.model()
+            model.noise_std = 0.0
+            flat = x.reshape(-1, 3)
+            flat = flat if flat.stride(-1) == 1 else flat.contiguous()
+            out = torch.empty_like(flat, memory_format=torch.contiguous_format)
+            ops.chain_advance(model, flat, out, 1)
+            return out.reshape(x.shape), self.dt ** 0.5
+        return self._rk4_transition(x), self.dt ** 0.5
+
+    def transition(self, x: Tensor, *, seed: Optional[int] = None) -> Tensor:
+        if self._fused(x):
+            return self._advance(x, 1, False, seed)
+        return Normal(*self.moments(x)).sample()
+
+    def trajectory(self, x: Tensor, length: int, last: bool = False, *, seed: Optional[int] = None) -> Tensor:
+        if self._fused(x) and length >= 1:
+            return self._advance(x, length, not last, seed)
+        return MarkovChain.trajectory(self, x, length, last)
+
+    def log_prob(self, x1: Tensor, x2: Tensor) -> Tensor:
+        return Normal(*self.moments(x1)).log_prob(x2).sum(dim=-1)
+
+
+class Lorenz96(DiscreteODE):
+    r"""Lorenz 1996 dynamics (sda/mcs.py:188-211); the kernel serves 4 <= n <= 64."""
+
+    def __init__(self, n: int = 32, F: float = 16.0, **kwargs):
+        super().__init__(**kwargs)
+        self.n, self.F = n, F
+
+    def prior(self, shape: Size = (), *, device=None) -> Tensor:
+        return torch.randn(*shape, self.n).to(device)
+
+    def f(self, x: Tensor) -> Tensor:
+        x1, x2, x3 = [torch.roll(x, i, dims=-1) for i in (1, -2, -1)]
+        return (x1 - x2) * x3 - x + self.F
+
+    def _params(self):
+        return self.n, (self.F,)
+
+    def _fused(self, x: Tensor) -> bool:
+        return 4 <= self.n <= 64 and super()._fused(x)
+
+
+Lorenz96._KERNEL = ('lorenz96', Lorenz96.f)
+
+
+class LotkaVolterra(DiscreteODE):
+    r"""Lotka-Volterra dynamics (sda/mcs.py:214-241)."""
+
+    def __init__(self, alpha: float = 1.0, beta: float = 1.0, delta: float = 1.0, gamma: float = 1.0, **kwargs):
+        super().__init__(**kwargs)
+        self.alpha, self.beta = alpha, beta
+        self.delta, self.gamma = delta, gamma
+
+    def prior(self, shape: Size = (), *, device=None) -> Tensor:
+        return torch.rand(*shape, 2).to(device)
+
+    def f(self, x: Tensor) -> Tensor:
+        return torch.stack((
+            self.alpha - self.beta * x[..., 1].exp(),
+            self.delta * x[..., 0].exp() - self.gamma,
+        ), dim=-1)
+
+    def _params(self):
+        return 2, (self.alpha, self.beta, self.delta, self.gamma)
+
+
+LotkaVolterra._KERNEL = ('lotka_volterra', LotkaVolterra.f)
+
+
+# ---------------------------------------------------------------- observation operators the fused filter understands
+class AffineObservation:
+    r"""A(x) = (x[..., index] - shift) / scale: each output is an affine function of ONE state component."""
+
+    def __init__(self, index, shift, scale):
+        self.index = [int(i) for i in index]
+        self.shift = [float(s) for s in shift]
+        self.scale = [float(s) for s in scale]
+        if not (1 <= len(self.index) <= CHAIN_MAXOBS) or len(self.shift) != len(self.index) or len(self.scale) != len(self.index):
+            raise ValueError('AffineObservation: index, shift and scale are equally long lists of 1 to 64 entries')
+        if any(s == 0 for s in self.scale):
+            raise ValueError('AffineObservation: zero scale')
+
+    def __call__(self, x: Tensor) -> Tensor:
+        return (x[..., self.index] - x.new_tensor(self.shift)) / x.new_tensor(self.scale)
+
+    def __repr__(self):
+        return f'AffineObservation(index={self.index}, shift={self.shift}, scale={self.scale})'
+
+
+def probe_affine(A: Callable[[Tensor], Tensor], chain: MarkovChain, d: int, rtol: float = 1e-6) -> Optional[AffineObservation]:
+    """Recover an AffineObservation from a callable, or None: evaluate A at 0 and at the d unit vectors (float64, host), require
+    every output to depend on exactly one component, then confirm A(x) = the recovered map on 64 prior-scale random states to
+    `rtol` of the largest output.  torch's global generator is left as it was."""
+    if isinstance(A, AffineObservation):
+        return A
+    try:
+        with torch.no_grad():
+            b = A(torch.zeros(d, dtype=torch.float64))
+            if b.dim() != 1 or not 1 <= b.numel() <= min(d, CHAIN_MAXOBS) or not b.is_floating_point():
+                return None
+            cols = A(torch.eye(d, dtype=torch.float64))
+            if cols.shape != (d, b.numel()):
+                return None
+            M = (cols - b).T                                  # (k, d): output r = sum_c M[r, c] x[c] + b[r]
+            if not (torch.isfinite(M).all() and torch.isfinite(b).all()) or ((M != 0).sum(dim=1) != 1).any():
+                return None
+            index = M.abs().argmax(dim=1)
+            gain = M[torch.arange(len(index)), index]
+            obs = AffineObservation(index.tolist(), (-b / gain).tolist(), (1 / gain).tolist())
+            with torch.random.fork_rng(devices=[]):
+                torch.manual_seed(0)
+                x = chain.prior((64,)).double().cpu()
+            got, want = A(x), obs(x)
+            if got.shape != want.shape or not ((got - want).abs().max() <= rtol * want.abs().max().clamp_min(1e-300)):
+                return None
+            return obs
+    except Exception:  # noqa: BLE001 -- a callable that cannot take these inputs is simply not recognised
+        return None
+
+
+def bpf_fused(chain: DiscreteODE, x: Tensor, y: Tensor, obs: AffineObservation, sigma: float, step: int = 1, *,
+              seed: Optional[int] = None, record: Optional[dict] = None) -> Tensor:
+    r"""Bootstrap particle filter (sda/utils.py:168-200) with ``chain.transition`` and the Gaussian likelihood
+    N(y_i; obs(x), sigma): per observation ONE advance launch (``step`` transitions read through the previous ancestors, the
+    log-weights of the last state), one cdf launch and one resample launch; one traceback at the end.  x (M, d) initial
+    particles, y (N, k); returns (M, N step + 1, d).  Raises SdaHipError if an observation leaves no particle with weight.
+    ``record``: a dict that receives the un-resampled states ``S`` and the ancestors ``anc`` (tests)."""
+    ops._dev(x)
+    model = chain.model()
+    m, d = x.shape
+    n = len(y)
+    y = y.to(device=x.device, dtype=torch.float32).reshape(n, -1).contiguous()
+    if y.shape[1] != len(obs.index) or n < 1 or step < 1:
+        raise SdaHipError(f'bpf_fused: {tuple(y.shape)} observations for {len(obs.index)} observed components, step {step}')
+    seed = _draw_seed() if seed is None else int(seed)
+    draw0 = chain._draw
+    chain._draw += n * step
+    dev = x.device
+    S = torch.empty(n * step + 1, m, d, device=dev, dtype=torch.float32)
+    S[0] = x
+    anc = torch.empty(n, m, device=dev, dtype=torch.int32)
+    status = torch.zeros(n, device=dev, dtype=torch.int32)
+    logw = torch.empty(m, device=dev, dtype=torch.float32)
+    pmax = torch.empty(ops._lib.load().sda_bpf_logweights_blocks(m), device=dev, dtype=torch.float32)
+    w = torch.empty(m, device=dev, dtype=torch.float32)
+    cdf = torch.empty(m, device=dev, dtype=torch.float64)
+    o = ops.chain_obs(obs.index, obs.shift, obs.scale, sigma, y[0])
+    for k in range(n):
+        o.y = y[k].data_ptr()
+        ops.chain_advance(model, S[k * step], S[k * step + 1:], step, every=True, out_st=m * d, anc=anc[k - 1] if k else None,
+                          seed=seed, draw0=draw0 + k * step, obs=o, logw=logw, pmax=pmax)
+        ops.bpf_cdf(logw, pmax, w=w, cdf=cdf, status=status[k:k + 1], check=False)
+        ops.bpf_resample(cdf, seed, k, anc[k])
+    out = ops.bpf_traceback(S, anc, step)
+    ops.bpf_check(status)                                    # the one read-back of the filter
+    if record is not None:
+        record.update(S=S, anc=anc, seed=seed, draw0=draw0)
+    return out
+
+
+def install() -> None:
+    """Rebind the chain names inside ``sda_amd.mcs`` (= ``sda.mcs`` after ``install_as_sda``) to the classes of this module;
+    call it before a driver's ``from sda.mcs import *``."""
+    import importlib
+    mcs = importlib.import_module(__package__ + '.mcs')
+    for name in ('MarkovChain', 'DiscreteODE', 'Lorenz63', 'NoisyLorenz63', 'Lorenz96', 'LotkaVolterra'):
+        setattr(mcs, name, globals()[name])
+    mcs.SOURCE = __name__

@@ -1,0 +1,541 @@
+// Markov chains (sda/mcs.py:85-241) and the bootstrap particle filter (sda/utils.py:168-200) of the reference's Lorenz
+// evaluation (experiments/lorenz/eval.py:44-68), as one launch per PHASE: advance (+ log-weights) -> cdf -> resample per
+// observation, one traceback at the end.  No kernel waits for another workgroup: every hand-off is a launch boundary.
+// The arithmetic of a transition lives in __host__ __device__ functions; under SDA_HOST_EMU the same functions run as plain
+// loops over host arrays (bottom of the file), which is what the CPU tests check.
+//
+// Latency-bound by design: 16 384 particles x 3 floats is 192 KiB, one RK4 transition is ~100 flops per particle.  What the
+// fusion removes is the ~40 elementwise launches per transition and the O(M T^2) history copies of the reference's
+// cat / x[j] (sda/utils.py:193-200).
+#include "sda_common.hpp"
+#include "philox.hpp"
+
+#define CH_THREADS 256
+
+// ---------------------------------------------------------------- RK4 (sda/mcs.py:98-110), one component, reference order
+__host__ __device__ __forceinline__ float rk4_half(float x, float h, float k) { return x + h * k / 2.0f; }
+__host__ __device__ __forceinline__ float rk4_full(float x, float h, float k) { return x + h * k; }
+__host__ __device__ __forceinline__ float rk4_comb(float x, float h, float k1, float k2, float k3, float k4) {
+    return x + h * (k1 + 2.0f * k2 + 2.0f * k3 + k4) / 6.0f;
+}
+
+// sda/mcs.py:153-158
+__host__ __device__ __forceinline__ void lorenz63_f(const float* p, const float* x, float* f) {
+    f[0] = p[0] * (x[1] - x[0]);
+    f[1] = x[0] * (p[1] - x[2]) - x[1];
+    f[2] = x[0] * x[1] - p[2] * x[2];
+}
+// sda/mcs.py:237-241
+__host__ __device__ __forceinline__ void lotka_volterra_f(const float* p, const float* x, float* f) {
+    f[0] = p[0] - p[1] * expf(x[1]);
+    f[1] = p[2] * expf(x[0]) - p[3];
+}
+// sda/mcs.py:208-211: (roll(x, 1) - roll(x, -2)) roll(x, -1) - x + F, one component
+__host__ __device__ __forceinline__ float lorenz96_f(float xm1, float xp2, float xp1, float x, float F) {
+    return (xm1 - xp2) * xp1 - x + F;
+}
+
+// one transition (model.steps RK4 sub-steps) of a small-state chain, state in registers
+template <int KIND>
+__host__ __device__ __forceinline__ void chain_small_transition(const sda_chain_model& m, float* x) {
+    constexpr int D = KIND == SDA_CHAIN_LORENZ63 ? 3 : 2;
+    for (int s = 0; s < m.steps; ++s) {
+        float k1[D], k2[D], k3[D], k4[D], t[D];
+        if (KIND == SDA_CHAIN_LORENZ63) lorenz63_f(m.p, x, k1); else lotka_volterra_f(m.p, x, k1);
+#pragma unroll
+        for (int c = 0; c < D; ++c) t[c] = rk4_half(x[c], m.h, k1[c]);
+        if (KIND == SDA_CHAIN_LORENZ63) lorenz63_f(m.p, t, k2); else lotka_volterra_f(m.p, t, k2);
+#pragma unroll
+        for (int c = 0; c < D; ++c) t[c] = rk4_half(x[c], m.h, k2[c]);
+        if (KIND == SDA_CHAIN_LORENZ63) lorenz63_f(m.p, t, k3); else lotka_volterra_f(m.p, t, k3);
+#pragma unroll
+        for (int c = 0; c < D; ++c) t[c] = rk4_full(x[c], m.h, k3[c]);
+        if (KIND == SDA_CHAIN_LORENZ63) lorenz63_f(m.p, t, k4); else lotka_volterra_f(m.p, t, k4);
+#pragma unroll
+        for (int c = 0; c < D; ++c) x[c] = rk4_comb(x[c], m.h, k1[c], k2[c], k3[c], k4[c]);
+    }
+}
+
+// the four normals of quad q of global row `grow` in draw t: what sda_randn_rows writes to elements 4q .. 4q+3 of that row
+__host__ __device__ __forceinline__ void chain_noise4(uint64_t seed, uint64_t grow, int64_t t, int64_t q, float* z) {
+    const philox4 w = philox_noise_words(q, grow, t, (uint32_t)seed, (uint32_t)(seed >> 32));
+    box_muller(w.v[0], w.v[1], z[0], z[1]);
+    box_muller(w.v[2], w.v[3], z[2], z[3]);
+}
+
+// log N(v; mu, s) as torch.distributions.Normal.log_prob writes it, in float64
+__host__ __device__ __forceinline__ double normal_log_prob(double v, double mu, double s) {
+    const double d = v - mu;
+    return -(d * d) / (2.0 * s * s) - log(s) - 0.91893853320467274178;
+}
+
+// the affine-select log-weight of one state (y: the k observed values)
+__host__ __device__ __forceinline__ float obs_logweight(const sda_chain_obs& o, const float* y, const float* x) {
+    double l = 0.0;
+    for (int k = 0; k < o.k; ++k) l += normal_log_prob((double)((x[o.idx[k]] - o.shift[k]) / o.scale[k]), (double)y[k], (double)o.sigma);
+    return (float)l;
+}
+
+// u in (0, 1): 52 Philox bits and a set 53rd, exact in float64
+__host__ __device__ __forceinline__ double bpf_uniform(uint64_t seed, int64_t j, int64_t obs) {
+    const philox4 w = philox4x32_10((uint32_t)j, (uint32_t)obs, 0x80000000u | (uint32_t)((uint64_t)j >> 32), 0x52455341u,
+                                    (uint32_t)seed, (uint32_t)(seed >> 32));
+    const uint64_t v = ((uint64_t)(w.v[0] >> 6) << 26) | (uint64_t)(w.v[1] >> 6);
+    return (double)(2 * v + 1) * (1.0 / 9007199254740992.0);
+}
+
+// smallest i with cdf[i] > target, clamped to m - 1; at most ceil(log2 m) probes whatever cdf holds
+__host__ __device__ __forceinline__ int bpf_search(const double* cdf, int m, double target) {
+    int lo = 0, hi = m - 1;
+    while (lo < hi) {
+        const int mid = lo + ((hi - lo) >> 1);
+        if (cdf[mid] > target) hi = mid; else lo = mid + 1;
+    }
+    return lo;
+}
+
+__host__ __device__ __forceinline__ int bpf_ancestor(const double* cdf, int m, uint64_t seed, int64_t j, int64_t obs) {
+    return bpf_search(cdf, m, bpf_uniform(seed, j, obs) * cdf[m - 1]);
+}
+
+__host__ __device__ __forceinline__ int clamp_slot(int a, int m) { return a < 0 ? 0 : (a >= m ? m - 1 : a); }
+
+// the trajectory of final particle j: walk the ancestors back from the last observation
+__host__ __device__ __forceinline__ void bpf_traceback_one(const float* S, int64_t s_st, int64_t s_sp, const int32_t* anc, int m,
+                                                           int n_obs, int step, int d, int j, float* out) {
+    float* o = out + (int64_t)j * ((int64_t)n_obs * step + 1) * d;
+    int i = j;
+    for (int k = n_obs - 1; k >= 0; --k) {
+        i = clamp_slot(anc[(int64_t)k * m + i], m);
+        for (int t = k * step + 1; t <= (k + 1) * step; ++t)
+            for (int c = 0; c < d; ++c) o[(int64_t)t * d + c] = S[t * s_st + i * s_sp + c];
+    }
+    for (int c = 0; c < d; ++c) o[c] = S[i * s_sp + c];
+}
+
+// log p(x_next | x) of a small-state chain (NoisyLorenz63.log_prob, sda/mcs.py:184-185)
+template <int KIND>
+__host__ __device__ __forceinline__ double chain_pair_log_prob(const sda_chain_model& m, const float* x, const float* x_next) {
+    constexpr int D = KIND == SDA_CHAIN_LORENZ63 ? 3 : 2;
+    float mu[D];
+#pragma unroll
+    for (int c = 0; c < D; ++c) mu[c] = x[c];
+    chain_small_transition<KIND>(m, mu);
+    double l = 0.0;
+#pragma unroll
+    for (int c = 0; c < D; ++c) l += normal_log_prob((double)x_next[c], (double)mu[c], (double)m.noise_std);
+    return l;
+}
+
+static int chain_model_check(const sda_chain_model* m) {
+    if (!m || m->steps < 1 || !(m->noise_std >= 0.f)) return SDA_E_BADARG;
+    if (m->kind == SDA_CHAIN_LORENZ63) return m->d == 3 ? SDA_OK : SDA_E_BADARG;
+    if (m->kind == SDA_CHAIN_LOTKA_VOLTERRA) return m->d == 2 ? SDA_OK : SDA_E_BADARG;
+    if (m->kind == SDA_CHAIN_LORENZ96) return m->d >= 4 && m->d <= 64 ? SDA_OK : SDA_E_UNSUPPORTED;
+    return SDA_E_UNSUPPORTED;
+}
+
+static int chain_obs_check(const sda_chain_obs* o, int d) {
+    if (!o || !o->y || o->k < 1 || o->k > d || o->k > SDA_CHAIN_MAXOBS || !(o->sigma > 0.f)) return SDA_E_BADARG;
+    for (int k = 0; k < o->k; ++k)
+        if (o->idx[k] < 0 || o->idx[k] >= d || o->scale[k] == 0.f) return SDA_E_BADARG;
+    return SDA_OK;
+}
+
+static int chain_adv_check(const sda_chain_adv* a) {
+    if (!a) return SDA_E_BADARG;
+    int rc = chain_model_check(&a->model);
+    if (rc != SDA_OK) return rc;
+    if (!a->x_in || !a->out || a->m < 1 || a->transitions < 1 || a->row0 < 0 || a->draw0 < 0) return SDA_E_BADARG;
+    if (a->in_sp < a->model.d || a->out_sp < a->model.d) return SDA_E_BADARG;
+    if (a->obs) {
+        if (a->model.kind == SDA_CHAIN_LORENZ96) return SDA_E_UNSUPPORTED;
+        if (!a->logw || !a->pmax) return SDA_E_BADARG;
+        return chain_obs_check(a->obs, a->model.d);
+    }
+    return SDA_OK;
+}
+
+extern "C" int sda_bpf_logweights_blocks(int m) { return m < 1 ? SDA_E_BADARG : (m + CH_THREADS - 1) / CH_THREADS; }
+
+#ifndef SDA_HOST_EMU
+// ---------------------------------------------------------------- device kernels
+struct ChainAdvArgs {       // sda_chain_adv without the host pointer
+    sda_chain_model model;
+    const float* x_in; int64_t in_sp; const int32_t* anc;
+    float* out; int64_t out_st, out_sp; int32_t every, m, transitions;
+    uint64_t seed; int64_t row0, draw0;
+    int32_t has_obs; float* logw; float* pmax;
+};
+
+// max over the workgroup's CH_THREADS values -> pmax[blockIdx.x] (every thread of the workgroup calls it)
+__device__ __forceinline__ void block_max_store(float v, float* pmax) {
+    __shared__ float s_max[CH_THREADS / SDA_WAVE];
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v = fmaxf(v, __shfl_down(v, off, SDA_WAVE));
+    if ((threadIdx.x & 63) == 0) s_max[threadIdx.x >> 6] = v;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        float r = s_max[0];
+#pragma unroll
+        for (int w = 1; w < CH_THREADS / SDA_WAVE; ++w) r = fmaxf(r, s_max[w]);
+        pmax[blockIdx.x] = r;
+    }
+}
+
+template <int KIND>
+__global__ __launch_bounds__(CH_THREADS) void chain_advance_small_kernel(ChainAdvArgs a, sda_chain_obs obs) {
+    constexpr int D = KIND == SDA_CHAIN_LORENZ63 ? 3 : 2;
+    const int j = blockIdx.x * CH_THREADS + threadIdx.x;
+    const bool live = j < a.m;
+    float x[D];
+#pragma unroll
+    for (int c = 0; c < D; ++c) x[c] = 0.f;
+    if (live) {
+        const int src = a.anc ? clamp_slot(a.anc[j], a.m) : j;
+#pragma unroll
+        for (int c = 0; c < D; ++c) x[c] = a.x_in[src * a.in_sp + c];
+        for (int t = 0; t < a.transitions; ++t) {
+            chain_small_transition<KIND>(a.model, x);
+            if (a.model.noise_std > 0.f) {
+                float z[4];
+                chain_noise4(a.seed, (uint64_t)(a.row0 + j), a.draw0 + t, 0, z);
+#pragma unroll
+                for (int c = 0; c < D; ++c) x[c] = x[c] + a.model.noise_std * z[c];
+            }
+            if (a.every) {
+#pragma unroll
+                for (int c = 0; c < D; ++c) a.out[t * a.out_st + j * a.out_sp + c] = x[c];
+            }
+        }
+        if (!a.every) {
+#pragma unroll
+            for (int c = 0; c < D; ++c) a.out[j * a.out_sp + c] = x[c];
+        }
+    }
+    if (a.has_obs) {        // wave-uniform: the whole workgroup takes it
+        float l = -INFINITY;
+        if (live) {
+            l = obs_logweight(obs, obs.y, x);
+            a.logw[j] = l;
+        }
+        block_max_store(l, a.pmax);
+    }
+}
+
+// Lorenz-96: component c of a particle on lane (group base + c) of a sub-group of W lanes, W = next power of two >= n
+__global__ __launch_bounds__(CH_THREADS) void chain_advance_l96_kernel(ChainAdvArgs a, int W) {
+    const int n = a.model.d;
+    const int lane = threadIdx.x & 63, sub = lane & (W - 1), base = lane - sub;
+    const int per_block = CH_THREADS / W;
+    const int64_t j = (int64_t)blockIdx.x * per_block + threadIdx.x / W;
+    const bool live = j < a.m && sub < n;
+    const int c = sub < n ? sub : 0;
+    // roll(x, 1)[c] = x[c - 1], roll(x, -1)[c] = x[c + 1], roll(x, -2)[c] = x[c + 2], indices modulo n
+    const int lm1 = base + (c + n - 1) % n, lp1 = base + (c + 1) % n, lp2 = base + (c + 2) % n;
+    const float h = a.model.h, F = a.model.p[0];
+    float x = 0.f;
+    if (live) {
+        const int64_t src = a.anc ? clamp_slot(a.anc[j], a.m) : j;
+        x = a.x_in[src * a.in_sp + c];
+    }
+    // every lane of the wave runs the shuffles (dead lanes carry zeros); only the stores are predicated
+    for (int t = 0; t < a.transitions; ++t) {
+        for (int s = 0; s < a.model.steps; ++s) {
+            const float k1 = lorenz96_f(__shfl(x, lm1, SDA_WAVE), __shfl(x, lp2, SDA_WAVE), __shfl(x, lp1, SDA_WAVE), x, F);
+            float v = rk4_half(x, h, k1);
+            const float k2 = lorenz96_f(__shfl(v, lm1, SDA_WAVE), __shfl(v, lp2, SDA_WAVE), __shfl(v, lp1, SDA_WAVE), v, F);
+            v = rk4_half(x, h, k2);
+            const float k3 = lorenz96_f(__shfl(v, lm1, SDA_WAVE), __shfl(v, lp2, SDA_WAVE), __shfl(v, lp1, SDA_WAVE), v, F);
+            v = rk4_full(x, h, k3);
+            const float k4 = lorenz96_f(__shfl(v, lm1, SDA_WAVE), __shfl(v, lp2, SDA_WAVE), __shfl(v, lp1, SDA_WAVE), v, F);
+            x = rk4_comb(x, h, k1, k2, k3, k4);
+        }
+        if (a.model.noise_std > 0.f && live) {
+            float z[4];
+            chain_noise4(a.seed, (uint64_t)(a.row0 + j), a.draw0 + t, c >> 2, z);
+            x = x + a.model.noise_std * z[c & 3];
+        }
+        if (a.every && live) a.out[t * a.out_st + j * a.out_sp + c] = x;
+    }
+    if (!a.every && live) a.out[j * a.out_sp + c] = x;
+}
+
+extern "C" int sda_chain_advance(const sda_chain_adv* a, void* stream) {
+    int rc = chain_adv_check(a);
+    if (rc != SDA_OK) return rc;
+    ChainAdvArgs k;
+    k.model = a->model;
+    k.x_in = a->x_in; k.in_sp = a->in_sp; k.anc = a->anc;
+    k.out = a->out; k.out_st = a->every ? a->out_st : 0; k.out_sp = a->out_sp;
+    k.every = a->every ? 1 : 0; k.m = a->m; k.transitions = a->transitions;
+    k.seed = a->seed; k.row0 = a->row0; k.draw0 = a->draw0;
+    k.has_obs = a->obs ? 1 : 0; k.logw = a->logw; k.pmax = a->pmax;
+    sda_chain_obs obs = {};
+    if (a->obs) obs = *a->obs;
+    const hipStream_t st = (hipStream_t)stream;
+    if (a->model.kind == SDA_CHAIN_LORENZ96) {
+        int W = 4;
+        while (W < a->model.d) W <<= 1;
+        const int per_block = CH_THREADS / W;
+        const int64_t blocks = ((int64_t)a->m + per_block - 1) / per_block;
+        if (blocks > 0x7fffffff) return SDA_E_UNSUPPORTED;
+        hipLaunchKernelGGL(chain_advance_l96_kernel, dim3((unsigned)blocks), dim3(CH_THREADS), 0, st, k, W);
+    } else {
+        const unsigned blocks = (unsigned)((a->m + CH_THREADS - 1) / CH_THREADS);
+        if (a->model.kind == SDA_CHAIN_LORENZ63)
+            hipLaunchKernelGGL(chain_advance_small_kernel<SDA_CHAIN_LORENZ63>, dim3(blocks), dim3(CH_THREADS), 0, st, k, obs);
+        else
+            hipLaunchKernelGGL(chain_advance_small_kernel<SDA_CHAIN_LOTKA_VOLTERRA>, dim3(blocks), dim3(CH_THREADS), 0, st, k, obs);
+    }
+    return sda_launch_status();
+}
+
+// one wave per trajectory: lanes stride over the L - 1 pairs, float64 partial sums, one shuffle tree
+template <int KIND>
+__global__ __launch_bounds__(CH_THREADS) void chain_log_prob_kernel(sda_chain_model model, const float* __restrict__ x, int b, int len,
+                                                                    int64_t sb, int64_t sl, double* __restrict__ out) {
+    constexpr int D = KIND == SDA_CHAIN_LORENZ63 ? 3 : 2;
+    const int lane = threadIdx.x & 63;
+    const int traj = blockIdx.x * (CH_THREADS / SDA_WAVE) + (threadIdx.x >> 6);
+    double acc = 0.0;
+    if (traj < b) {
+        const float* xt = x + traj * sb;
+        for (int i = lane; i + 1 < len; i += SDA_WAVE) {
+            float a[D], n[D];
+#pragma unroll
+            for (int c = 0; c < D; ++c) { a[c] = xt[i * sl + c]; n[c] = xt[(i + 1) * sl + c]; }
+            acc += chain_pair_log_prob<KIND>(model, a, n);
+        }
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off, SDA_WAVE);
+    if (lane == 0 && traj < b) out[traj] = acc;
+}
+
+extern "C" int sda_chain_log_prob(const sda_chain_model* model, const float* x, int b, int len, int64_t sb, int64_t sl, double* out,
+                                  void* stream) {
+    int rc = chain_model_check(model);
+    if (rc != SDA_OK) return rc;
+    if (model->kind == SDA_CHAIN_LORENZ96) return SDA_E_UNSUPPORTED;
+    if (!x || !out || b < 1 || len < 2 || sl < model->d || !(model->noise_std > 0.f)) return SDA_E_BADARG;
+    const unsigned blocks = (unsigned)((b + CH_THREADS / SDA_WAVE - 1) / (CH_THREADS / SDA_WAVE));
+    if (model->kind == SDA_CHAIN_LORENZ63)
+        hipLaunchKernelGGL(chain_log_prob_kernel<SDA_CHAIN_LORENZ63>, dim3(blocks), dim3(CH_THREADS), 0, (hipStream_t)stream, *model, x,
+                           b, len, sb, sl, out);
+    else
+        hipLaunchKernelGGL(chain_log_prob_kernel<SDA_CHAIN_LOTKA_VOLTERRA>, dim3(blocks), dim3(CH_THREADS), 0, (hipStream_t)stream,
+                           *model, x, b, len, sb, sl, out);
+    return sda_launch_status();
+}
+
+__global__ __launch_bounds__(CH_THREADS) void bpf_logweights_kernel(const float* __restrict__ x, int m, int64_t sp, sda_chain_obs obs,
+                                                                    float* __restrict__ logw, float* __restrict__ pmax) {
+    const int j = blockIdx.x * CH_THREADS + threadIdx.x;
+    float l = -INFINITY;
+    if (j < m) {
+        l = obs_logweight(obs, obs.y, x + j * sp);
+        logw[j] = l;
+    }
+    block_max_store(l, pmax);
+}
+
+extern "C" int sda_bpf_logweights(const float* x, int m, int64_t sp, int d, const sda_chain_obs* obs, float* logw, float* pmax,
+                                  void* stream) {
+    if (!x || !logw || !pmax || m < 1 || d < 1 || sp < d) return SDA_E_BADARG;
+    int rc = chain_obs_check(obs, d);
+    if (rc != SDA_OK) return rc;
+    hipLaunchKernelGGL(bpf_logweights_kernel, dim3((unsigned)((m + CH_THREADS - 1) / CH_THREADS)), dim3(CH_THREADS), 0,
+                       (hipStream_t)stream, x, m, sp, *obs, logw, pmax);
+    return sda_launch_status();
+}
+
+// ONE workgroup: max (+ NaN / all -inf check), then the vector in chunks of CDF_THREADS with a float64 carry.  The chunk loop
+// has a trip count every thread computes from m alone, so the barriers inside it are uniform.
+#define CDF_THREADS 1024
+__global__ __launch_bounds__(CDF_THREADS) void bpf_cdf_kernel(const float* __restrict__ logw, int m, const float* __restrict__ pmax,
+                                                              int npmax, float* __restrict__ w, double* __restrict__ cdf,
+                                                              int32_t* __restrict__ status) {
+    __shared__ float s_max[CDF_THREADS / SDA_WAVE];
+    __shared__ int s_bad[CDF_THREADS / SDA_WAVE];
+    __shared__ double s_sum[CDF_THREADS / SDA_WAVE];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    float mx = -INFINITY;
+    int bad = 0;
+    for (int i = tid; i < m; i += CDF_THREADS) {
+        const float l = logw[i];
+        bad |= (l != l);
+        if (!pmax) mx = fmaxf(mx, l);
+    }
+    if (pmax)
+        for (int i = tid; i < npmax; i += CDF_THREADS) mx = fmaxf(mx, pmax[i]);
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        mx = fmaxf(mx, __shfl_down(mx, off, SDA_WAVE));
+        bad |= __shfl_down(bad, off, SDA_WAVE);
+    }
+    if (lane == 0) { s_max[wave] = mx; s_bad[wave] = bad; }
+    __syncthreads();
+    mx = s_max[0]; bad = s_bad[0];
+#pragma unroll
+    for (int k = 1; k < CDF_THREADS / SDA_WAVE; ++k) { mx = fmaxf(mx, s_max[k]); bad |= s_bad[k]; }
+    const bool degenerate = bad || !(mx > -INFINITY) || !(mx < INFINITY);      // the same value in every thread
+    if (tid == 0) status[0] = degenerate ? 1 : 0;
+    if (degenerate) {
+        for (int i = tid; i < m; i += CDF_THREADS) { w[i] = 1.0f; cdf[i] = (double)(i + 1); }
+        return;
+    }
+    double carry = 0.0;
+    const int chunks = (m + CDF_THREADS - 1) / CDF_THREADS;
+    for (int ch = 0; ch < chunks; ++ch) {
+        const int i = ch * CDF_THREADS + tid;
+        float wi = 0.f;
+        if (i < m) { wi = expf(logw[i] - mx); w[i] = wi; }
+        double v = (double)wi;
+#pragma unroll
+        for (int off = 1; off < SDA_WAVE; off <<= 1) {      // inclusive scan inside the wave
+            const double u = __shfl_up(v, off, SDA_WAVE);
+            if (lane >= off) v += u;
+        }
+        if (lane == 63) s_sum[wave] = v;
+        __syncthreads();
+        double before = carry, total = 0.0;
+#pragma unroll
+        for (int k = 0; k < CDF_THREADS / SDA_WAVE; ++k) {
+            const double s = s_sum[k];
+            if (k < wave) before += s;
+            total += s;
+        }
+        if (i < m) cdf[i] = before + v;
+        carry += total;
+        __syncthreads();        // s_sum is rewritten by the next chunk
+    }
+}
+
+extern "C" int sda_bpf_cdf(const float* logw, int m, const float* pmax, int npmax, float* w, double* cdf, int32_t* status,
+                           void* stream) {
+    if (!logw || !w || !cdf || !status || m < 1 || (pmax && npmax < 1)) return SDA_E_BADARG;
+    hipLaunchKernelGGL(bpf_cdf_kernel, dim3(1), dim3(CDF_THREADS), 0, (hipStream_t)stream, logw, m, pmax, npmax, w, cdf, status);
+    return sda_launch_status();
+}
+
+__global__ __launch_bounds__(CH_THREADS) void bpf_resample_kernel(const double* __restrict__ cdf, int m, uint64_t seed, int64_t obs,
+                                                                  int32_t* __restrict__ anc) {
+    const int j = blockIdx.x * CH_THREADS + threadIdx.x;
+    if (j < m) anc[j] = bpf_ancestor(cdf, m, seed, j, obs);
+}
+
+extern "C" int sda_bpf_resample(const double* cdf, int m, uint64_t seed, int64_t obs_index, int32_t* anc, void* stream) {
+    if (!cdf || !anc || m < 1 || obs_index < 0) return SDA_E_BADARG;
+    hipLaunchKernelGGL(bpf_resample_kernel, dim3((unsigned)((m + CH_THREADS - 1) / CH_THREADS)), dim3(CH_THREADS), 0,
+                       (hipStream_t)stream, cdf, m, seed, obs_index, anc);
+    return sda_launch_status();
+}
+
+__global__ __launch_bounds__(CH_THREADS) void bpf_traceback_kernel(const float* __restrict__ S, int64_t s_st, int64_t s_sp,
+                                                                   const int32_t* __restrict__ anc, int m, int n_obs, int step, int d,
+                                                                   float* __restrict__ out) {
+    const int j = blockIdx.x * CH_THREADS + threadIdx.x;
+    if (j < m) bpf_traceback_one(S, s_st, s_sp, anc, m, n_obs, step, d, j, out);
+}
+
+extern "C" int sda_bpf_traceback(const float* S, int64_t s_st, int64_t s_sp, const int32_t* anc, int m, int n_obs, int step, int d,
+                                 float* out, void* stream) {
+    if (!S || !anc || !out || m < 1 || n_obs < 1 || step < 1 || d < 1 || s_sp < d || s_st < 0) return SDA_E_BADARG;
+    if ((int64_t)n_obs * step + 1 > 0x7fffffff) return SDA_E_UNSUPPORTED;
+    hipLaunchKernelGGL(bpf_traceback_kernel, dim3((unsigned)((m + CH_THREADS - 1) / CH_THREADS)), dim3(CH_THREADS), 0,
+                       (hipStream_t)stream, S, s_st, s_sp, anc, m, n_obs, step, d, out);
+    return sda_launch_status();
+}
+
+#else  // SDA_HOST_EMU
+// ---------------------------------------------------------------- CPU replay (tests only; libsda_emu.so): the same
+// __host__ __device__ functions as plain loops over HOST arrays.  Lorenz-96 keeps a particle in one array where the device
+// keeps it on the lanes of a sub-group: the rolls index modulo n where the device shuffles.
+static void l96_f_host(const float* x, int n, float F, float* f) {
+    for (int c = 0; c < n; ++c) f[c] = lorenz96_f(x[(c + n - 1) % n], x[(c + 2) % n], x[(c + 1) % n], x[c], F);
+}
+
+static void l96_transition_host(const sda_chain_model& m, float* x) {
+    const int n = m.d;
+    float k1[64], k2[64], k3[64], k4[64], v[64];
+    for (int s = 0; s < m.steps; ++s) {
+        l96_f_host(x, n, m.p[0], k1);
+        for (int c = 0; c < n; ++c) v[c] = rk4_half(x[c], m.h, k1[c]);
+        l96_f_host(v, n, m.p[0], k2);
+        for (int c = 0; c < n; ++c) v[c] = rk4_half(x[c], m.h, k2[c]);
+        l96_f_host(v, n, m.p[0], k3);
+        for (int c = 0; c < n; ++c) v[c] = rk4_full(x[c], m.h, k3[c]);
+        l96_f_host(v, n, m.p[0], k4);
+        for (int c = 0; c < n; ++c) x[c] = rk4_comb(x[c], m.h, k1[c], k2[c], k3[c], k4[c]);
+    }
+}
+
+extern "C" int sda_chain_advance_host(const sda_chain_adv* a) {
+    int rc = chain_adv_check(a);
+    if (rc != SDA_OK) return rc;
+    const sda_chain_model& md = a->model;
+    const int d = md.d;
+    for (int j = 0; j < a->m; ++j) {
+        const int src = a->anc ? clamp_slot(a->anc[j], a->m) : j;
+        float x[64];
+        for (int c = 0; c < d; ++c) x[c] = a->x_in[src * a->in_sp + c];
+        for (int t = 0; t < a->transitions; ++t) {
+            if (md.kind == SDA_CHAIN_LORENZ63) chain_small_transition<SDA_CHAIN_LORENZ63>(md, x);
+            else if (md.kind == SDA_CHAIN_LOTKA_VOLTERRA) chain_small_transition<SDA_CHAIN_LOTKA_VOLTERRA>(md, x);
+            else l96_transition_host(md, x);
+            if (md.noise_std > 0.f)
+                for (int q = 0; 4 * q < d; ++q) {
+                    float z[4];
+                    chain_noise4(a->seed, (uint64_t)(a->row0 + j), a->draw0 + t, q, z);
+                    for (int e = 0; e < 4 && 4 * q + e < d; ++e) x[4 * q + e] = x[4 * q + e] + md.noise_std * z[e];
+                }
+            if (a->every)
+                for (int c = 0; c < d; ++c) a->out[t * a->out_st + j * a->out_sp + c] = x[c];
+        }
+        if (!a->every)
+            for (int c = 0; c < d; ++c) a->out[j * a->out_sp + c] = x[c];
+        if (a->obs) a->logw[j] = obs_logweight(*a->obs, a->obs->y, x);
+    }
+    return SDA_OK;
+}
+
+extern "C" int sda_chain_log_prob_host(const sda_chain_model* model, const float* x, int b, int len, int64_t sb, int64_t sl,
+                                       double* out) {
+    int rc = chain_model_check(model);
+    if (rc != SDA_OK) return rc;
+    if (model->kind == SDA_CHAIN_LORENZ96) return SDA_E_UNSUPPORTED;
+    if (!x || !out || b < 1 || len < 2 || sl < model->d || !(model->noise_std > 0.f)) return SDA_E_BADARG;
+    for (int t = 0; t < b; ++t) {
+        double acc = 0.0;
+        for (int i = 0; i + 1 < len; ++i) {
+            const float* a = x + t * sb + i * sl;
+            acc += model->kind == SDA_CHAIN_LORENZ63 ? chain_pair_log_prob<SDA_CHAIN_LORENZ63>(*model, a, a + sl)
+                                                     : chain_pair_log_prob<SDA_CHAIN_LOTKA_VOLTERRA>(*model, a, a + sl);
+        }
+        out[t] = acc;
+    }
+    return SDA_OK;
+}
+
+extern "C" int sda_bpf_logweights_host(const float* x, int m, int64_t sp, int d, const sda_chain_obs* obs, float* logw) {
+    if (!x || !logw || m < 1 || d < 1 || sp < d) return SDA_E_BADARG;
+    int rc = chain_obs_check(obs, d);
+    if (rc != SDA_OK) return rc;
+    for (int j = 0; j < m; ++j) logw[j] = obs_logweight(*obs, obs->y, x + j * sp);
+    return SDA_OK;
+}
+
+extern "C" int sda_bpf_resample_host(const double* cdf, int m, uint64_t seed, int64_t obs_index, int32_t* anc) {
+    if (!cdf || !anc || m < 1 || obs_index < 0) return SDA_E_BADARG;
+    for (int j = 0; j < m; ++j) anc[j] = bpf_ancestor(cdf, m, seed, j, obs_index);
+    return SDA_OK;
+}
+
+extern "C" int sda_bpf_traceback_host(const float* S, int64_t s_st, int64_t s_sp, const int32_t* anc, int m, int n_obs, int step,
+                                      int d, float* out) {
+    if (!S || !anc || !out || m < 1 || n_obs < 1 || step < 1 || d < 1 || s_sp < d || s_st < 0) return SDA_E_BADARG;
+    for (int j = 0; j < m; ++j) bpf_traceback_one(S, s_st, s_sp, anc, m, n_obs, step, d, j, out);
+    return SDA_OK;
+}
+#endif  // SDA_HOST_EMU

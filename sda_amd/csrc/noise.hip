@@ -7,36 +7,7 @@
 // one 16-byte store per lane and Philox call; no reads.
 #include "sda_common.hpp"
 
-#define PHILOX_M0 0xD2511F53u
-#define PHILOX_M1 0xCD9E8D57u
-#define PHILOX_W0 0x9E3779B9u
-#define PHILOX_W1 0xBB67AE85u
-
-struct philox4 { uint32_t v[4]; };
-
-__host__ __device__ __forceinline__ philox4 philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0,
-                                                          uint32_t k1) {
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const uint64_t p0 = (uint64_t)PHILOX_M0 * c0, p1 = (uint64_t)PHILOX_M1 * c2;
-        const uint32_t hi0 = (uint32_t)(p0 >> 32), lo0 = (uint32_t)p0, hi1 = (uint32_t)(p1 >> 32), lo1 = (uint32_t)p1;
-        const uint32_t n0 = hi1 ^ c1 ^ k0, n2 = hi0 ^ c3 ^ k1;
-        c0 = n0; c1 = lo1; c2 = n2; c3 = lo0;
-        k0 += PHILOX_W0; k1 += PHILOX_W1;
-    }
-    philox4 o; o.v[0] = c0; o.v[1] = c1; o.v[2] = c2; o.v[3] = c3;
-    return o;
-}
-
-// two uniforms in (0, 1) from the top 24 bits of each word (never 0 or 1) -> two independent N(0, 1)
-__device__ __forceinline__ void box_muller(uint32_t a, uint32_t b, float& z0, float& z1) {
-    const float u1 = ((float)(a >> 8) + 0.5f) * (1.0f / 16777216.0f);
-    const float u2 = ((float)(b >> 8) + 0.5f) * (1.0f / 16777216.0f);
-    const float r = sqrtf(-2.0f * logf(u1));
-    float s, c;
-    sincosf(6.28318530717958647692f * u2, &s, &c);
-    z0 = r * c; z1 = r * s;
-}
+#include "philox.hpp"      // philox4x32_10, box_muller (shared with chain.hip)
 
 // out: [rows][per_row]; quad q of a row (elements 4q .. 4q+3) comes from counter {q_lo, row, draw_lo, draw_hi ^ q_hi << 16}
 __global__ __launch_bounds__(256) void randn_rows_kernel(float* __restrict__ out, int rows, int64_t per_row, uint32_t k0,

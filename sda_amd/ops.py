@@ -993,3 +993,147 @@ def clock_probe(device, ms: float = 2.0, blocks: int = 1024) -> dict:
     ghz = (v[:, 0] / v[:, 1].clamp_min(1)) * 0.1
     return {'ghz': float(ghz.median()), 'ghz_min': float(ghz.min()), 'ghz_max': float(ghz.max()), 'blocks': blocks,
             'mfma_per_wave': iters * 8, 'instruction': 'v_mfma_f32_16x16x4_f32, register operands'}
+
+
+# ---------------------------------------------------------------- Markov chains and the particle filter (csrc/chain.hip)
+def chain_model(kind: str, d: int, dt: float, steps: int, params, noise_std: float = 0.0) -> '_lib.ChainModel':
+    """`sda_chain_model`: h = dt / steps rounded to fp32 ONCE, as torch rounds the reference's python scalar."""
+    m = _lib.ChainModel()
+    m.kind, m.d, m.steps = _lib.CHAIN_KINDS[kind], int(d), int(steps)
+    m.h = dt / steps
+    for i, v in enumerate(params):
+        m.p[i] = float(v)
+    m.noise_std = float(noise_std)
+    return m
+
+
+def chain_obs(index, shift, scale, sigma: float, y: Tensor) -> '_lib.ChainObs':
+    """`sda_chain_obs` for A(x) = (x[index] - shift) / scale observed as y (k,) with noise sigma."""
+    _dev(y)
+    o = _lib.ChainObs()
+    o.k = len(index)
+    if o.k > _lib.CHAIN_MAXOBS or y.numel() != o.k or not y.is_contiguous():
+        raise _lib.SdaHipError(f'chain_obs: {o.k} observed components, y has {y.numel()} values')
+    for i in range(o.k):
+        o.idx[i], o.shift[i], o.scale[i] = int(index[i]), float(shift[i]), float(scale[i])
+    o.sigma = float(sigma)
+    o.y = y.data_ptr()
+    o._keep = y
+    return o
+
+
+def _i32(t: Optional[Tensor], n: int, what: str):
+    if t is None:
+        return None
+    if not t.is_cuda or t.dtype != torch.int32 or not t.is_contiguous() or t.numel() != n:
+        raise _lib.SdaHipError(f'{what}: expected {n} contiguous int32 values on the device')
+    return t.data_ptr()
+
+
+def chain_advance(model, x: Tensor, out: Tensor, transitions: int, *, every: bool = False, out_st: int = 0, out_sp: Optional[int] = None,
+                  anc: Optional[Tensor] = None, seed: int = 0, row0: int = 0, draw0: int = 0, obs=None,
+                  logw: Optional[Tensor] = None, pmax: Optional[Tensor] = None) -> Tensor:
+    """`transitions` transitions of x (m, d) in one launch.  `out` is a preallocated fp32 device tensor the caller addresses by
+    strides (in floats): the last state at out[j * out_sp], or with every=True the state after transition t at
+    out[t * out_st + j * out_sp].  The caller guarantees that those addresses lie inside `out`."""
+    _dev(x, out, logw, pmax)
+    m, d = x.shape
+    if x.dim() != 2 or x.stride(1) != 1 or d != model.d:
+        raise _lib.SdaHipError(f'chain_advance: states {tuple(x.shape)} (strides {x.stride()}) for a {model.d}-component chain')
+    out_sp = d if out_sp is None else out_sp
+    last = (transitions - 1) * out_st if every else 0
+    if out_sp < d or (every and out_st < 0) or last + (m - 1) * out_sp + d > out.numel() or not out.is_contiguous():
+        raise _lib.SdaHipError('chain_advance: the output strides leave the output tensor')
+    a = _lib.ChainAdv()
+    a.model = model
+    a.x_in, a.in_sp, a.anc = x.data_ptr(), x.stride(0) if m > 1 else d, _i32(anc, m, 'chain_advance: anc')
+    a.out, a.out_st, a.out_sp, a.every = out.data_ptr(), out_st, out_sp, int(every)
+    a.m, a.transitions = m, transitions
+    a.seed, a.row0, a.draw0 = seed & 0xffffffffffffffff, row0, draw0
+    if obs is not None:
+        nb = _lib.load().sda_bpf_logweights_blocks(m)
+        if logw is None or pmax is None or logw.numel() < m or pmax.numel() < nb:
+            raise _lib.SdaHipError('chain_advance: fused weights need logw (m,) and pmax (blocks,)')
+        a.obs, a.logw, a.pmax = ctypes.pointer(obs), logw.data_ptr(), pmax.data_ptr()
+    _lib.check(_lib.load().sda_chain_advance(ctypes.byref(a), _stream()), 'sda_chain_advance')
+    return out
+
+
+def chain_log_prob(model, x: Tensor) -> Tensor:
+    """x (b, L, d) -> (b,) float64: sum_i log p(x_{i+1} | x_i) of the noisy chain."""
+    _dev(x)
+    if x.dim() != 3 or x.shape[2] != model.d or x.shape[1] < 2:
+        raise _lib.SdaHipError(f'chain_log_prob: trajectories {tuple(x.shape)} for a {model.d}-component chain')
+    if x.stride(2) != 1:
+        x = x.contiguous()
+    out = torch.empty(x.shape[0], device=x.device, dtype=torch.float64)
+    _lib.check(_lib.load().sda_chain_log_prob(ctypes.byref(model), x.data_ptr(), x.shape[0], x.shape[1], x.stride(0), x.stride(1),
+                                              out.data_ptr(), _stream()), 'sda_chain_log_prob')
+    return out
+
+
+def bpf_logweights(x: Tensor, obs):
+    """x (m, d) -> (logw (m,), pmax (blocks,)): affine-select Gaussian log-weights and the per-workgroup maxima."""
+    _dev(x)
+    if x.dim() != 2 or x.stride(1) != 1:
+        raise _lib.SdaHipError(f'bpf_logweights: states {tuple(x.shape)} (strides {x.stride()})')
+    m, d = x.shape
+    lib = _lib.load()
+    logw = torch.empty(m, device=x.device, dtype=torch.float32)
+    pmax = torch.empty(lib.sda_bpf_logweights_blocks(m), device=x.device, dtype=torch.float32)
+    _lib.check(lib.sda_bpf_logweights(x.data_ptr(), m, x.stride(0) if m > 1 else d, d, ctypes.byref(obs), logw.data_ptr(),
+                                      pmax.data_ptr(), _stream()), 'sda_bpf_logweights')
+    return logw, pmax
+
+
+def bpf_cdf(logw: Tensor, pmax: Optional[Tensor] = None, *, w: Optional[Tensor] = None, cdf: Optional[Tensor] = None,
+            status: Optional[Tensor] = None, check: bool = True):
+    """logw (m,) -> (w (m,) fp32 = exp(logw - max), cdf (m,) float64 inclusive prefix sums, status (1,) int32).  check=True reads
+    the status (one synchronisation) and raises when no particle carries weight; a filter passes check=False and reads all its
+    status words once at the end (`bpf_check`)."""
+    _dev(logw, pmax)
+    m = logw.numel()
+    if not logw.is_contiguous() or (pmax is not None and not pmax.is_contiguous()):
+        raise _lib.SdaHipError('bpf_cdf: contiguous vectors expected')
+    w = torch.empty(m, device=logw.device, dtype=torch.float32) if w is None else w
+    cdf = torch.empty(m, device=logw.device, dtype=torch.float64) if cdf is None else cdf
+    status = torch.empty(1, device=logw.device, dtype=torch.int32) if status is None else status
+    if w.numel() != m or cdf.numel() != m or cdf.dtype != torch.float64 or status.dtype != torch.int32 or status.numel() < 1:
+        raise _lib.SdaHipError('bpf_cdf: w (m,) fp32, cdf (m,) float64 and status (1,) int32 expected')
+    _lib.check(_lib.load().sda_bpf_cdf(logw.data_ptr(), m, _ptr(pmax), 0 if pmax is None else pmax.numel(), w.data_ptr(),
+                                       cdf.data_ptr(), status.data_ptr(), _stream()), 'sda_bpf_cdf')
+    if check:
+        bpf_check(status)
+    return w, cdf, status
+
+
+def bpf_check(status: Tensor) -> None:
+    """Raise if any observation left no particle with weight (every log-weight -inf, or a NaN): where the reference's
+    torch.multinomial raises."""
+    bad = status.nonzero().flatten().tolist()
+    if bad:
+        raise _lib.SdaHipError(f'particle filter: no particle carries weight at observation(s) {bad} (every log-weight is -inf, or '
+                               f'one is NaN)')
+
+
+def bpf_resample(cdf: Tensor, seed: int, obs_index: int, anc: Optional[Tensor] = None) -> Tensor:
+    """cdf (m,) float64 -> (m,) int32 i.i.d. categorical ancestors (draw j of observation obs_index: csrc/philox.hpp)."""
+    if not cdf.is_cuda or cdf.dtype != torch.float64 or not cdf.is_contiguous():
+        raise _lib.SdaHipError('bpf_resample: a contiguous float64 device vector expected (there is no CPU fallback)')
+    m = cdf.numel()
+    anc = torch.empty(m, device=cdf.device, dtype=torch.int32) if anc is None else anc
+    _lib.check(_lib.load().sda_bpf_resample(cdf.data_ptr(), m, seed & 0xffffffffffffffff, obs_index, _i32(anc, m, 'bpf_resample: anc'),
+                                            _stream()), 'sda_bpf_resample')
+    return anc
+
+
+def bpf_traceback(S: Tensor, anc: Tensor, step: int) -> Tensor:
+    """S (T + 1, m, d) un-resampled states, anc (N, m) int32, T = N step -> (m, T + 1, d) resampled trajectories."""
+    _dev(S)
+    if S.dim() != 3 or not S.is_contiguous() or anc.dim() != 2 or S.shape[0] != anc.shape[0] * step + 1 or anc.shape[1] != S.shape[1]:
+        raise _lib.SdaHipError(f'bpf_traceback: states {tuple(S.shape)}, ancestors {tuple(anc.shape)}, step {step}')
+    t1, m, d = S.shape
+    out = torch.empty(m, t1, d, device=S.device, dtype=torch.float32)
+    _lib.check(_lib.load().sda_bpf_traceback(S.data_ptr(), m * d, d, _i32(anc, anc.numel(), 'bpf_traceback: anc'), m, anc.shape[0], step, d,
+                                             out.data_ptr(), _stream()), 'sda_bpf_traceback')
+    return out
