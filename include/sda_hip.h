@@ -432,6 +432,50 @@ int sda_mlp_fwd(const sda_mlp_desc* d, void* stream);
 int sda_mlp_bwd(const sda_mlp_desc* d, void* stream);
 int sda_mlp_slab_floats(int in_f, int out_f);         /* host, no launch */
 
+/* Parameter gradients of the same chain (csrc/mlp_train.hip; opt-in training, sda_amd.training.parameter_gradients(mlp=True)).
+ *
+ * sda_mlp_bwd_train: sda_mlp_bwd on `mlp` (same transposed slabs, same saves, same input gradient bit for bit) that also stores the
+ *   cotangent at every GEMM's OUTPUT as rows g_save[g][row][g_ld] (GEMM stride g_stride floats):
+ *     kind 0: the cotangent of the Linear's output;  kind 2: the cotangent of the block's output;
+ *     kind 1: gz = (g . W2) * act'(z), the cotangent of the pre-activation.
+ *   Rows are written as whole 16-feature fragments: columns [out_f[g], padded width) of a row receive zeros, columns beyond the padded
+ *   width (16 for out_f <= 16, else 128, else 256) are not touched.  g_ld >= the widest padded out_f, a multiple of 4; g_save 16-byte
+ *   aligned, g_stride a multiple of 4.
+ *
+ * sda_mlp_wgrad: ONE launch for every GEMM of the chain, then one slab reduction:
+ *     dw[g][o][i] (+)= sum_r G[r][o] U[r][i],   db[g][o] (+)= sum_r G[r][o]        (dw = torch's unpadded [out_f][in_f], db [out_f])
+ *   on the fp32 matrix cores, G = g[g] (rows of g_save, row stride g_ld) and U rebuilt by the loader from what the forward saved:
+ *     kind 0: src[g][r][i]                                   (the Linear's own input rows: the net input or a segment's output)
+ *     kind 1: (src[g][r][i] - mean[g][r]) * rstd[g][r]       (src = the block's rows of a_save, mean / rstd its statistics)
+ *     kind 2: act(src[g][r][i])                              (src = the block's rows of z_save)
+ *   (row stride src_ld[g]).  The bias is one more column of the same multiply (U = 1).  The row axis is cut into `slabs` contiguous
+ *   ranges (0 = the planner's choice, a function of the shapes only; 1 .. 64 = forced, clipped to the number of 32-row stages);
+ *   unreduced partials go to work[sda_mlp_wgrad_work_floats(d)]; the second kernel sums them in slab order: no atomics, bitwise
+ *   reproducible.  accumulate: add onto dw / db instead of overwriting.  db[g] may be NULL.  Nothing outside [out_f][in_f] / [out_f]
+ *   is written.  SDA_E_UNSUPPORTED: rows < 1, ngemm outside 1 .. SDA_MLP_MAXG, a width outside 1 .. 256, a kind outside 0 .. 2;
+ *   SDA_E_BADARG: null pointers, slabs outside 0 .. 64, row strides shorter than the width. */
+typedef struct sda_mlp_train_desc {
+    sda_mlp_desc mlp;
+    float* g_save; int64_t g_stride; int32_t g_ld;
+} sda_mlp_train_desc;
+typedef struct sda_mlp_wgrad_desc {
+    int32_t rows, ngemm;
+    int32_t act;
+    int32_t kind[SDA_MLP_MAXG];
+    int32_t in_f[SDA_MLP_MAXG], out_f[SDA_MLP_MAXG];
+    const float* src[SDA_MLP_MAXG]; int64_t src_ld[SDA_MLP_MAXG];
+    const float* mean[SDA_MLP_MAXG]; const float* rstd[SDA_MLP_MAXG];
+    const float* g[SDA_MLP_MAXG]; int64_t g_ld;
+    float* dw[SDA_MLP_MAXG]; float* db[SDA_MLP_MAXG];
+    float* work;
+    int32_t slabs, accumulate;
+} sda_mlp_wgrad_desc;
+int sda_mlp_bwd_train(const sda_mlp_train_desc* d, void* stream);
+int sda_mlp_wgrad(const sda_mlp_wgrad_desc* d, void* stream);
+/* planning only (nothing is launched, `work` may be NULL): the slab count the launch will use / the floats of `work` it needs; <0 error */
+int sda_mlp_wgrad_slabs(const sda_mlp_wgrad_desc* d);
+int64_t sda_mlp_wgrad_work_floats(const sda_mlp_wgrad_desc* d);
+
 /* The same two launches as the halves of a Gaussian-guided evaluation of a LOCAL score network -- MCScoreNet over a ScoreNet kernel
  * (sda/score.py:134-164, 53-63; experiments/lorenz/utils.py:45-59) inside GaussianScore (score.py:375-396) --, the rows being the
  * nw = len - 2k windows of each of rows / nw trajectories x (B, len, c), (2k + 1) c <= 16:

@@ -133,6 +133,27 @@ class MlpDesc(Structure):
     ]
 
 
+class MlpTrainDesc(Structure):
+    """Mirror of `struct sda_mlp_train_desc` (include/sda_hip.h)."""
+    _fields_ = [('mlp', MlpDesc), ('g_save', c_fp), ('g_stride', c_int64), ('g_ld', c_int32)]
+
+
+class MlpWgradDesc(Structure):
+    """Mirror of `struct sda_mlp_wgrad_desc` (include/sda_hip.h)."""
+    _fields_ = [
+        ('rows', c_int32), ('ngemm', c_int32),
+        ('act', c_int32),
+        ('kind', c_int32 * MLP_MAXG),
+        ('in_f', c_int32 * MLP_MAXG), ('out_f', c_int32 * MLP_MAXG),
+        ('src', c_fp * MLP_MAXG), ('src_ld', c_int64 * MLP_MAXG),
+        ('mean', c_fp * MLP_MAXG), ('rstd', c_fp * MLP_MAXG),
+        ('g', c_fp * MLP_MAXG), ('g_ld', c_int64),
+        ('dw', c_fp * MLP_MAXG), ('db', c_fp * MLP_MAXG),
+        ('work', c_fp),
+        ('slabs', c_int32), ('accumulate', c_int32),
+    ]
+
+
 class MlpWin(Structure):
     """Mirror of `struct sda_mlp_win` (include/sda_hip.h)."""
     _fields_ = [
@@ -244,6 +265,10 @@ SIGNATURES = {
     'sda_mlp_fwd': (c_int, [POINTER(MlpDesc), c_void_p]),
     'sda_mlp_bwd': (c_int, [POINTER(MlpDesc), c_void_p]),
     'sda_mlp_slab_floats': (c_int, [c_int, c_int]),
+    'sda_mlp_bwd_train': (c_int, [POINTER(MlpTrainDesc), c_void_p]),
+    'sda_mlp_wgrad': (c_int, [POINTER(MlpWgradDesc), c_void_p]),
+    'sda_mlp_wgrad_slabs': (c_int, [POINTER(MlpWgradDesc)]),
+    'sda_mlp_wgrad_work_floats': (c_int64, [POINTER(MlpWgradDesc)]),
     'sda_mlp_fwd_win': (c_int, [POINTER(MlpDesc), POINTER(MlpWin), c_void_p]),
     'sda_mlp_bwd_win': (c_int, [POINTER(MlpDesc), POINTER(MlpWin), c_void_p]),
     'sda_mc_finish': (c_int, [c_fp, c_fp, c_fp, c_int, c_int, c_int, c_int, c_float, c_float, c_fp, c_int, c_fp, c_fp, c_fp, c_fp, c_void_p]),

@@ -15,7 +15,7 @@ import torch
 import torch.nn as nn
 from torch import Tensor
 
-from . import _lib, ops
+from . import _lib, ops, training
 
 
 def _rows(x: Tensor):
@@ -95,6 +95,12 @@ class _FusedPlan:
         self.nres = sum(1 for k, *_ in self.gemms if k == 2)
         # row length of the saved streams (block inputs, pre-activations): the widest residual block, padded as the kernel pads it
         self.save_ld = max([16 * _mf(i) for k, i, _o, _ in self.gemms if k == 1] + [128])
+        # training (_TrainMLPFunction): the forward runs as SEGMENTS [g0, g1) that end in front of every Linear but the first, so that a
+        # segment's output is the next Linear's input -- the one weight-gradient operand the forward kernels do not save
+        cuts = [0] + [g for g, (k, *_r) in enumerate(self.gemms) if k == 0 and g > 0] + [len(self.gemms)]
+        self.segments = list(zip(cuts[:-1], cuts[1:]))
+        # row length of the cotangent streams: the widest GEMM output as the kernels pad it (wide nets: 16 / 128 / 256; narrow: 16 / 128)
+        self.g_ld = max(16 * _mf(o) for _k, _i, o, _ in self.gemms) if self.gemms else 16
         self._key = None
 
     def _pack(self):
@@ -117,12 +123,14 @@ class _FusedPlan:
             bn += b.numel()
         self.wf, self.wb, self.bias, self.w_off, self.b_off, self._key = torch.cat(fw), torch.cat(bw), torch.cat(bs), w_off, b_off, key
 
-    def desc(self, rows: int, backward: bool):
+    def desc(self, rows: int, backward: bool, d=None, g0: int = 0, g1: Optional[int] = None):
+        """The descriptor of GEMMs [g0, g1) (default: the whole chain), filled into ``d`` when given."""
         self._pack()
-        d = _lib.MlpDesc()
-        d.rows, d.ngemm, d.act, d.unbiased, d.eps = rows, len(self.gemms), self.act, int(self.unbiased), self.eps
-        for g, (k, i, o, _lin) in enumerate(self.gemms):
-            d.kind[g], d.in_f[g], d.out_f[g], d.w_off[g], d.b_off[g] = k, i, o, self.w_off[g], self.b_off[g]
+        d = _lib.MlpDesc() if d is None else d
+        g1 = len(self.gemms) if g1 is None else g1
+        d.rows, d.ngemm, d.act, d.unbiased, d.eps = rows, g1 - g0, self.act, int(self.unbiased), self.eps
+        for g, (k, i, o, _lin) in enumerate(self.gemms[g0:g1]):
+            d.kind[g], d.in_f[g], d.out_f[g], d.w_off[g], d.b_off[g] = k, i, o, self.w_off[g0 + g], self.b_off[g0 + g]
         d.w = (self.wb if backward else self.wf).data_ptr()
         d.bias = self.bias.data_ptr()
         return d
@@ -179,6 +187,91 @@ class _FusedMLPFunction(torch.autograd.Function):
         return gx, None
 
 
+class _TrainMLPFunction(torch.autograd.Function):
+    """The whole layer chain with parameter gradients (sda_amd.training with mlp = True; csrc/mlp_train.hip).  The Linear weights and
+    biases are inputs of the function (in GEMM order: w0, b0, w1, b1, ...), so ``.grad`` accumulation, hooks and ``zero_grad`` behave as
+    torch's do.  Forward: sda_mlp_fwd with saves, one launch per segment (see _FusedPlan.segments).  Backward: three launches whatever the
+    depth -- sda_mlp_bwd_train over the whole chain (the input gradient + the cotangent at every GEMM's output), sda_mlp_wgrad for all
+    GEMMs and its slab reduction."""
+
+    @staticmethod
+    def forward(ctx, x: Tensor, plan: _FusedPlan, *params):
+        rows, dev = x.shape[0], x.device
+        nres, ld = max(plan.nres, 1), plan.save_ld
+        # ONE save allocation, indexed across all segments: [a | z][block][row][save_ld] and [mean | rstd][block][row]
+        sv = torch.empty(2, nres, rows, ld, device=dev, dtype=torch.float32)
+        stats = torch.empty(2, nres, rows, device=dev, dtype=torch.float32)
+        inputs, h, rb = [], x, 0
+        for g0, g1 in plan.segments:
+            d = plan.desc(rows, False, g0=g0, g1=g1)
+            out = torch.empty(rows, plan.gemms[g1 - 1][2], device=dev, dtype=torch.float32)
+            d.x, d.x_ld, d.out, d.out_ld = h.data_ptr(), h.stride(0), out.data_ptr(), out.stride(0)
+            nb = sum(1 for k, *_r in plan.gemms[g0:g1] if k == 2)
+            if nb:
+                d.a_save, d.z_save, d.save_stride, d.save_ld = sv[0, rb].data_ptr(), sv[1, rb].data_ptr(), rows * ld, ld
+                d.mean_save, d.rstd_save, d.stat_stride = stats[0, rb].data_ptr(), stats[1, rb].data_ptr(), rows
+            ops.mlp_launch(d, False)
+            inputs.append(h)
+            h, rb = out, rb + nb
+        # (x, the segment outputs and the saves: torch checks their versions before the backward reads them)
+        ctx.save_for_backward(sv, stats, *inputs)
+        ctx.plan, ctx.rows = plan, rows
+        return h
+
+    @staticmethod
+    def backward(ctx, g: Tensor):
+        plan, rows = ctx.plan, ctx.rows
+        sv, stats, *inputs = ctx.saved_tensors
+        dev, ld, ng = g.device, plan.save_ld, len(plan.gemms)
+        g = g.contiguous()
+        t = _lib.MlpTrainDesc()
+        d = plan.desc(rows, True, d=t.mlp)
+        gx = torch.empty(rows, plan.gemms[0][1], device=dev, dtype=torch.float32)
+        g_save = torch.empty(ng, rows, plan.g_ld, device=dev, dtype=torch.float32)
+        d.x, d.x_ld, d.out, d.out_ld = g.data_ptr(), g.stride(0), gx.data_ptr(), gx.stride(0)
+        d.a_save, d.z_save, d.save_stride, d.save_ld = sv[0].data_ptr(), sv[1].data_ptr(), rows * ld, ld
+        d.mean_save, d.rstd_save, d.stat_stride = stats[0].data_ptr(), stats[1].data_ptr(), rows
+        t.g_save, t.g_stride, t.g_ld = g_save.data_ptr(), rows * plan.g_ld, plan.g_ld
+        ops.mlp_bwd_train(t)
+        # the weight gradient's GEMM list: those whose weight or bias asks for a gradient (its GEMMs are independent of one another);
+        # every dw / db is a view of ONE allocation
+        need = ctx.needs_input_grad
+        want = [j for j in range(ng) if need[2 + 2 * j] or need[3 + 2 * j]]
+        grads = [None] * (2 * ng)
+        if want:
+            pad4 = lambda n: (n + 3) & ~3
+            flat = torch.empty(sum(pad4(plan.gemms[j][1] * plan.gemms[j][2]) + pad4(plan.gemms[j][2]) for j in want), device=dev, dtype=torch.float32)
+            seg_of = {g0: n for n, (g0, _g1) in enumerate(plan.segments)}       # a Linear opens a segment (or is GEMM 0): its input is that segment's
+            rb_of, nb = [], 0                                                   # residual block of GEMM j
+            for k, *_r in plan.gemms:
+                rb_of.append(nb)
+                nb += k == 2
+            w = _lib.MlpWgradDesc()
+            w.rows, w.ngemm, w.act, w.g_ld, w.slabs, w.accumulate = rows, len(want), plan.act, plan.g_ld, 0, 0
+            off = 0
+            for n, j in enumerate(want):
+                k, i, o, _lin = plan.gemms[j]
+                w.kind[n], w.in_f[n], w.out_f[n] = k, i, o
+                if k == 0:
+                    src = inputs[seg_of[j]]
+                    w.src[n], w.src_ld[n] = src.data_ptr(), src.stride(0)
+                else:
+                    w.src[n], w.src_ld[n] = sv[0 if k == 1 else 1, rb_of[j]].data_ptr(), ld
+                    if k == 1:
+                        w.mean[n], w.rstd[n] = stats[0, rb_of[j]].data_ptr(), stats[1, rb_of[j]].data_ptr()
+                w.g[n] = g_save[j].data_ptr()
+                dw = flat[off:off + o * i].view(o, i)
+                off += pad4(o * i)
+                db = flat[off:off + o]
+                off += pad4(o)
+                w.dw[n], w.db[n] = dw.data_ptr(), db.data_ptr()
+                grads[2 * j], grads[2 * j + 1] = dw, db
+            work = torch.empty(ops.mlp_wgrad_work_floats(w), device=dev, dtype=torch.float32)
+            w.work = work.data_ptr()
+            ops.mlp_wgrad(w)
+        return (gx if need[0] else None, None) + tuple(gr if need[2 + n] else None for n, gr in enumerate(grads))
+
+
 class _MLPFunction(torch.autograd.Function):
     """A chain of ``nn.Linear`` and residual blocks on (rows, features); VJP w.r.t. the input only."""
 
@@ -227,10 +320,24 @@ class _MLPFunction(torch.autograd.Function):
         return g, None
 
 
-def _run(layers, x: Tensor) -> Tensor:
+def _run(layers, x: Tensor, owner: Optional[nn.Module] = None) -> Tensor:
+    layers = list(layers)
+    if owner is not None and training.mlp_active(owner):
+        # parameter gradients (opt-in): the whole-MLP plan or an error -- no other route forms them
+        training.check_mlp(owner)
+        if not x.is_cuda or x.dtype != torch.float32:
+            raise NotImplementedError(f'parameter gradients of a ResMLP are formed on the device in fp32 only (got a {x.device.type} '
+                                      f'{x.dtype} tensor); supported: {training.served()}')
+        xr = _rows(x)
+        plan = _fused_plan(layers)
+        if xr.shape[0] == 0 or xr.shape[1] != plan.gemms[0][1]:
+            raise NotImplementedError(f'parameter gradients of a ResMLP: input of shape {tuple(x.shape)} does not fit the network; '
+                                      f'supported: {training.served()}')
+        params = [p for *_r, lin in plan.gemms for p in (lin.weight, lin.bias)]
+        out = _TrainMLPFunction.apply(xr, plan, *params)
+        return out.reshape(*x.shape[:-1], out.shape[-1])
     ops._dev(x)
     xr = _rows(x)
-    layers = list(layers)
     plan = _fused_plan(layers)
     if plan is not None and xr.is_cuda and xr.shape[0] > 0 and xr.stride(1) == 1 and xr.shape[1] == plan.gemms[0][1]:
         out = _FusedMLPFunction.apply(xr, plan)
@@ -258,4 +365,4 @@ def resmlp_forward(mlp, x: Tensor) -> Tensor:
     layers = list(mlp)
     if not all(isinstance(l, nn.Linear) or _is_res_block(l) for l in layers):
         raise NotImplementedError('ResMLP with custom layers has no gfx950 path')
-    return _run(layers, x)
+    return _run(layers, x, owner=mlp)

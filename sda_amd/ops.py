@@ -764,6 +764,43 @@ def mlp_launch_win(d: '_lib.MlpDesc', w: '_lib.MlpWin', backward: bool):
     prof.records.append((e0, e1, flops, 'mlp_bwd' if backward else 'mlp_fwd'))
 
 
+def mlp_bwd_train(d: '_lib.MlpTrainDesc'):
+    """The input VJP of a whole ResMLP that also stores the cotangent at every GEMM's output (sda_mlp_bwd_train, csrc/mlp_train.hip)."""
+    lib = _lib.load()
+    prof = conv_profile
+    if prof is None:
+        _lib.check(lib.sda_mlp_bwd_train(ctypes.byref(d), _stream()), 'sda_mlp_bwd_train')
+        return
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    _lib.check(lib.sda_mlp_bwd_train(ctypes.byref(d), _stream()), 'sda_mlp_bwd_train')
+    e1.record()
+    m = d.mlp
+    prof.records.append((e0, e1, 2.0 * m.rows * sum(m.in_f[g] * m.out_f[g] for g in range(m.ngemm)), 'mlp_bwd'))
+
+
+def mlp_wgrad_work_floats(d: '_lib.MlpWgradDesc') -> int:
+    """Floats of the ``work`` buffer sda_mlp_wgrad needs for this descriptor (``d.work`` is not read)."""
+    floats = _lib.load().sda_mlp_wgrad_work_floats(ctypes.byref(d))
+    _lib.check(int(min(floats, 0)), 'sda_mlp_wgrad_work_floats')
+    return int(floats)
+
+
+def mlp_wgrad(d: '_lib.MlpWgradDesc') -> None:
+    """dw[g] / db[g] (+)= the weight and bias gradients of every GEMM of a ResMLP: one launch + one slab reduction (sda_mlp_wgrad,
+    csrc/mlp_train.hip).  ``d.work`` holds mlp_wgrad_work_floats(d) floats."""
+    lib = _lib.load()
+    prof = conv_profile
+    if prof is None:
+        _lib.check(lib.sda_mlp_wgrad(ctypes.byref(d), _stream()), 'sda_mlp_wgrad')
+        return
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    _lib.check(lib.sda_mlp_wgrad(ctypes.byref(d), _stream()), 'sda_mlp_wgrad')
+    e1.record()
+    prof.records.append((e0, e1, 2.0 * d.rows * sum((d.in_f[g] + 1) * d.out_f[g] for g in range(d.ngemm)), 'wgrad'))
+
+
 def mc_finish(eps: Tensor, ghat: Tensor, gwin: Tensor, b: int, nw: int, k: int, c: int, cx0: float, cx1: float, coef_ptr: int, mode: int,
               out: Optional[Tensor], xs: Optional[Tensor], step_coef_ptr: int, partial: Optional[Tensor]):
     _dev(eps, ghat, gwin, out, xs, partial)

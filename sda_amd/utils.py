@@ -82,7 +82,7 @@ def loop(sde: 'VPSDE', trainset, validset, epochs: int = 256, batch_size: int = 
     As the reference's loop: shuffled DataLoaders whose items are ``(x, kwargs)`` pairs (``kwargs`` go on to ``sde.loss``),
     AdamW over ``sde.parameters()``, the learning rate scaled per epoch by the ``linear`` / ``cosine`` / ``exponential`` factor,
     the mean training loss, the mean validation loss (under ``no_grad``) and the learning rate the epoch ran with.  Parameter
-    gradients are switched on (``sda_amd.training.parameter_gradients()``) while the training steps run."""
+    gradients are switched on (``sda_amd.training.parameter_gradients(mlp=True)``: the U-Nets and ScoreNet) while the training steps run."""
     from torch.utils.data import DataLoader
     loaders = [DataLoader(ds, batch_size=batch_size, shuffle=True) for ds in (trainset, validset)]
     if optimizer != 'AdamW':
@@ -94,7 +94,7 @@ def loop(sde: 'VPSDE', trainset, validset, epochs: int = 256, batch_size: int = 
     for _ in range(epochs):
         losses_train, losses_valid = [], []
         sde.train()
-        with training.parameter_gradients():
+        with training.parameter_gradients(mlp=True):
             for batch in loaders[0]:
                 x, kwargs = _to(batch, device=device)
                 loss = sde.loss(x, **kwargs)
