@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define SDA_ABI_VERSION 13
+#define SDA_ABI_VERSION 14
 
 enum {
     SDA_OK = 0,
@@ -98,10 +98,6 @@ typedef struct sda_conv_desc {
     const float* res;               /* out += res           (NULL = off) */
     /* tiling: cout tile = 32*mt (mt in 1..4); weights must be packed with cout_pad % (32*mt) == 0 */
     int32_t mt;
-    /* optional Winograd F(2x2,3x3) weights [16][cin_pad][cout_pad] (sda_pack_conv_weight_wino); when non-NULL and the
-     * layer is eligible (3x3, stride 1, no zero insertion, no ctx, cout % 96 == 0, even output size, mt == 3) the
-     * transform-domain kernel is used: 2.25x fewer multiplies, fp32 round-off-level error */
-    const float* w_wino;
     /* optional overrides (all zero = the defaults above, so a zero-initialised descriptor keeps its meaning).
      *   explicit_pad != 0: taps read in[o*stride + t - pad_h|pad_w]; default kh/2, kw/2 (odd kernels).  Even kernels
      *   need it.
@@ -111,12 +107,16 @@ typedef struct sda_conv_desc {
      *   interleaved quarter of the gradient, instead of convolving a zero-inserted tensor (4x the multiplies). */
     int32_t explicit_pad, pad_h, pad_w;
     int64_t out_sn, out_sc, out_sy, out_sx;
-    /* optional Winograd weights for the second-generation kernel (sda_pack_conv_weight_wino4: [cin_pad/8][16][cout/16][64][2],
-     * U fragments in MFMA lane order).  Taken when the layer is Winograd-eligible as above, its output height is a multiple
-     * of 8 and its width of 16 (workgroup tile = 96 couts x 16 x 8 pixels of one image), and the loader fusions are one of
-     * none / SiLU / LayerNorm / modulation + LayerNorm; otherwise w_wino / the direct kernel serve the launch.
-     * (ABI v13) cout % 32 == 0 suffices for THIS kernel: its cout tile is 96 where cout % 96 == 0, else 64 where cout % 64 == 0 (the
-     * reference's default widths (64, 128, 256), experiments/kolmogorov/utils.py:52), else 32 (sda/nn.py:99's (32, 64, 128)). */
+    /* optional Winograd F(2x2,3x3) weights (sda_pack_conv_weight_wino4: [cin_pad/8][16][cout/16][64][2], U fragments in MFMA lane
+     * order): 2.25x fewer multiplies than the direct kernel, fp32 round-off-level error.  When non-NULL the Winograd kernel
+     * (csrc/conv_wino4.hip) takes the launch if ALL of this holds, and the direct kernels serve it otherwise:
+     *   3 x 3, stride 1, no zero insertion, default padding and planar output (explicit_pad and out_s* zero);
+     *   cout % 32 == 0 and cout_pad == cout: the cout tile is 96 where cout % 96 == 0 (the reference's training widths), else 64
+     *     where cout % 64 == 0 (its default widths (64, 128, 256), experiments/kolmogorov/utils.py:52), else 32 (sda/nn.py:99);
+     *   output height a multiple of 8 and width of 16 (workgroup tile = 16 x 8 pixels of one image), source up-sampled by 1 or 2;
+     *   loader fusions none / SiLU / LayerNorm / modulation (shared by all images) + LayerNorm; ctx channels only without any.
+     * SDA_CONV_WINO=0 or SDA_CONV_WINO4=0 in the environment switch the kernel off.  (The first-generation kernel and its weight field, ABI <= 13,
+     * are retired: even-sized images that do not tile by 8 x 16 and other activations now run direct.) */
     const float* w_wino4;
     /* optional output pooling (0 / 1 = off): out is [n][cout][ho / pool_h][wo / pool_w] and receives the SUM of each pool_h x pool_w
      * cell of the convolution's ho x wo output -- the input VJP of `Upsample(nearest) -> conv` (the tails, sda/nn.py:161-169) in one
@@ -158,10 +158,10 @@ int sda_conv_igemm(const sda_conv_desc* d, void* stream);
  * SDA_E_UNSUPPORTED outside the kernel's range (cout % 32 -- 96- / 64- / 32-cout tiles as sda_conv_desc.w_wino4 --, ho % 8, wo % 16,
  * loader fusions): run the four class launches. */
 int sda_conv_parity4(const sda_conv_desc* d, void* stream);
-/* which kernel family would serve the launch (pure planning, nothing is launched): 2 = one-wave-per-SIMD Winograd
- * (w_wino4), 1 = Winograd (w_wino), 3 = the single-round-trip small 1-D kernel, 4 = the 3 x 3 kernel for <= 16 output
- * channels, 5 = the w_wino4 kernel in its zero-position form (2 x 2 up-sampled source or pooled output: 54 of the 96 multiplies
- * per stage), 0 = direct implicit GEMM; <0 error */
+/* which kernel family would serve the launch (pure planning, nothing is launched): 0 = direct implicit GEMM, 2 = the Winograd
+ * kernel (w_wino4), 5 = the same in its zero-position form (2 x 2 up-sampled source or pooled output: 54 of the 96 multiplies
+ * per stage), 3 = the single-round-trip small 1-D kernel, 4 = the 3 x 3 kernel for <= 16 output channels; <0 error.
+ * (1 was the first-generation Winograd kernel: retired, never returned.) */
 int sda_conv_igemm_path(const sda_conv_desc* d);
 /* bytes of dynamic LDS the launch would use (or <0 error), for planning / tests */
 int64_t sda_conv_igemm_lds_bytes(const sda_conv_desc* d);
@@ -325,11 +325,7 @@ int sda_pc_correct_keyed(float* x, const float* eps, int b, int64_t per_sample, 
 int sda_pack_conv_weight(const float* w, int cout, int cin, int kh, int kw, int transpose, int cin_keep,
                          float* dst, int k_pad, int m_pad, void* stream);
 
-/* Winograd-domain weights U[4*xi+nu][k][m] = (G g G^T)[xi][nu] for 3x3 filters; transpose / cin_keep as above. */
-int sda_pack_conv_weight_wino(const float* w, int cout, int cin, int transpose, int cin_keep, float* dst, int k_pad,
-                              int m_pad, void* stream);
-
-/* U for the second-generation Winograd kernel: dst[k_pad/8][16][m_pad/16][64][2], k_pad % 8 == 0, m_pad % 32 == 0 (ABI v13; % 96 before:
+/* Winograd-domain weights (G g G^T)[xi][nu] of 3 x 3 filters for sda_conv_desc.w_wino4 (transpose / cin_keep as above): dst[k_pad/8][16][m_pad/16][64][2], k_pad % 8 == 0, m_pad % 32 == 0 (ABI v13; % 96 before:
  * the layout is per 16-cout fragment and does not depend on the cout tile the kernel then picks from m_pad). */
 int sda_pack_conv_weight_wino4(const float* w, int cout, int cin, int transpose, int cin_keep, float* dst, int k_pad,
                                int m_pad, void* stream);

@@ -48,7 +48,6 @@ class ConvDesc(Structure):
         ('act_d', c_int32),
         ('res', c_fp),
         ('mt', c_int32),
-        ('w_wino', c_fp),
         ('explicit_pad', c_int32), ('pad_h', c_int32), ('pad_w', c_int32),
         ('out_sn', c_int64), ('out_sc', c_int64), ('out_sy', c_int64), ('out_sx', c_int64),
         ('w_wino4', c_fp),
@@ -249,7 +248,6 @@ SIGNATURES = {
     'sda_plane_sum': (c_int, [c_fp, c_fp, c_int, c_int, c_int64, c_fp, c_int64, c_int, c_int, c_void_p]),
     'sda_conv_igemm_lds_bytes': (c_int64, [POINTER(ConvDesc)]),
     'sda_pack_conv_weight': (c_int, [c_fp, c_int, c_int, c_int, c_int, c_int, c_int, c_fp, c_int, c_int, c_void_p]),
-    'sda_pack_conv_weight_wino': (c_int, [c_fp, c_int, c_int, c_int, c_int, c_fp, c_int, c_int, c_void_p]),
     'sda_pack_conv_weight_wino4': (c_int, [c_fp, c_int, c_int, c_int, c_int, c_fp, c_int, c_int, c_void_p]),
     'sda_pack_conv_weight_wino4_zp': (c_int, [c_fp, c_int, c_int, c_fp, c_void_p]),
     'sda_wino4_zp_floats': (c_int64, [c_int, c_int]),

@@ -793,10 +793,8 @@ static int conv_launch_m(const sda_conv_desc* d, const ConvGeom& g, hipStream_t 
     return conv_launch_t<MT, SDA_CONV_MAXPOS>(d, g, stream);
 }
 
-// Winograd F(2x2,3x3) path (conv_wino.hip)
-struct WinoGeom;
-int sda_wino_try(const sda_conv_desc* d, hipStream_t stream);   // SDA_E_UNSUPPORTED -> use the direct kernel
-int sda_wino4_try(const sda_conv_desc* d, hipStream_t stream);  // one-wave-per-SIMD Winograd (conv_wino4.hip)
+// each *_try returns SDA_E_UNSUPPORTED when its kernel does not take the launch: the next one, last the direct kernel, serves it
+int sda_wino4_try(const sda_conv_desc* d, hipStream_t stream);  // Winograd F(2x2,3x3), one wave per SIMD (conv_wino4.hip)
 int sda_small1d_try(const sda_conv_desc* d, hipStream_t stream); // small 1-D layers: one round trip per launch (conv_small1d.hip)
 int sda_few_try(const sda_conv_desc* d, hipStream_t stream);     // 3 x 3, <= 16 output channels (conv_few.hip)
 
@@ -808,10 +806,6 @@ extern "C" int sda_conv_igemm(const sda_conv_desc* d, void* stream) {
     }
     // (pooled output exists in the w_wino4 kernel only: the caller runs the plain launch + a pooling reader instead)
     if (d && (d->pool_h > 1 || d->pool_w > 1)) return SDA_E_UNSUPPORTED;
-    if (d && d->w_wino) {
-        const int rcw = sda_wino_try(d, s);
-        if (rcw != SDA_E_UNSUPPORTED) return rcw;
-    }
     if (d && d->kh == 1 && d->kw == 3) {
         const int rcs = sda_small1d_try(d, s);
         if (rcs != SDA_E_UNSUPPORTED) return rcs;
@@ -878,11 +872,11 @@ extern "C" int sda_conv_igemm(const sda_conv_desc* d, void* stream) {
     }
 }
 
-// which kernel family sda_conv_igemm would serve this launch with: 2 one-wave-per-SIMD Winograd, 1 Winograd, 3 the small 1-D
-// kernel (conv_small1d.hip), 4 the few-output-channel 3 x 3 kernel (conv_few.hip), 0 the direct implicit-GEMM kernels
+// which kernel family sda_conv_igemm would serve this launch with: 2 / 5 Winograd (conv_wino4.hip / its conv_h2 form), 3 the small
+// 1-D kernel (conv_small1d.hip), 4 the few-output-channel 3 x 3 kernel (conv_few.hip), 0 the direct implicit-GEMM kernels
+// (1 was the first-generation Winograd kernel: retired, never returned)
 struct Wino4Geom;
 int sda_wino4_path(const sda_conv_desc* d);
-int sda_wino_path(const sda_conv_desc* d);
 int sda_small1d_path(const sda_conv_desc* d);
 int sda_few_path(const sda_conv_desc* d);
 extern "C" int sda_conv_igemm_path(const sda_conv_desc* d) {
@@ -892,7 +886,6 @@ extern "C" int sda_conv_igemm_path(const sda_conv_desc* d) {
         if (p4) return p4 == 2 ? 5 : 2;
     }
     if (d->pool_h > 1 || d->pool_w > 1) return SDA_E_UNSUPPORTED;
-    if (d->w_wino && sda_wino_path(d)) return 1;
     if (d->kh == 1 && d->kw == 3 && sda_small1d_path(d)) return 3;
     if (d->kh == 3 && d->kw == 3 && d->cout <= 16 && sda_few_path(d)) return 4;
     return 0;

@@ -15,8 +15,8 @@ from . import _lib
 from ._lib import ACT_IDS, ConvDesc
 
 CONV_CK = 8          # K-stage depth of conv_igemm (SDA_CONV_CK)
-WINOGRAD = os.environ.get('SDA_CONV_WINO', '1') != '0'      # Winograd F(2x2,3x3) for eligible 3x3 layers
-WINOGRAD4 = os.environ.get('SDA_CONV_WINO4', '1') != '0'    # ... its one-wave-per-SIMD kernel where images are multiples of 16
+WINOGRAD = os.environ.get('SDA_CONV_WINO', '1') != '0'      # 0: no Winograd form at all for the 3x3 layers
+WINOGRAD4 = os.environ.get('SDA_CONV_WINO4', '1') != '0'    # 0: no conv_wino4 kernel (the one Winograd kernel: either switch means "direct kernel")
 #: OPT-IN: 'f16x2' = the block convolutions multiply on the f16 matrix cores with every fp32 operand split into two halves, fp32
 #: accumulation (csrc/conv_h2.hip; same 3e-7 error against float64 as the fp32 Winograd kernel).  Default 'f32': fp32 MFMAs only.
 MULTIPLY = os.environ.get('SDA_MULTIPLY', 'f32')
@@ -88,7 +88,7 @@ def make_conv_desc(*, x_ptr, n, cx, hs, ws, x_sc, x_sy, x_sx, x_sn_outer, x_sn_i
                    w_ptr, cin_pad, cout_pad, cout, kh, kw, out_ptr, ho, wo, mt,
                    stride_h=1, stride_w=1, circular=False, up_h=1, up_w=1, zins_h=1, zins_w=1,
                    ctx_ptr=None, cctx=0, ctx_sn=0, mod_ptr=None, mod_sn=0, ln_mean_ptr=None, ln_rstd_ptr=None,
-                   act_in=0, bias_ptr=None, dact_z_ptr=None, act_d=0, res_ptr=None, w_wino_ptr=None,
+                   act_in=0, bias_ptr=None, dact_z_ptr=None, act_d=0, res_ptr=None,
                    w_wino4_ptr=None, pad=None, out_strides=(0, 0, 0, 0), pool=(1, 1), w_wino4_zp_ptr=None) -> ConvDesc:
     d = ConvDesc()
     d.x = x_ptr
@@ -108,7 +108,6 @@ def make_conv_desc(*, x_ptr, n, cx, hs, ws, x_sc, x_sy, x_sx, x_sn_outer, x_sn_i
     d.dact_z, d.act_d = dact_z_ptr, act_d
     d.res = res_ptr
     d.mt = mt
-    d.w_wino = w_wino_ptr
     d.w_wino4 = w_wino4_ptr
     d.explicit_pad = 0 if pad is None else 1
     d.pad_h, d.pad_w = (0, 0) if pad is None else pad
@@ -138,7 +137,7 @@ class ConvProfile:
         operands), the output written once -- what the PMC traffic of profiles/*_traffic.json is compared against."""
         cin = d.cx + d.cctx
         rd = 4.0 * d.n * d.cx * d.hs * d.ws + 4.0 * d.cctx * d.hs * d.ws * (d.n if d.ctx_sn else 1)
-        rd += 4.0 * cin * d.cout * (16 if (d.w_wino4 or d.w_wino) and conv_path(d) in (1, 2, 5) else d.kh * d.kw)
+        rd += 4.0 * cin * d.cout * (16 if d.w_wino4 and conv_path(d) in (2, 5) else d.kh * d.kw)
         if d.ln_mean:
             rd += 8.0 * d.n * d.hs * d.ws
         out = 4.0 * d.n * d.cout * d.ho * d.wo / (max(1, d.pool_h) * max(1, d.pool_w))
@@ -284,12 +283,13 @@ def conv_pooled(desc: ConvDesc) -> bool:
     return True
 
 
-CONV_FAMILIES = ('direct', 'wino', 'wino4', 'small1d', 'few', 'wino4zp')     # indexed by sda_conv_igemm_path
+# indexed by sda_conv_igemm_path; slot 1 ('wino', the retired first-generation Winograd kernel) only keeps the indices: never returned
+CONV_FAMILIES = ('direct', 'wino', 'wino4', 'small1d', 'few', 'wino4zp')
 
 
 def conv_path(desc: ConvDesc) -> int:
-    """Kernel family that would serve the launch: 2 one-wave-per-SIMD Winograd, 5 its zero-position form (2 x 2 up-sampled source or
-    pooled output), 1 Winograd, 3 small 1-D kernel, 4 few-output-channel kernel, 0 direct implicit GEMM."""
+    """Kernel family that would serve the launch: 2 Winograd (conv_wino4), 5 its zero-position form (2 x 2 up-sampled source or
+    pooled output), 3 small 1-D kernel, 4 few-output-channel kernel, 0 direct implicit GEMM (1: retired, never returned)."""
     return _lib.load().sda_conv_igemm_path(ctypes.byref(desc))
 
 
@@ -385,19 +385,13 @@ class PackedConv:
         self.packed = torch.empty(self.kh * self.kw * self.k_pad * self.m_pad, device=w.device, dtype=torch.float32)
         pack_conv_weight(w, cout, cin, self.kh, self.kw, transpose, keep, self.packed, self.k_pad, self.m_pad)
         self.bias = None if (bias is None or transpose) else bias.detach().contiguous()
-        # Winograd F(2x2,3x3) form for 3x3 layers whose output channels tile by 96 (the U-Net block / tail convolutions)
-        self.wino = None
-        if WINOGRAD and (self.kh, self.kw) == (3, 3) and self.m_real % 96 == 0 and self.mt == 3:
-            self.wino = torch.empty(16 * self.k_pad * self.m_pad, device=w.device, dtype=torch.float32)
-            _lib.check(_lib.load().sda_pack_conv_weight_wino(w.data_ptr(), cout, cin, int(transpose), keep,
-                                                             self.wino.data_ptr(), self.k_pad, self.m_pad, _stream()),
-                       'sda_pack_conv_weight_wino')
-        # ... and the packing of the second-generation Winograd kernel (conv_wino4.hip: U fragments in MFMA lane order).  Its cout tile is
-        # 96 where the width allows (the reference's training widths (96, 192, 384)), 64 for the other multiples of 64 -- the reference's
-        # DEFAULT widths (64, 128, 256), experiments/kolmogorov/utils.py:52 -- and 32 for the remaining multiples of 32 (UNet's own
-        # default (32, 64, 128), sda/nn.py:99) (round 6; the first-generation kernel stays 96-only)
+        # Winograd F(2x2,3x3) form for the 3x3 layers (conv_wino4.hip: U fragments in MFMA lane order).  Its cout tile is 96 where the
+        # width allows (the reference's training widths (96, 192, 384)), 64 for the other multiples of 64 -- the reference's DEFAULT
+        # widths (64, 128, 256), experiments/kolmogorov/utils.py:52 -- and 32 for the remaining multiples of 32 (UNet's own default
+        # (32, 64, 128), sda/nn.py:99)
         self.wino4 = None
-        if WINOGRAD4 and (self.kh, self.kw) == (3, 3) and self.m_pad == self.m_real and (self.wino is not None or (WINO4_BM64 and self.m_real % 32 == 0)):
+        if (WINOGRAD and WINOGRAD4 and (self.kh, self.kw) == (3, 3) and self.m_pad == self.m_real and
+                (self.m_real % 96 == 0 or (WINO4_BM64 and self.m_real % 32 == 0))):
             self.wino4 = torch.empty(16 * self.k_pad * self.m_pad, device=w.device, dtype=torch.float32)
             _lib.check(_lib.load().sda_pack_conv_weight_wino4(w.data_ptr(), cout, cin, int(transpose), keep,
                                                               self.wino4.data_ptr(), self.k_pad, self.m_pad, _stream()),

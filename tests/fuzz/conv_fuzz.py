@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Randomised parity sweep of sda_conv_igemm (direct, Winograd, parity-class and fallback kernels) against torch fp64.
+"""Randomised parity sweep of sda_conv_igemm (direct, Winograd, parity-class and small-shape kernels) against torch fp64.
 
     python tests/fuzz/conv_fuzz.py [--cases 300] [--seed 0]
 
@@ -29,12 +29,13 @@ def ref_conv(x, w, b, stride, circular, kh, kw):
 
 def one_case(rng, dev, idx, large=False):
     """large=True: images of 128 / 256 pixels per side (the configs[3] / [4] U-Net levels), one image, fewer channels."""
-    mode = rng.choice(['plain', 'plain', 'wino', 'wino', 'wino4', 'wino4', 'stride2', 'up', 'zins', 'oned'])
+    mode = rng.choice(['plain', 'plain', 'even96', 'even96', 'wino4', 'wino4', 'stride2', 'up', 'zins', 'oned'])
     if large and mode == 'oned':
         mode = 'wino4'
     circular = rng.random() < 0.6
     cfg = dict(mode=mode, circular=circular)
-    if mode == 'wino':
+    if mode == 'even96':
+        # 96-multiple widths on even-sized images: conv_wino4 where the image tiles by 8 x 16 and the loader is one of its own, else direct
         cin = rng.choice([8, 24, 96, 100, 192])
         cout = rng.choice([96, 192])
         h, w_ = rng.choice([2, 4, 6, 8, 16, 18, 32, 64]), rng.choice([2, 4, 8, 10, 16, 32, 64])
@@ -81,7 +82,7 @@ def one_case(rng, dev, idx, large=False):
     per_image = rng.random() < 0.5
     act = rng.choice([None, None, 'SiLU', 'GELU', 'ELU', 'ReLU', 'SELU'])
     if mode == 'wino4':
-        act = rng.choice([None, 'SiLU', 'SiLU', 'GELU'])          # (GELU: falls back to the first-generation kernel)
+        act = rng.choice([None, 'SiLU', 'SiLU', 'GELU'])          # (GELU: the direct kernel)
         per_image = False                                         # (per-image modulation: direct kernel)
     cfg.update(mod=use_mod, ln=use_ln, per_image=per_image, act=act, bias=bias is not None)
     if use_mod:
@@ -168,11 +169,13 @@ def one_case(rng, dev, idx, large=False):
     except Exception as e:  # noqa: BLE001
         return cfg, f'EXCEPTION {type(e).__name__}: {e}'
     cfg['path'] = ops.conv_path(desc)
-    # the second-generation Winograd kernel serves the four loader configurations of the reference U-Net
+    if cfg['path'] == 1:
+        return cfg, 'path 1 (the retired first-generation Winograd kernel) reported'
+    # the Winograd kernel serves the four loader configurations of the reference U-Net
     w4_cfg = (use_mod, use_ln, act == 'SiLU') in ((False, False, False), (False, False, True), (False, True, False), (True, True, False))
     # (5 = its zero-position form)
     if mode == 'wino4' and act in (None, 'SiLU') and w4_cfg and ops.WINOGRAD4 and ops.WINOGRAD and (cout % 96 == 0 or ops.WINO4_BM64) and cfg['path'] not in (2, 5):
-        return cfg, f'expected the second-generation Winograd kernel, got path {cfg["path"]}'
+        return cfg, f'expected the Winograd kernel, got path {cfg["path"]}'
     torch.cuda.synchronize()
     got = out.cpu().double()
     if torch.isnan(got).any():

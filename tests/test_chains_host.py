@@ -207,7 +207,7 @@ def test_abi_lists_the_chain_entries(tmp_path):
     lib = _lib.load()
     for n in names:
         assert re.search(r'\b%s\s*\(' % n, text) and n in _lib.SIGNATURES and hasattr(lib, n), n
-    assert '#define SDA_ABI_VERSION 13' in header and lib.sda_abi_version() == 13
+    assert '#define SDA_ABI_VERSION 14' in header and lib.sda_abi_version() == 14
     # the ctypes mirrors of the three new structs against what gcc sees
     for mirror, ctype in (('ChainModel', 'sda_chain_model'), ('ChainObs', 'sda_chain_obs'), ('ChainAdv', 'sda_chain_adv')):
         Desc = getattr(_lib, mirror)

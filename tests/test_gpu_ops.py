@@ -339,6 +339,54 @@ def test_conv_randomised_sweep(dev):
     assert not failures, failures[:3]
 
 
+# (cout, cin, n, (ho, wo), variant): the smallest launches the retired first-generation Winograd kernel used to take
+_HANDED_OVER = [(96, cin, 2, hw, var) for hw, var in (((4, 4), ''), ((8, 8), ''), ((6, 10), ''), ((6, 10), 'up'), ((8, 16), 'gelu'))
+                for cin in (8, 96)] + [(192, 96, 1, (4, 4), '')]
+
+
+@pytest.mark.parametrize('res', [False, True])
+@pytest.mark.parametrize('ln', [False, True])
+@pytest.mark.parametrize('case', _HANDED_OVER, ids=lambda c: f'{c[0]}x{c[1]}n{c[2]}_{c[3][0]}x{c[3][1]}{c[4]}')
+def test_conv3x3_wide_untiled_runs_direct(dev, case, ln, res):
+    """The shape class that changed hands when the first-generation Winograd kernel (a 96-cout tile for any even-sized image and
+    any loader activation) was removed: 3 x 3 stride-1 layers whose width is a multiple of 96 but which conv_wino4 does not take --
+    images that do not tile by 8 x 16 ((8, 8): the height tiles, the width does not), also 2 x up-sampled, or a loader activation
+    other than SiLU.  They run on the direct kernel now (path 0, 2.25 x the multiplies, the more exact arithmetic) and no Winograd
+    buffer of the old form is packed.  A fast path for them belongs in conv_wino4's tiling (csrc/conv_wino4.hip: sda_wino4_plan)."""
+    from sda_amd import ops
+    from sda_amd._lib import ACT_IDS
+    from sda_amd.engine import launch_conv, planar_source
+    cout, cin, n, (ho, wo), var = case
+    hs, ws = (ho // 2, wo // 2) if var == 'up' else (ho, wo)
+    torch.manual_seed(17)
+    x, w, b = torch.randn(n, cin, hs, ws) * 1.5 + 0.2, torch.randn(cout, cin, 3, 3) / (3 * cin ** 0.5), torch.randn(cout)
+    opts, xin = {}, x.double()
+    if ln:
+        var_, mean = torch.var_mean(xin, dim=1, unbiased=True, keepdim=True)
+        rstd = 1 / torch.sqrt(var_ + 1e-5)
+        opts['ln'] = tuple(t.float().reshape(n, -1).to(dev).contiguous() for t in (mean, rstd))
+        xin = (xin - mean) * rstd
+    if var == 'gelu':
+        opts['act_in'] = ACT_IDS['GELU']
+        xin = F.gelu(xin)
+    if var == 'up':
+        opts['up'] = (2, 2)
+        xin = xin.repeat_interleave(2, -1).repeat_interleave(2, -2)
+    ref = F.conv2d(F.pad(xin, (1, 1, 1, 1), mode='circular'), w.double(), b.double())
+    if res:
+        r = torch.randn(n, cout, ho, wo)
+        opts['res'] = r.to(dev)
+        ref = ref + r.double()
+    pk = ops.PackedConv(w.to(dev), b.to(dev))
+    assert not hasattr(pk, 'wino')
+    out = torch.full((n, cout, ho, wo), float('nan'), device=dev)
+    desc = launch_conv(pk, planar_source(x.to(dev)), out, ho, wo, circular=True, bias=pk.bias, **opts)
+    assert ops.conv_path(desc) == 0
+    torch.cuda.synchronize()
+    assert not torch.isnan(out).any()
+    assert_close(out.cpu(), ref, TOL)
+
+
 def test_vp_schedule_kernel(dev):
     """mu_sigma(t) for a device scalar == the schedule tables of every SDE flavour (oracle Schedule, pinned to the
     reference's own tables in tests/golden/schedule.npz), and the pair is handed to the kernels without a copy."""

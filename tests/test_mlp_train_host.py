@@ -155,11 +155,11 @@ def test_new_desc_layouts_match_c(tmp_path, mirror, ctype):
         assert Desc.mlp.offset == 0 and Desc.g_save.offset == ctypes.sizeof(_lib.MlpDesc)
 
 
-def test_abi_version_stays_13_and_new_symbols_resolve():
+def test_abi_version_and_new_symbols_resolve():
     from sda_amd import _lib
     sbuild.build()
     lib = _lib.load()
-    assert lib.sda_abi_version() == 13
+    assert lib.sda_abi_version() == 14
     for name in ('sda_mlp_bwd_train', 'sda_mlp_wgrad', 'sda_mlp_wgrad_slabs', 'sda_mlp_wgrad_work_floats'):
         assert hasattr(lib, name)
 

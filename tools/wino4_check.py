@@ -1,12 +1,12 @@
 #!/usr/bin/env python3
-"""Correctness + speed of the one-wave-per-SIMD Winograd kernel (conv_wino4.hip) on the GPU box.
+"""Correctness + speed of the Winograd kernel (conv_wino4.hip) on the GPU box.
 
     python tools/wino4_check.py [--cases 120] [--bench]
 
 1. structured cases (every loader / epilogue fusion, both paddings, upsampling, partial K-stages, several cout tiles,
    batches that leave workgroups with 0 / 1 / many tiles) + a randomised sweep, each against torch float64;
-2. --bench: the K64 layer shapes at 64^2 and 256^2 with both Winograd kernels (SDA_CONV_WINO4 toggled per process is not
-   possible, so the old kernel is timed by passing descriptors without w_wino4)."""
+2. --bench: the K64 layer shapes at 64^2 and 256^2 on conv_wino4 and on the direct kernel (SDA_CONV_WINO4 cannot be toggled inside
+   a process, so the direct kernel is timed by passing descriptors without w_wino4)."""
 import argparse
 import os
 import random
@@ -86,9 +86,8 @@ def run_case(n, cin, cout, h, w_, circular, mod, ln, silu, up, dact, res, bias, 
 
 
 def expect_path(c):
-    """the second-generation kernel serves the four loader configurations of the reference U-Net; the first generation the rest --
-    where it exists: cout % 96 == 0.  Widths that are multiples of 64 only run the 64-cout tile of conv_wino4 (MF = 2) and fall
-    back to the direct kernel (0)."""
+    """conv_wino4 serves the four loader configurations of the reference U-Net -- on its 96-cout tile where cout % 96 == 0, else on
+    the 64- / 32-cout tiles (MF = 2 / 1) --; the direct kernel (0) the rest."""
     key = (bool(c['mod']), bool(c['ln']), bool(c['silu']))
     mf = 3 if c['cout'] % 96 == 0 else (2 if c['cout'] % 64 == 0 else 1)
     nstage = (c['cin'] + 7) // 8
@@ -96,7 +95,7 @@ def expect_path(c):
     # (consumer-side loads), never at 32
     epi_ok = (mf == 3 and nstage >= 12) or mf == 2
     if key not in ((False, False, False), (False, False, True), (False, True, False), (True, True, False)):
-        return 1 if mf == 3 else 0
+        return 0
     # (5 = its zero-position form: 2 x 2 up-sampled source with the LayerNorm loader and ONE epilogue operand through the helpers -- the skip
     #  tensor in the reference tails; an act'(z) operand alone selects it as well)
     if key == (False, True, False) and c['up'] and (bool(c['res']) != bool(c['dact'])) and epi_ok and os.environ.get('SDA_W4_ZP', '1') != '0':
@@ -356,7 +355,7 @@ def trace():
 
 
 def bench():
-    print('--- layer bench (algorithmic TFLOP/s; issued = /2.25)')
+    print('--- layer bench, conv_wino4 (path 2 / 5) | direct kernel (path 0): algorithmic TFLOP/s; conv_wino4 issues 1/2.25 of them')
     for S, n in ((64, 896), (256, 60)):
         layers = [('blk0 96->96 plain', 96, 96, S, {}), ('blk0 96->96 no bias', 96, 96, S, dict(nobias=True)), ('blk0 96->96 mod+LN', 96, 96, S, dict(ln=True, mod=True)),
                   ('blk0 96->96 silu+res', 96, 96, S, dict(silu=True, res=True)), ('blk0^T 96->96 dact', 96, 96, S, dict(dact=True)),
@@ -403,7 +402,7 @@ def bench():
                 pk.wino4 = keep
                 flops = 2.0 * n * h * h * cout * cin * 9
                 res.append((path, ms, flops / ms / 1e9))
-            print(f'S={S:3d} {name:24s} ' + '   '.join(f'path{p}: {ms:7.3f} ms {tf:6.1f} TF (mfma util {tf / 2.25 / 157.3:.2f})' for p, ms, tf in res), flush=True)
+            print(f'S={S:3d} {name:24s} ' + '   '.join(f'path{p}: {ms:7.3f} ms {tf:6.1f} TF (mfma util {tf / (1.0 if p == 0 else 2.25) / 157.3:.2f})' for p, ms, tf in res), flush=True)
 
 
 if __name__ == '__main__':
