@@ -472,6 +472,36 @@ int sda_mlp_wgrad(const sda_mlp_wgrad_desc* d, void* stream);
 int sda_mlp_wgrad_slabs(const sda_mlp_wgrad_desc* d);
 int64_t sda_mlp_wgrad_work_floats(const sda_mlp_wgrad_desc* d);
 
+/* The optimizer step of the same training route (csrc/optim.hip; sda_amd.training.AdamW): a multi-tensor AdamW with decoupled weight
+ * decay over up to SDA_ADAMW_MAXT fp32 tensors in ONE launch, in the operation order of torch's single-tensor AdamW:
+ *     p = p * decay;   m = m + (g - m) * one_m_beta1;   v = v * beta2 + (one_m_beta2 * g) * g;
+ *     p = p - step_size * (m / (sqrt(v) * rsqrt_bc2 + eps))
+ *   with decay = 1 - lr wd, step_size = lr / (1 - beta1^t), rsqrt_bc2 = 1 / sqrt(1 - beta2^t) formed by the caller in double and passed
+ *   as fp32.  p, m, v [numel] are updated in place; g is read.
+ * The pack epilogue keeps a sda_mlp_desc's slabs valid without a re-pack: a tensor with pack_kind 1 is a GEMM weight [out_f][in_f]
+ *   (numel = out_f in_f, both sides 1 .. 256) whose new value p[o][i] also goes to fwd[pos(out_f, in_f, o, i)] and bwd[pos(in_f, out_f, i, o)]
+ *   -- fwd / bwd = the GEMM's forward / transposed slab (w + w_off[g] of the two weight buffers), pos = the slab order described at
+ *   sda_mlp_desc above --; pack_kind 2 is a bias [numel] whose new value also goes to fwd[o] (bias + b_off[g]).  The zero padding of the
+ *   slabs is never written.
+ * Block b of the launch updates chunk b - blk0[t] (1024 elements) of the tensor t with blk0[t] <= b < blk0[t + 1]; sda_adamw_step fills
+ *   blk0 itself (callers leave it alone).  Every output element has one writer and there are no atomics: bitwise reproducible.
+ * SDA_E_BADARG: a null descriptor or p / g / m / v, ntensor outside 1 .. SDA_ADAMW_MAXT, numel < 1, a pack_kind outside 0 .. 2, a weight
+ *   whose numel is not out_f in_f, a null fwd (kinds 1, 2) or bwd (kind 1); SDA_E_UNSUPPORTED: a weight side outside 1 .. 256, more than
+ *   2^31 - 1 blocks.  Nothing is launched then. */
+#define SDA_ADAMW_MAXT 32
+typedef struct sda_adamw_desc {
+    int32_t ntensor;
+    float decay, one_m_beta1, beta2, one_m_beta2, step_size, rsqrt_bc2, eps;
+    float* p[SDA_ADAMW_MAXT]; const float* g[SDA_ADAMW_MAXT];
+    float* m[SDA_ADAMW_MAXT]; float* v[SDA_ADAMW_MAXT];
+    float* fwd[SDA_ADAMW_MAXT]; float* bwd[SDA_ADAMW_MAXT];
+    int64_t numel[SDA_ADAMW_MAXT];
+    int32_t pack_kind[SDA_ADAMW_MAXT];                 /* 0 none, 1 GEMM weight, 2 bias */
+    int32_t out_f[SDA_ADAMW_MAXT], in_f[SDA_ADAMW_MAXT];
+    int32_t blk0[SDA_ADAMW_MAXT + 1];                  /* filled by sda_adamw_step */
+} sda_adamw_desc;
+int sda_adamw_step(const sda_adamw_desc* d, void* stream);
+
 /* The same two launches as the halves of a Gaussian-guided evaluation of a LOCAL score network -- MCScoreNet over a ScoreNet kernel
  * (sda/score.py:134-164, 53-63; experiments/lorenz/utils.py:45-59) inside GaussianScore (score.py:375-396) --, the rows being the
  * nw = len - 2k windows of each of rows / nw trajectories x (B, len, c), (2k + 1) c <= 16:

@@ -153,6 +153,24 @@ class MlpWgradDesc(Structure):
     ]
 
 
+ADAMW_MAXT = 32
+
+
+class AdamWDesc(Structure):
+    """Mirror of `struct sda_adamw_desc` (include/sda_hip.h)."""
+    _fields_ = [
+        ('ntensor', c_int32),
+        ('decay', c_float), ('one_m_beta1', c_float), ('beta2', c_float), ('one_m_beta2', c_float),
+        ('step_size', c_float), ('rsqrt_bc2', c_float), ('eps', c_float),
+        ('p', c_fp * ADAMW_MAXT), ('g', c_fp * ADAMW_MAXT), ('m', c_fp * ADAMW_MAXT), ('v', c_fp * ADAMW_MAXT),
+        ('fwd', c_fp * ADAMW_MAXT), ('bwd', c_fp * ADAMW_MAXT),
+        ('numel', c_int64 * ADAMW_MAXT),
+        ('pack_kind', c_int32 * ADAMW_MAXT),
+        ('out_f', c_int32 * ADAMW_MAXT), ('in_f', c_int32 * ADAMW_MAXT),
+        ('blk0', c_int32 * (ADAMW_MAXT + 1)),
+    ]
+
+
 class MlpWin(Structure):
     """Mirror of `struct sda_mlp_win` (include/sda_hip.h)."""
     _fields_ = [
@@ -267,6 +285,7 @@ SIGNATURES = {
     'sda_mlp_wgrad': (c_int, [POINTER(MlpWgradDesc), c_void_p]),
     'sda_mlp_wgrad_slabs': (c_int, [POINTER(MlpWgradDesc)]),
     'sda_mlp_wgrad_work_floats': (c_int64, [POINTER(MlpWgradDesc)]),
+    'sda_adamw_step': (c_int, [POINTER(AdamWDesc), c_void_p]),
     'sda_mlp_fwd_win': (c_int, [POINTER(MlpDesc), POINTER(MlpWin), c_void_p]),
     'sda_mlp_bwd_win': (c_int, [POINTER(MlpDesc), POINTER(MlpWin), c_void_p]),
     'sda_mc_finish': (c_int, [c_fp, c_fp, c_fp, c_int, c_int, c_int, c_int, c_float, c_float, c_fp, c_int, c_fp, c_fp, c_fp, c_fp, c_void_p]),

@@ -103,8 +103,13 @@ class _FusedPlan:
         self.g_ld = max(16 * _mf(o) for _k, _i, o, _ in self.gemms) if self.gemms else 16
         self._key = None
 
+    def _pack_key(self):
+        """What the packed slabs are valid for: pointer / version of every weight and bias (shared with sda_amd.training.AdamW, whose
+        step writes the slabs itself and then sets ``_key`` to this)."""
+        return tuple((lin.weight.data_ptr(), ops.tensor_version(lin.weight), ops.tensor_version(lin.bias), str(lin.weight.device)) for *_, lin in self.gemms)
+
     def _pack(self):
-        key = tuple((lin.weight.data_ptr(), ops.tensor_version(lin.weight), ops.tensor_version(lin.bias), str(lin.weight.device)) for *_, lin in self.gemms)
+        key = self._pack_key()
         if key == self._key:
             return
         fw, bw, bs, w_off, b_off, wn, bn = [], [], [], [], [], 0, 0

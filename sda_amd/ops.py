@@ -773,6 +773,11 @@ def mlp_bwd_train(d: '_lib.MlpTrainDesc'):
     prof.records.append((e0, e1, 2.0 * m.rows * sum(m.in_f[g] * m.out_f[g] for g in range(m.ngemm)), 'mlp_bwd'))
 
 
+def adamw_step(d: '_lib.AdamWDesc') -> None:
+    """One multi-tensor AdamW launch with the pack epilogue (sda_adamw_step, csrc/optim.hip; sda_amd.training.AdamW)."""
+    _lib.check(_lib.load().sda_adamw_step(ctypes.byref(d), _stream()), 'sda_adamw_step')
+
+
 def mlp_wgrad_work_floats(d: '_lib.MlpWgradDesc') -> int:
     """Floats of the ``work`` buffer sda_mlp_wgrad needs for this descriptor (``d.work`` is not read)."""
     floats = _lib.load().sda_mlp_wgrad_work_floats(ctypes.byref(d))

@@ -76,18 +76,22 @@ _SCHEDULES = {
 
 def loop(sde: 'VPSDE', trainset, validset, epochs: int = 256, batch_size: int = 64, optimizer: str = 'AdamW',
          learning_rate: float = 1e-3, weight_decay: float = 1e-3, scheduler: str = 'linear', device: str = 'cpu',
-         **absorb) -> Iterator:
+         fused: bool = False, **absorb) -> Iterator:
     """Train ``sde`` (its score network) on ``trainset`` and yield ``(loss_train, loss_valid, lr)`` once per epoch.
 
     As the reference's loop: shuffled DataLoaders whose items are ``(x, kwargs)`` pairs (``kwargs`` go on to ``sde.loss``),
     AdamW over ``sde.parameters()``, the learning rate scaled per epoch by the ``linear`` / ``cosine`` / ``exponential`` factor,
     the mean training loss, the mean validation loss (under ``no_grad``) and the learning rate the epoch ran with.  Parameter
-    gradients are switched on (``sda_amd.training.parameter_gradients(mlp=True)``: the U-Nets and ScoreNet) while the training steps run."""
+    gradients are switched on (``sda_amd.training.parameter_gradients(mlp=True)``: the U-Nets and ScoreNet) while the training steps run.
+    ``fused=True`` takes ``sda_amd.training.AdamW`` (one launch per step, the ResMLP weight slabs stay packed) for ``torch.optim.AdamW``."""
     from torch.utils.data import DataLoader
     loaders = [DataLoader(ds, batch_size=batch_size, shuffle=True) for ds in (trainset, validset)]
     if optimizer != 'AdamW':
         raise ValueError(f'optimizer {optimizer!r} (the loop knows AdamW)')
-    opt = torch.optim.AdamW(sde.parameters(), lr=learning_rate, weight_decay=weight_decay)
+    if fused:
+        opt = training.AdamW(sde.parameters(), lr=learning_rate, weight_decay=weight_decay, net=sde)
+    else:
+        opt = torch.optim.AdamW(sde.parameters(), lr=learning_rate, weight_decay=weight_decay)
     if scheduler not in _SCHEDULES:
         raise ValueError(f'scheduler {scheduler!r} (expected one of {sorted(_SCHEDULES)})')
     sched = torch.optim.lr_scheduler.LambdaLR(opt, lr_lambda=_SCHEDULES[scheduler](epochs))

@@ -1,13 +1,16 @@
 """ms per training step (loss, backward, AdamW step) of the Lorenz LOCAL score kernel -- the reference's LOCAL_CONFIG: ScoreNet(15,
 embedding 32) over a ResMLP 47 -> 256 x 5 -> 15, SiLU -- on the device route (sda_amd.training.parameter_gradients(mlp=True),
 csrc/mlp_train.hip) against the same network as plain torch.nn modules under PyTorch eager autograd, on the same GPU in the same process,
-the two alternating block by block; per batch also loss + backward alone (no optimizer step) of each route.  Batch 64 is train_local's; 4096 is the row count of MCScoreNet training.
+and a third route, the device route with this project's optimizer (sda_amd.training.AdamW, csrc/optim.hip: one launch, the plan's weight slabs stay
+packed) -- the three alternating block by block; per batch also loss + backward alone (no optimizer step) of each route.  Batch 64 is train_local's;
+4096 is the row count of MCScoreNet training.
 
     python tools/mlp_train_bench.py [--iters 200] [--blocks 5] [--out profiles/mlp_train_bench.json]
 
 Per block and route: warm-up steps, then `iters` steps between two events; the figure reported is the median block.  The launch count is
-the number of this project's kernels one ResMLP forward + backward issues (the time embedding, the loss and AdamW are torch's on both
-routes)."""
+the number of this project's kernels one ResMLP forward + backward issues (the time embedding and the loss are torch's on every route, AdamW
+on the first two); `fused_step_launches` adds the optimizer launches of the third route.  `fused_optimizer_ms` = the fused step minus
+loss + backward alone."""
 import argparse
 import json
 import os
@@ -85,24 +88,27 @@ def main():
     ref = _TorchScoreNet().to(dev)
     opt_hip = torch.optim.AdamW(kernel.parameters(), lr=1e-3, weight_decay=1e-3)
     opt_ref = torch.optim.AdamW(ref.parameters(), lr=1e-3, weight_decay=1e-3)
+    opt_fused = training.AdamW(kernel.parameters(), lr=1e-3, weight_decay=1e-3, net=kernel)
 
     # launches of this project's kernels per ResMLP forward + backward
     counts = {'n': 0}
     wrapped = {}
-    for name, k in (('mlp_launch', 1), ('mlp_bwd_train', 1), ('mlp_wgrad', 2)):
+    for name, k in (('mlp_launch', 1), ('mlp_bwd_train', 1), ('mlp_wgrad', 2), ('adamw_step', 1)):
         fn = getattr(ops, name)
         wrapped[name] = fn
         setattr(ops, name, (lambda f, kk: lambda *a, **kw: (counts.__setitem__('n', counts['n'] + kk), f(*a, **kw))[1])(fn, k))
     with training.parameter_gradients(mlp=True):
         sde.loss(torch.randn(64, 15, device=dev)).backward()
     launches = counts['n']
+    opt_fused.step()
+    fused_launches = counts['n']
     for name, fn in wrapped.items():
         setattr(ops, name, fn)
-    opt_hip.zero_grad()
+    opt_fused.zero_grad()
 
     result = {'network': 'ScoreNet(15, embedding=32) / ResMLP 47 -> 256 x 5 -> 15 -> block(15), SiLU (LOCAL_CONFIG)',
               'step': 'VPSDE loss + backward + AdamW step', 'iters': args.iters, 'warmup': args.warmup, 'blocks': args.blocks,
-              'resmlp_launches_per_step': launches, 'device': torch.cuda.get_device_name(0), 'batches': {}}
+              'resmlp_launches_per_step': launches, 'fused_step_launches': fused_launches, 'device': torch.cuda.get_device_name(0), 'batches': {}}
     try:
         result['clock_mhz'] = torch.cuda.clock_rate()
     except Exception as e:  # noqa: BLE001 -- the SMI binding is optional
@@ -116,15 +122,22 @@ def main():
             opt_hip.step()
             opt_hip.zero_grad()
 
+        def step_fused():
+            with training.parameter_gradients(mlp=True):
+                sde.loss(x).backward()
+            opt_fused.step()
+            opt_fused.zero_grad()
+
         def step_ref():
             _torch_loss(ref, x).backward()
             opt_ref.step()
             opt_ref.zero_grad()
-        hip, eager = [], []
-        for _ in range(args.blocks):                      # alternate the two routes
+        hip, fused, eager = [], [], []
+        for _ in range(args.blocks):                      # alternate the three routes
             hip.append(_time(step_hip, args.warmup, args.iters))
+            fused.append(_time(step_fused, args.warmup, args.iters))
             eager.append(_time(step_ref, args.warmup, args.iters))
-        h, r = statistics.median(hip), statistics.median(eager)
+        h, fu, r = statistics.median(hip), statistics.median(fused), statistics.median(eager)
 
         # where the time goes: loss + backward alone (gradients accumulate; no optimizer step), one block per route
         def fb_hip():
@@ -136,9 +149,15 @@ def main():
         fh, fr = _time(fb_hip, args.warmup, args.iters), _time(fb_ref, args.warmup, args.iters)
         opt_hip.zero_grad()
         opt_ref.zero_grad()
+        # the optimizer's cost on the fused route: one more block of the fused step right behind loss + backward alone
+        ff = _time(step_fused, args.warmup, args.iters)
         result['batches'][str(batch)] = {'device_route_ms': h, 'torch_eager_ms': r, 'eager_over_device': r / h,
                                          'device_route_loss_backward_ms': fh, 'torch_eager_loss_backward_ms': fr,
-                                         'device_route_blocks_ms': hip, 'torch_eager_blocks_ms': eager}
+                                         'device_route_blocks_ms': hip, 'torch_eager_blocks_ms': eager,
+                                         'fused_route_ms': fu, 'eager_over_fused': r / fu, 'device_over_fused': h / fu,
+                                         'fused_route_blocks_ms': fused,
+                                         'fused_slowest_below_device_fastest': max(fused) < min(hip),
+                                         'fused_route_step_after_loss_backward_ms': ff, 'fused_optimizer_ms': ff - fh}
     os.makedirs(os.path.dirname(args.out) or '.', exist_ok=True)
     with open(args.out, 'w') as f:
         json.dump(result, f, indent=1)
