@@ -21,13 +21,14 @@
 // replayed on the CPU by the emulator at the bottom (built only into libsda_emu.so for tests/).
 #include "sda_common.hpp"
 #include <stdlib.h>
+#include <string.h>
 
 #ifndef SDA_CONV_CK
 #define SDA_CONV_CK 8
 #endif
-// This file is compiled once per SDA_CONV_PART (sda_amd/build.py) so that the ~60 kernel instantiations build in parallel:
-//   part 0: the C ABI, planner, generic kernel, parity / 32-channel-stage variants;   part 1: 3x3 kernels, cout tiles 32/64;
-//   part 2: 3x3 kernels, cout tiles 96/128;   part 3: 1x3 kernels (1-D nets)
+// This file is compiled once per SDA_CONV_PART (sda_amd/build.py) so that the 94 kernel instantiations build in parallel (85 of
+// conv_igemm_ws_kernel, 8 of conv_igemm_kernel, the weight repack; CONV_ROWS_P0 .. P3 below): part 0: the C ABI, planner, generic kernel,
+// parity / deep-stage variants;   part 1: 3x3 kernels, cout tiles 32/64;   part 2: 3x3 kernels, cout tiles 96/128;   part 3: 1x3 kernels (1-D nets)
 #ifndef SDA_CONV_PART
 #define SDA_CONV_PART 0
 #endif
@@ -253,6 +254,71 @@ __host__ __device__ inline void conv_epilogue_store(const sda_conv_desc& d, cons
 // D-fragment row of accumulator register r for v_mfma_f32_32x32x2_f32 (col = lane & 31)
 __host__ __device__ inline int mfma32_row(int r, int lane) { return (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5); }
 
+// ---------------------------------------------------------------- which direct kernel serves a launch (host; no device, no environment)
+// Two rules that conv_igemm_ws_kernel shares with its launcher.  Two workgroups per CU: __launch_bounds__ and (if 2 x the LDS fits) the grid
+constexpr bool conv_ws_two_per_cu(int mt, int nt, int spad, int ck) { return ck == SDA_CONV_CK && nt == 1 && mt <= 3 && spad <= 392; }
+constexpr int conv_ws_buf_floats(int mt, int spad, int ntaps, int ck) { return ntaps * ck * mt * 32 + ck * spad; }    // one stage buffer
+// wide (dwordx4) epilogue through a wave-private LDS slab: needs NT = 2 (64-pixel runs) and 8 KiB more LDS (0: narrow epilogue)
+constexpr int conv_ws_slab_bytes(int nt, int buf) { return (nt == 2 && 2 * buf * 4 + 4 * 16 * 32 * nt * 4 <= 160 * 1024) ? 4 * 16 * 32 * nt * 4 : 0; }
+constexpr int conv_ws_lds_bytes(int nt, int buf) { return 2 * buf * 4 + conv_ws_slab_bytes(nt, buf); }
+// $SDA_CONV_V1 (set: v1 only), $SDA_CONV_NT (1 / 2: that pixel tile only), $SDA_CONV_CK32 / $SDA_CONV_CK16 (0: no deep stages)
+struct ConvSwitches { bool force_v1; int nt; bool ck32, ck16; };
+struct ConvPick { int kernel, mt, nt, spad, kh, kw, ck, npos; };   // kernel 0: v1 <mt, npos>; 1: conv_igemm_ws_kernel<mt, nt, spad, kh, kw, ck>
+
+// The shipped instantiations, each written once: WS(KH, KW, MT, NT, SPAD, CK) and V1(MT, NPOS), grouped by the part that compiles them.
+// SPAD (LDS stride between the channel planes of the halo tile, >= S) comes in classes:
+//   NT = 1 (128-pixel tiles, two workgroups per CU when LDS allows): 272 / 392 / 1024, 1024 only for MT <= 3 (MT = 4: v1 serves S > 392)
+//   NT = 2 (256-pixel tiles, one workgroup per CU):                  400 / 520 / 1280
+#define CONV_WS_CLASSES4(WS, KH, KW, MT) \
+    WS(KH, KW, MT, 1, 272, 8) WS(KH, KW, MT, 1, 392, 8) WS(KH, KW, MT, 2, 400, 8) WS(KH, KW, MT, 2, 520, 8) WS(KH, KW, MT, 2, 1280, 8)
+#define CONV_WS_CLASSES(WS, KH, KW, MT) CONV_WS_CLASSES4(WS, KH, KW, MT) WS(KH, KW, MT, 1, 1024, 8)
+// part 0: v1 (any kernel size; NPOS halo positions per thread); the parity classes of a stride-2 head's VJP (1 x 1 .. 2 x 2 taps, MT = 3)
+// and the deep-stage forms (conv_pick below): parity shapes with 16- / 32-channel stages, 1 x 3 layers with 32-channel stages
+#define CONV_ROWS_P0(WS, V1) \
+    V1(1, 2) V1(1, 4) V1(2, 2) V1(2, 4) V1(3, 2) V1(3, 4) V1(4, 2) V1(4, 4) \
+    CONV_WS_CLASSES(WS, 1, 1, 3) CONV_WS_CLASSES(WS, 1, 2, 3) CONV_WS_CLASSES(WS, 2, 1, 3) CONV_WS_CLASSES(WS, 2, 2, 3) \
+    WS(2, 2, 3, 2, 400, 16) WS(2, 2, 3, 2, 520, 16) WS(1, 1, 3, 2, 400, 16) WS(1, 1, 3, 2, 520, 16) WS(1, 1, 3, 2, 400, 32) \
+    WS(1, 2, 3, 2, 400, 16) WS(1, 2, 3, 2, 520, 16) WS(1, 2, 3, 2, 400, 32) WS(2, 1, 3, 2, 400, 16) WS(2, 1, 3, 2, 520, 16) WS(2, 1, 3, 2, 400, 32) \
+    WS(1, 3, 1, 1, 272, 32) WS(1, 3, 1, 1, 392, 32) WS(1, 3, 2, 1, 272, 32) WS(1, 3, 2, 1, 392, 32)
+#define CONV_ROWS_P1(WS, V1) CONV_WS_CLASSES(WS, 3, 3, 1) CONV_WS_CLASSES(WS, 3, 3, 2)
+#define CONV_ROWS_P2(WS, V1) CONV_WS_CLASSES(WS, 3, 3, 3) CONV_WS_CLASSES4(WS, 3, 3, 4)
+#define CONV_ROWS_P3(WS, V1) CONV_WS_CLASSES(WS, 1, 3, 1) CONV_WS_CLASSES(WS, 1, 3, 2) CONV_WS_CLASSES(WS, 1, 3, 3) CONV_WS_CLASSES4(WS, 1, 3, 4)
+#define CONV_WS_PICK(KH, KW, MT, NT, SPAD, CK) {1, MT, NT, SPAD, KH, KW, CK, 0},
+#define CONV_V1_PICK(MT, NPOS) {0, MT, 0, 0, 0, 0, 0, NPOS},
+// Plans the launch and names the instantiation that serves it; returns what sda_conv_igemm returns short of the launch's own status.
+static int conv_pick(const sda_conv_desc* d, const ConvSwitches& sw, ConvGeom* g, ConvPick* p) {
+    if (!d) return SDA_E_BADARG;
+    const bool parity_shape = d->mt == 3 && d->kh >= 1 && d->kh <= 2 && d->kw >= 1 && d->kw <= 2;
+    if (!sw.force_v1 && ((d->kh == 3 && d->kw == 3) || (d->kh == 1 && d->kw == 3) || parity_shape)) {
+        // 256-pixel tiles (one workgroup per CU) unless the problem is too small to give every CU a tile, or forced
+        int rc = sw.nt == 1 ? SDA_E_LDS : conv_plan(d, g, 256, 1280, false);
+        if (sw.nt != 2 && (rc != SDA_OK || g->grid < 256)) rc = conv_plan(d, g, 128, 1024, false);
+        if (rc != SDA_OK && rc != SDA_E_UNSUPPORTED && rc != SDA_E_LDS) return rc;
+        const int nt = rc != SDA_OK ? 0 : g->tn * g->tr * g->tw == 128 ? 1 : 2, S = nt ? g->S : 0;
+        const int spad = nt == 2 ? (S <= 400 ? 400 : S <= 520 ? 520 : S <= 1280 ? 1280 : 0)
+                       : nt == 1 ? (S <= 272 ? 272 : S <= 392 ? 392 : (d->mt <= 3 && S <= 1024) ? 1024 : 0) : 0;
+        int ck = SDA_CONV_CK;                            // input channels per K-stage; deeper for two latency-bound shape classes:
+        // 1-D nets with a tile or less per CU are latency-bound: every K-stage costs one exposed global-load round trip
+        // (12 of the 21 us of a 64-channel, 64-pixel Lorenz layer), so they take 32-channel stages -- a quarter of the trips
+        if (sw.ck32 && d->kh == 1 && d->kw == 3 && nt == 1 && g->grid <= 256 && S <= 392 && d->cin_pad % 32 == 0 && d->mt <= 2) ck = 32;
+        // The parity classes of a stride-2 head's VJP (1 x 1 .. 2 x 2 taps): an 8-channel stage is only 1-4 taps of MFMAs
+        // (1.5-6 k cycles) against one HBM round trip of the stage behind it (~4-5 k cycles, the pipeline is one stage deep):
+        // they take 16-channel stages -- half the barriers, twice the multiply time per round trip;
+        // 1 and 2 taps: 32-channel stages (6-12 k cycles of MFMAs per round trip)
+        else if (sw.ck16 && parity_shape && d->cin_pad % 16 == 0 && nt == 2 && S <= 520)
+            ck = (d->kh * d->kw <= 2 && d->cin_pad % 32 == 0 && S <= 400) ? 32 : 16;
+        if (spad) {                                      // (no class holds S: v1 serves it, e.g. MT = 4 on the 128-pixel tile with S > 392)
+            g->nstage = d->cin_pad / ck;
+            *p = ConvPick{1, d->mt, nt, spad, d->kh, d->kw, ck, 0};
+            return SDA_OK;
+        }
+    }
+    const int rc = conv_plan(d, g);
+    if (rc != SDA_OK) return rc;
+    *p = ConvPick{0, d->mt, 0, 0, 0, 0, 0, (g->S + SDA_CONV_THREADS - 1) / SDA_CONV_THREADS <= 2 ? 2 : SDA_CONV_MAXPOS};
+    return SDA_OK;
+}
+
 // ---------------------------------------------------------------- the kernel
 #ifndef SDA_HOST_EMU
 
@@ -377,14 +443,13 @@ __global__ __launch_bounds__(SDA_CONV_THREADS) void conv_igemm_kernel(const sda_
 // Compile-time: MT (cout tile = 32 MT), NT (pixel tile = 128 NT; each consumer wave owns 32 NT pixels x all MT cout
 // sub-tiles), SPAD (LDS stride between channel planes of the halo tile, >= S), KH x KW.
 template <int MT, int NT, int SPAD, int KH, int KW, int CK = SDA_CONV_CK>
-__global__ __launch_bounds__(512, ((CK == SDA_CONV_CK && NT == 1 && MT <= 3 && SPAD <= 392) ? 4 : 2)) void conv_igemm_ws_kernel(const sda_conv_desc d, const ConvGeom g) {
+__global__ __launch_bounds__(512, conv_ws_two_per_cu(MT, NT, SPAD, CK) ? 4 : 2) void conv_igemm_ws_kernel(const sda_conv_desc d, const ConvGeom g) {
     constexpr int BM = MT * 32;
     constexpr int NTAPS = KH * KW;
     constexpr int NPOS = (SPAD + 255) / 256;
     constexpr int WSZ = NTAPS * CK * BM;     // floats of one weight slab
     constexpr int BUF = WSZ + CK * SPAD;     // floats of one stage buffer
-    // wide (dwordx4) epilogue through a wave-private LDS slab: needs NT = 2 (64-pixel runs) and 8 KiB more LDS
-    constexpr bool WIDE_EPI = (NT == 2) && (2 * BUF * 4 + 4 * 16 * 32 * NT * 4 <= 160 * 1024);
+    constexpr bool WIDE_EPI = conv_ws_slab_bytes(NT, BUF) > 0;
     extern __shared__ __attribute__((aligned(16))) float smem[];
 
     const int tid = threadIdx.x;
@@ -708,11 +773,9 @@ __global__ __launch_bounds__(512, ((CK == SDA_CONV_CK && NT == 1 && MT <= 3 && S
     }
 }
 
-template <int MT, int NT, int SPAD, int KH, int KW, int CK = SDA_CONV_CK>
+template <int MT, int NT, int SPAD, int KH, int KW, int CK>
 static int conv_launch_ws(const sda_conv_desc* d, const ConvGeom& g, hipStream_t stream) {
-    constexpr int BUF = KH * KW * CK * MT * 32 + CK * SPAD;
-    constexpr int slab = (NT == 2 && 2 * BUF * 4 + 4 * 16 * 32 * NT * 4 <= 160 * 1024) ? 4 * 16 * 32 * NT * 4 : 0;
-    constexpr int lds = 2 * BUF * 4 + slab;
+    constexpr int lds = conv_ws_lds_bytes(NT, conv_ws_buf_floats(MT, SPAD, KH * KW, CK));
     static_assert(lds <= 160 * 1024, "stage buffers exceed the LDS");
     auto kern = conv_igemm_ws_kernel<MT, NT, SPAD, KH, KW, CK>;
     static bool attr_set[SDA_MAX_DEVICES];           // per device: a process may use several GPUs
@@ -723,7 +786,7 @@ static int conv_launch_ws(const sda_conv_desc* d, const ConvGeom& g, hipStream_t
     // persistent grid: as many workgroups as stay co-resident
     const int cus = sda_cu_count();
     if (!cus) return SDA_E_BADARG;
-    const int per_cu = (CK == SDA_CONV_CK && NT == 1 && 2 * lds <= 160 * 1024 && MT <= 3 && SPAD <= 392) ? 2 : 1;
+    const int per_cu = (conv_ws_two_per_cu(MT, NT, SPAD, CK) && 2 * lds <= 160 * 1024) ? 2 : 1;
     int grid = cus * per_cu;
     grid -= grid % 8;
     const int need = (g.grid + 7) / 8 * 8;            // never launch more workgroups than there are tiles (x8 for the XCD map)
@@ -733,161 +796,78 @@ static int conv_launch_ws(const sda_conv_desc* d, const ConvGeom& g, hipStream_t
     return sda_launch_status();
 }
 
-// NT = 2 (256-pixel tiles, one workgroup per CU): SPAD classes 400 / 520 / 1280
-// NT = 1 (128-pixel tiles, two workgroups per CU when LDS allows): SPAD classes 272 / 392 / 1024
-template <int MT, int KH, int KW>
-static int conv_launch_ws_s(const sda_conv_desc* d, const ConvGeom& g, hipStream_t stream) {
-    if (g.tn * g.tr * g.tw == 128) {
-        if (g.S <= 272) return conv_launch_ws<MT, 1, 272, KH, KW>(d, g, stream);
-        if (g.S <= 392) return conv_launch_ws<MT, 1, 392, KH, KW>(d, g, stream);
-        if (MT <= 3 && g.S <= 1024) return conv_launch_ws<MT, 1, 1024, KH, KW>(d, g, stream);
-        return SDA_E_LDS;
-    }
-    if (g.S <= 400) return conv_launch_ws<MT, 2, 400, KH, KW>(d, g, stream);
-    if (g.S <= 520) return conv_launch_ws<MT, 2, 520, KH, KW>(d, g, stream);
-    if (g.S <= 1280) return conv_launch_ws<MT, 2, 1280, KH, KW>(d, g, stream);
-    return SDA_E_LDS;
-}
-
-// the big instantiation families live in their own translation units (parts 1-3)
-int sda_conv_ws_k33_lo(const sda_conv_desc* d, const ConvGeom& g, hipStream_t stream);    // 3x3, mt 1..2
-int sda_conv_ws_k33_hi(const sda_conv_desc* d, const ConvGeom& g, hipStream_t stream);    // 3x3, mt 3..4
-int sda_conv_ws_k13(const sda_conv_desc* d, const ConvGeom& g, hipStream_t stream);       // 1x3, mt 1..4
-#if SDA_CONV_PART == 1
-int sda_conv_ws_k33_lo(const sda_conv_desc* d, const ConvGeom& g, hipStream_t stream) {
-    return d->mt == 1 ? conv_launch_ws_s<1, 3, 3>(d, g, stream) : conv_launch_ws_s<2, 3, 3>(d, g, stream);
-}
-#elif SDA_CONV_PART == 2
-int sda_conv_ws_k33_hi(const sda_conv_desc* d, const ConvGeom& g, hipStream_t stream) {
-    return d->mt == 3 ? conv_launch_ws_s<3, 3, 3>(d, g, stream) : conv_launch_ws_s<4, 3, 3>(d, g, stream);
-}
-#elif SDA_CONV_PART == 3
-int sda_conv_ws_k13(const sda_conv_desc* d, const ConvGeom& g, hipStream_t stream) {
-    switch (d->mt) {
-        case 1: return conv_launch_ws_s<1, 1, 3>(d, g, stream);
-        case 2: return conv_launch_ws_s<2, 1, 3>(d, g, stream);
-        case 3: return conv_launch_ws_s<3, 1, 3>(d, g, stream);
-        default: return conv_launch_ws_s<4, 1, 3>(d, g, stream);
-    }
-}
-#endif
-
-#if SDA_CONV_PART == 0
-
 template <int MT, int NPOS>
 static int conv_launch_t(const sda_conv_desc* d, const ConvGeom& g, hipStream_t stream) {
     auto kern = conv_igemm_kernel<MT, NPOS>;
-    if (g.lds_bytes > 48 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           (int)g.lds_bytes);
-        if (e != hipSuccess) return (int)e;
-    }
+    static bool attr_set[SDA_MAX_DEVICES];           // (the LDS varies per launch: raised once, to the 160 KiB conv_plan caps it at)
+    const int rc = g.lds_bytes > 48 * 1024 ? sda_raise_dyn_lds(reinterpret_cast<const void*>(kern), 160 * 1024, attr_set) : SDA_OK;
+    if (rc != SDA_OK) return rc;
     hipLaunchKernelGGL(kern, dim3(g.grid), dim3(SDA_CONV_THREADS), (size_t)g.lds_bytes, stream, *d, g);
     return sda_launch_status();
 }
 
-template <int MT>
-static int conv_launch_m(const sda_conv_desc* d, const ConvGeom& g, hipStream_t stream) {
-    int npos = (g.S + SDA_CONV_THREADS - 1) / SDA_CONV_THREADS;
-    if (npos <= 2) return conv_launch_t<MT, 2>(d, g, stream);
-    return conv_launch_t<MT, SDA_CONV_MAXPOS>(d, g, stream);
+// this part's rows of the variant table with their launchers (null: `p` is no row of this part); parts 1-3 hold the big families
+typedef int (*conv_launch_fn)(const sda_conv_desc*, const ConvGeom&, hipStream_t);
+conv_launch_fn sda_conv_variant_p0(const ConvPick& p), sda_conv_variant_p1(const ConvPick& p), sda_conv_variant_p2(const ConvPick& p),
+    sda_conv_variant_p3(const ConvPick& p);
+#define CONV_WS_VARIANT(KH, KW, MT, NT, SPAD, CK) {CONV_WS_PICK(KH, KW, MT, NT, SPAD, CK) conv_launch_ws<MT, NT, SPAD, KH, KW, CK>},
+#define CONV_V1_VARIANT(MT, NPOS) {CONV_V1_PICK(MT, NPOS) conv_launch_t<MT, NPOS>},
+#define CONV_PART_NAME_(stem, k) stem##k
+#define CONV_PART_NAME(stem, k) CONV_PART_NAME_(stem, k)
+conv_launch_fn CONV_PART_NAME(sda_conv_variant_p, SDA_CONV_PART)(const ConvPick& p) {
+    static const struct { ConvPick pick; conv_launch_fn launch; } rows[] = {
+        CONV_PART_NAME(CONV_ROWS_P, SDA_CONV_PART)(CONV_WS_VARIANT, CONV_V1_VARIANT)};
+    for (const auto& v : rows)
+        if (!memcmp(&v.pick, &p, sizeof(p))) return v.launch;
+    return nullptr;
 }
 
-// each *_try returns SDA_E_UNSUPPORTED when its kernel does not take the launch: the next one, last the direct kernel, serves it
+#if SDA_CONV_PART == 0
+// The kernel families in front of the direct kernels, in the order they are offered a launch: sda_conv_igemm and _path walk this one list.
 int sda_wino4_try(const sda_conv_desc* d, hipStream_t stream);  // Winograd F(2x2,3x3), one wave per SIMD (conv_wino4.hip)
 int sda_small1d_try(const sda_conv_desc* d, hipStream_t stream); // small 1-D layers: one round trip per launch (conv_small1d.hip)
 int sda_few_try(const sda_conv_desc* d, hipStream_t stream);     // 3 x 3, <= 16 output channels (conv_few.hip)
+int sda_wino4_path(const sda_conv_desc* d), sda_small1d_path(const sda_conv_desc* d), sda_few_path(const sda_conv_desc* d);
+// run: SDA_E_UNSUPPORTED = the tier does not take the launch, the next is asked; path: sda_conv_igemm_path's number if run would take it, else 0
+typedef const sda_conv_desc* conv_dp;
+struct ConvTier { bool (*offered)(conv_dp d); int (*run)(conv_dp d, hipStream_t stream); int (*path)(conv_dp d); };
+static const ConvTier CONV_TIERS[] = {
+    {[](conv_dp d) { return !!d->w_wino4; }, sda_wino4_try, [](conv_dp d) { const int p = sda_wino4_path(d); return p == 2 ? 5 : p ? 2 : 0; }},
+    // pooled output exists in the w_wino4 kernel only: refused (no run), the caller runs the plain launch + a pooling reader instead
+    {[](conv_dp d) { return d->pool_h > 1 || d->pool_w > 1; }, nullptr, nullptr},
+    {[](conv_dp d) { return d->kh == 1 && d->kw == 3; }, sda_small1d_try, [](conv_dp d) { return sda_small1d_path(d) ? 3 : 0; }},
+    {[](conv_dp d) { return d->kh == 3 && d->kw == 3 && d->cout <= 16; }, sda_few_try, [](conv_dp d) { return sda_few_path(d) ? 4 : 0; }},
+};
 
 extern "C" int sda_conv_igemm(const sda_conv_desc* d, void* stream) {
-    hipStream_t s = (hipStream_t)stream;
-    if (d && d->w_wino4) {
-        const int rc4 = sda_wino4_try(d, s);
-        if (rc4 != SDA_E_UNSUPPORTED) return rc4;
+    if (!d) return SDA_E_BADARG;
+    for (const ConvTier& t : CONV_TIERS) {
+        if (!t.offered(d)) continue;
+        if (!t.run) return SDA_E_UNSUPPORTED;
+        const int rc = t.run(d, (hipStream_t)stream);
+        if (rc != SDA_E_UNSUPPORTED) return rc;
     }
-    // (pooled output exists in the w_wino4 kernel only: the caller runs the plain launch + a pooling reader instead)
-    if (d && (d->pool_h > 1 || d->pool_w > 1)) return SDA_E_UNSUPPORTED;
-    if (d && d->kh == 1 && d->kw == 3) {
-        const int rcs = sda_small1d_try(d, s);
-        if (rcs != SDA_E_UNSUPPORTED) return rcs;
-    }
-    if (d && d->kh == 3 && d->kw == 3 && d->cout <= 16) {
-        const int rcf = sda_few_try(d, s);
-        if (rcf != SDA_E_UNSUPPORTED) return rcf;
-    }
-    static const bool force_v1 = getenv("SDA_CONV_V1") != nullptr;
-    const bool parity_shape = d && d->mt == 3 && d->kh >= 1 && d->kh <= 2 && d->kw >= 1 && d->kw <= 2;
-    if (!force_v1 && d && ((d->kh == 3 && d->kw == 3) || (d->kh == 1 && d->kw == 3) || parity_shape)) {
-        ConvGeom g2;
-        // 256-pixel tiles (one workgroup per CU) unless the problem is too small to give every CU a tile, or forced
-        static const int nt_env = getenv("SDA_CONV_NT") ? atoi(getenv("SDA_CONV_NT")) : 0;
-        int rc2 = nt_env == 1 ? SDA_E_LDS : conv_plan(d, &g2, 256, 1280, false);
-        if (nt_env != 2 && (rc2 != SDA_OK || g2.grid < 256)) rc2 = conv_plan(d, &g2, 128, 1024, false);
-        // 1-D nets with a tile or less per CU are latency-bound: every K-stage costs one exposed global-load round trip
-        // (12 of the 21 us of a 64-channel, 64-pixel Lorenz layer), so they take 32-channel stages -- a quarter of the trips
-        static const bool no_ck32 = getenv("SDA_CONV_CK32") != nullptr && atoi(getenv("SDA_CONV_CK32")) == 0;
-        if (rc2 == SDA_OK && !no_ck32 && d->kh == 1 && d->kw == 3 && g2.grid <= 256 && g2.tn * g2.tr * g2.tw == 128 &&
-            g2.S <= 392 && d->cin_pad % 32 == 0 && d->mt <= 2) {
-            g2.nstage = d->cin_pad / 32;
-            if (d->mt == 1) return g2.S <= 272 ? conv_launch_ws<1, 1, 272, 1, 3, 32>(d, g2, s) : conv_launch_ws<1, 1, 392, 1, 3, 32>(d, g2, s);
-            return g2.S <= 272 ? conv_launch_ws<2, 1, 272, 1, 3, 32>(d, g2, s) : conv_launch_ws<2, 1, 392, 1, 3, 32>(d, g2, s);
-        }
-        // The parity classes of a stride-2 head's VJP (1 x 1 .. 2 x 2 taps): an 8-channel stage is only 1-4 taps of MFMAs
-        // (1.5-6 k cycles) against one HBM round trip of the stage behind it (~4-5 k cycles, the pipeline is one stage deep):
-        // they take 16-channel stages -- half the barriers, twice the multiply time per round trip.
-        static const bool no_ck16 = getenv("SDA_CONV_CK16") != nullptr && atoi(getenv("SDA_CONV_CK16")) == 0;
-        if (rc2 == SDA_OK && parity_shape && !no_ck16 && d->cin_pad % 16 == 0 && g2.tn * g2.tr * g2.tw == 256 && g2.S <= 520) {
-            const bool s400 = g2.S <= 400;
-            if (d->kh == 2 && d->kw == 2) {
-                g2.nstage = d->cin_pad / 16;
-                return s400 ? conv_launch_ws<3, 2, 400, 2, 2, 16>(d, g2, s) : conv_launch_ws<3, 2, 520, 2, 2, 16>(d, g2, s);
-            }
-            if (d->cin_pad % 32 == 0 && s400) {              // 1 and 2 taps: 32-channel stages (6-12 k cycles of MFMAs per round trip)
-                g2.nstage = d->cin_pad / 32;
-                if (d->kh == 1 && d->kw == 1) return conv_launch_ws<3, 2, 400, 1, 1, 32>(d, g2, s);
-                if (d->kh == 1 && d->kw == 2) return conv_launch_ws<3, 2, 400, 1, 2, 32>(d, g2, s);
-                return conv_launch_ws<3, 2, 400, 2, 1, 32>(d, g2, s);
-            }
-            g2.nstage = d->cin_pad / 16;
-            if (d->kh == 1 && d->kw == 1) return s400 ? conv_launch_ws<3, 2, 400, 1, 1, 16>(d, g2, s) : conv_launch_ws<3, 2, 520, 1, 1, 16>(d, g2, s);
-            if (d->kh == 1 && d->kw == 2) return s400 ? conv_launch_ws<3, 2, 400, 1, 2, 16>(d, g2, s) : conv_launch_ws<3, 2, 520, 1, 2, 16>(d, g2, s);
-            return s400 ? conv_launch_ws<3, 2, 400, 2, 1, 16>(d, g2, s) : conv_launch_ws<3, 2, 520, 2, 1, 16>(d, g2, s);
-        }
-        if (rc2 == SDA_OK) {
-            if (d->kw == 3) rc2 = d->kh == 3 ? (d->mt <= 2 ? sda_conv_ws_k33_lo(d, g2, s) : sda_conv_ws_k33_hi(d, g2, s)) : sda_conv_ws_k13(d, g2, s);
-            else if (d->kh == 1) rc2 = d->kw == 1 ? conv_launch_ws_s<3, 1, 1>(d, g2, s) : conv_launch_ws_s<3, 1, 2>(d, g2, s);
-            else rc2 = d->kw == 1 ? conv_launch_ws_s<3, 2, 1>(d, g2, s) : conv_launch_ws_s<3, 2, 2>(d, g2, s);
-            if (rc2 != SDA_E_LDS) return rc2;
-        } else if (rc2 != SDA_E_UNSUPPORTED && rc2 != SDA_E_LDS) {
-            return rc2;
-        }
-    }
-    ConvGeom g;
-    int rc = conv_plan(d, &g);
+    static const ConvSwitches sw = [] {                  // the environment is read here, once
+        const char *v1 = getenv("SDA_CONV_V1"), *nt = getenv("SDA_CONV_NT"), *ck32 = getenv("SDA_CONV_CK32"), *ck16 = getenv("SDA_CONV_CK16");
+        return ConvSwitches{v1 != nullptr, nt ? atoi(nt) : 0, !(ck32 && atoi(ck32) == 0), !(ck16 && atoi(ck16) == 0)};
+    }();
+    ConvGeom g; ConvPick p;
+    const int rc = conv_pick(d, sw, &g, &p);
     if (rc != SDA_OK) return rc;
-    switch (d->mt) {
-        case 1: return conv_launch_m<1>(d, g, s);
-        case 2: return conv_launch_m<2>(d, g, s);
-        case 3: return conv_launch_m<3>(d, g, s);
-        default: return conv_launch_m<4>(d, g, s);
-    }
+    for (auto part : {sda_conv_variant_p0, sda_conv_variant_p1, sda_conv_variant_p2, sda_conv_variant_p3})
+        if (conv_launch_fn launch = part(p)) return launch(d, g, (hipStream_t)stream);
+    return SDA_E_UNSUPPORTED;                            // (not reached: conv_pick names table rows only, tests/test_conv_dispatch_host.py)
 }
 
-// which kernel family sda_conv_igemm would serve this launch with: 2 / 5 Winograd (conv_wino4.hip / its conv_h2 form), 3 the small
-// 1-D kernel (conv_small1d.hip), 4 the few-output-channel 3 x 3 kernel (conv_few.hip), 0 the direct implicit-GEMM kernels
-// (1 was the first-generation Winograd kernel: retired, never returned)
-struct Wino4Geom;
-int sda_wino4_path(const sda_conv_desc* d);
-int sda_small1d_path(const sda_conv_desc* d);
-int sda_few_path(const sda_conv_desc* d);
+// which kernel family sda_conv_igemm would serve this launch with: 2 / 5 Winograd (conv_wino4.hip / its conv_h2 form), 3 the small 1-D kernel
+// (conv_small1d.hip), 4 the few-output-channel 3 x 3 kernel (conv_few.hip), 0 the direct kernels (1: retired Winograd kernel, never returned)
 extern "C" int sda_conv_igemm_path(const sda_conv_desc* d) {
     if (!d) return SDA_E_BADARG;
-    if (d->w_wino4) {
-        const int p4 = sda_wino4_path(d);
-        if (p4) return p4 == 2 ? 5 : 2;
+    for (const ConvTier& t : CONV_TIERS) {
+        if (!t.offered(d)) continue;
+        if (!t.path) return SDA_E_UNSUPPORTED;
+        if (const int id = t.path(d)) return id;
     }
-    if (d->pool_h > 1 || d->pool_w > 1) return SDA_E_UNSUPPORTED;
-    if (d->kh == 1 && d->kw == 3 && sda_small1d_path(d)) return 3;
-    if (d->kh == 3 && d->kw == 3 && d->cout <= 16 && sda_few_path(d)) return 4;
     return 0;
 }
 
@@ -1005,6 +985,25 @@ extern "C" int sda_conv_igemm_emulate(const sda_conv_desc* dp) {
         }
     }
     return SDA_OK;
+}
+
+// conv_pick for tests/test_conv_dispatch_host.py.  out: the pick's 8 fields, g.tn, tr, tw, S, grid, nstage, wide_out, the dynamic-LDS bytes
+extern "C" int sda_conv_igemm_pick(const sda_conv_desc* d, int force_v1, int nt, int ck32, int ck16, int out[16]) {
+    ConvGeom g; ConvPick p;
+    const int rc = conv_pick(d, ConvSwitches{force_v1 != 0, nt, ck32 != 0, ck16 != 0}, &g, &p);
+    if (rc != SDA_OK) return rc;
+    const int lds = p.kernel ? conv_ws_lds_bytes(p.nt, conv_ws_buf_floats(p.mt, p.spad, p.kh * p.kw, p.ck)) : (int)g.lds_bytes;
+    const int geom[8] = {g.tn, g.tr, g.tw, g.S, g.grid, g.nstage, g.wide_out, lds};
+    memcpy(out, &p, sizeof(p));
+    memcpy(out + 8, geom, sizeof(geom));
+    return SDA_OK;
+}
+// the variant table, all parts: copies its rows (the 8 pick fields each) if `cap` rows fit and returns their number
+extern "C" int sda_conv_igemm_variants(int* out, int cap) {
+    static const ConvPick rows[] = {CONV_ROWS_P0(CONV_WS_PICK, CONV_V1_PICK) CONV_ROWS_P1(CONV_WS_PICK, CONV_V1_PICK)
+                                    CONV_ROWS_P2(CONV_WS_PICK, CONV_V1_PICK) CONV_ROWS_P3(CONV_WS_PICK, CONV_V1_PICK)};
+    if (cap >= (int)(sizeof(rows) / sizeof(rows[0]))) memcpy(out, rows, sizeof(rows));
+    return (int)(sizeof(rows) / sizeof(rows[0]));
 }
 
 extern "C" void sda_pack_conv_weight_host(const float* w, int cout, int cin, int kh, int kw, int transpose, int cin_keep,

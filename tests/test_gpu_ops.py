@@ -120,6 +120,54 @@ def test_loader_mod_ln_act_and_epilogue(dev, act):
     assert_close(out, ref_conv(x, wgt, None, 1, True) * dz + res, TOL)
 
 
+def _direct_variant_cases():
+    """For every row of the direct kernels' variant table (csrc/conv_igemm.hip) the recorded launch with the fewest output elements that
+    no other kernel family takes, no switch set (tests/golden/conv_dispatch.json; tests/test_conv_dispatch_host.py checks that every
+    row has one and that conv_pick names that row for it)."""
+    from tests.util import load_conv_dispatch
+    best = {}
+    for c in load_conv_dispatch():
+        if c['rc'] == 0 and c['direct'] and c['switches'] == (0, 0, 1, 1) and not c['misalign']:
+            key = (c['n'] * c['cout'] * c['ho'] * c['wo'], c['cx'])
+            if c['pick'] not in best or key < best[c['pick']][0]:
+                best[c['pick']] = (key, c)
+    return [best[p][1] for p in sorted(best)]
+
+
+def _variant_id(c):
+    k, mt, nt, spad, kh, kw, ck, npos = c['pick']
+    return f'ws_{kh}x{kw}_mt{mt}_nt{nt}_spad{spad}_ck{ck}' if k else f'v1_mt{mt}_npos{npos}'
+
+
+@pytest.mark.parametrize('case', _direct_variant_cases(), ids=_variant_id)
+def test_direct_kernel_every_variant(dev, case):
+    """Every instantiation the direct-kernel dispatch can launch runs once, with bias, against conv2d in float64."""
+    from sda_amd import ops
+    from sda_amd.engine import launch_conv, planar_source
+    c = case
+    n, cin, hs, ws, ho, wo, kh, kw, sh, sw = (c[k] for k in ('n', 'cx', 'hs', 'ws', 'ho', 'wo', 'kh', 'kw', 'stride_h', 'stride_w'))
+    torch.manual_seed(n + 7 * ho + 13 * wo + 31 * kh + 61 * kw)
+    x, w, b = torch.randn(n, cin, hs, ws), torch.randn(c['cout'], cin, kh, kw) / (kh * kw * cin) ** 0.5, torch.randn(c['cout'])
+    pk = ops.PackedConv(w.to(dev), b.to(dev))
+    assert (pk.mt, pk.k_pad, pk.m_pad, pk.wino4) == (c['mt'], c['cin_pad'], c['cout_pad'], None)
+    xd = x.to(dev)                                     # (held: planar_source keeps addresses, not tensors)
+    out = torch.full((n, c['cout'], ho, wo), float('nan'), device=dev)
+    d = launch_conv(pk, planar_source(xd), out, ho, wo, circular=bool(c['circular']), stride=(sh, sw), bias=pk.bias,
+                    pad=(c['pad_h'], c['pad_w']) if c['explicit_pad'] else None)
+    torch.cuda.synchronize()
+    assert ops.conv_path(d) == 0
+    # reference: the rows / columns every output reads, gathered with the launch's padding, then a plain strided convolution
+    ph, pw = (c['pad_h'], c['pad_w']) if c['explicit_pad'] else (kh // 2, kw // 2)
+    rows, cols = torch.arange(-ph, (ho - 1) * sh + kh - ph), torch.arange(-pw, (wo - 1) * sw + kw - pw)
+    if c['circular']:
+        xp = x.double()[:, :, rows % hs][:, :, :, cols % ws]
+    else:
+        inside = ((rows >= 0) & (rows < hs))[:, None] & ((cols >= 0) & (cols < ws))[None, :]
+        xp = x.double()[:, :, rows.clamp(0, hs - 1)][:, :, :, cols.clamp(0, ws - 1)] * inside
+    ref = F.conv2d(xp, w.double(), b.double(), stride=(sh, sw))
+    assert_close(out.cpu(), ref, TOL)
+
+
 @pytest.mark.parametrize('circular', [False, True])
 @pytest.mark.parametrize('shape', [(2, 8, 6, 10, 5), (2, 192, 32, 32, 96), (1, 96, 16, 64, 192)])
 @pytest.mark.parametrize('kern', [(1, 1), (1, 2), (2, 1), (2, 2)])

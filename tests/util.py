@@ -49,6 +49,34 @@ def assert_close(a, b, rtol=1e-4, atol=None, what=''):
                              f'at |b|={b.abs().reshape(-1)[worst]:.3e}')
 
 
+def load_conv_dispatch():
+    """tests/golden/conv_dispatch.json, the direct-kernel dispatch recorded before conv_pick existed: the list of cases.
+    A case is a dict of the descriptor's integer fields, the four switches, `direct` (no other kernel family takes the launch),
+    `rc`, and on rc == 0 `pick` (kernel, mt, nt, spad, kh, kw, ck, npos) and `geom` (tn, tr, tw, S, grid, nstage, wide_out, lds bytes)."""
+    import json
+    with open(os.path.join(GOLDEN, 'conv_dispatch.json')) as f:
+        data = json.load(f)
+    nd, ns = len(data['desc_fields']), len(data['switch_fields'])
+    cases = []
+    for row in data['cases']:
+        c = dict(zip(data['desc_fields'], row[:nd]))
+        c['switches'] = tuple(row[nd:nd + ns])
+        c['direct'], c['rc'] = row[nd + ns], row[nd + ns + 1]
+        c['pick'], c['geom'] = tuple(row[nd + ns + 2:nd + ns + 10]), tuple(row[nd + ns + 10:])
+        cases.append(c)
+    return cases
+
+
+def conv_dispatch_desc(c, x_ptr=0x10000, w_ptr=0x20000, out_ptr=0x30000, **ptrs):
+    """The sda_conv_desc of a load_conv_dispatch() case: a planar source; `misalign` bytes are added to the output address."""
+    from sda_amd.ops import make_conv_desc
+    return make_conv_desc(x_ptr=x_ptr, n=c['n'], cx=c['cx'], hs=c['hs'], ws=c['ws'], x_sc=c['hs'] * c['ws'], x_sy=c['ws'], x_sx=1,
+                          x_sn_outer=c['cx'] * c['hs'] * c['ws'], w_ptr=w_ptr, cin_pad=c['cin_pad'], cout_pad=c['cout_pad'],
+                          cout=c['cout'], kh=c['kh'], kw=c['kw'], out_ptr=out_ptr + c['misalign'], ho=c['ho'], wo=c['wo'], mt=c['mt'],
+                          stride_h=c['stride_h'], stride_w=c['stride_w'], circular=c['circular'],
+                          pad=(c['pad_h'], c['pad_w']) if c['explicit_pad'] else None, **ptrs)
+
+
 # ---------------------------------------------------------------------------- model builders shared by GPU tests
 def build_unet1d_tiny():
     import torch.nn as nn
