@@ -196,6 +196,17 @@ int sda_conv_wgrad(const sda_wgrad_desc* d, void* stream);
 /* planning only (nothing is launched): the slab count the launch would use / the floats of `work` it needs; <0 error */
 int sda_conv_wgrad_slabs(const sda_wgrad_desc* d);
 int64_t sda_conv_wgrad_work_floats(const sda_wgrad_desc* d);
+/* OPT-IN second route for the 3 x 3 block convolutions (csrc/conv_wgrad3.hip; additions that keep ABI v14).  Same descriptor, same
+ * result layout, same slab-order reduction (no atomics, bitwise reproducible, `accumulate` as above); the input tile is staged once
+ * with its halo and the nine taps are shifted reads of it.  Served: 2-D, kh = kw = 3, stride 1, up = zins = pool = 1, cctx = 0, no
+ * explicit pad, planar contiguous source (x_sx = 1, x_sy = ws, x_sc = hs * ws, n_inner = 1), cx % 32 == 0, cout % 32 == 0, circular or
+ * zero padding, loader = ln_mean / ln_rstd + mod (conv1), act_in (conv2) or none, a tile within the 160 KiB LDS (ws <= ~180).
+ * `slabs`: 0 = planner's choice (a function of the shape), at most 256; `work` holds sda_conv_wgrad3_work_floats floats.
+ *   sda_conv_wgrad3_serves: 1 when the launch is in the served set, else 0 (planning only, nothing is launched)
+ *   sda_conv_wgrad3: SDA_E_UNSUPPORTED outside the served set (run sda_conv_wgrad) */
+int sda_conv_wgrad3_serves(const sda_wgrad_desc* d);
+int64_t sda_conv_wgrad3_work_floats(const sda_wgrad_desc* d);
+int sda_conv_wgrad3(const sda_wgrad_desc* d, void* stream);
 /* Gradient of the modulation rows (sda/nn.py:28 ``x + project(y)`` before the LayerNorm): spatial sums of the cotangent at the
  * LayerNorm's input.  x, y: planar [n][c][hw]; out[i * out_sn + ch] (+)= sum_pix (x - y)[i][ch][pix] (y = NULL: x alone), or
  * with sum_images = 1 (a time embedding shared by all images) out[ch] (+)= sum_i sum_pix, images summed in order.

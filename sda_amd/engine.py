@@ -841,6 +841,8 @@ class ParamGrads:
         self.per_image = per_image
         self.gmod = torch.empty_like(mod_all) if (need_mod and mod_all is not None) else None
         self._mod_written = set()
+        from . import training
+        self.route = training.wgrad_route()                 # 'tiled': the block convolutions on csrc/conv_wgrad3.hip
 
     def conv(self, cc: _ConvCache, desc, g: Tensor):
         hit = self.conv_grads.get(id(cc))
@@ -849,7 +851,9 @@ class ParamGrads:
             w, b = cc.conv.weight, cc.conv.bias
             hit = self.conv_grads[id(cc)] = (torch.empty(w.shape, device=g.device, dtype=torch.float32),
                                              None if b is None else torch.empty(b.shape, device=g.device, dtype=torch.float32))
-        ops.conv_wgrad(desc, g, hit[0], hit[1], accumulate)
+        # (the default call stays the one it was: replacements of ops.conv_wgrad that predate the switch keep working)
+        route = {} if self.route == 'general' else dict(route=self.route)
+        ops.conv_wgrad(desc, g, hit[0], hit[1], accumulate, **route)
 
     def modulation(self, blk: _Block, gx: Tensor, g: Tensor, lo: int, mod_total: int):
         """Block ``blk``'s rows: the spatial sums of gx - g (images [lo, lo + n)), summed over the images for a shared row."""

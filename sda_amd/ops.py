@@ -317,8 +317,14 @@ def wgrad_flops(conv: ConvDesc) -> float:
     return 2.0 * conv.n * conv.ho * conv.wo * conv.cout * (conv.cx + conv.cctx) * conv.kh * conv.kw
 
 
-def conv_wgrad(conv: ConvDesc, g: Tensor, dw: Tensor, db: Optional[Tensor], accumulate: bool, slabs: int = 0):
-    """dw (+)= the weight gradient of the layer ``conv`` describes for the output cotangent ``g``; db (+)= its bias gradient."""
+WGRAD_ROUTES = ('general', 'tiled')
+
+
+def conv_wgrad(conv: ConvDesc, g: Tensor, dw: Tensor, db: Optional[Tensor], accumulate: bool, slabs: int = 0, route: str = 'general'):
+    """dw (+)= the weight gradient of the layer ``conv`` describes for the output cotangent ``g``; db (+)= its bias gradient.
+    route 'tiled': the tiled 3 x 3 kernel (csrc/conv_wgrad3.hip) where sda_conv_wgrad3_serves says so, the general kernel otherwise."""
+    if route not in WGRAD_ROUTES:
+        raise ValueError(f"conv_wgrad route {route!r} (expected 'general' or 'tiled')")
     _dev(g, dw, db)
     if not g.is_contiguous() or tuple(g.shape) != (conv.n, conv.cout, conv.ho, conv.wo):
         raise _lib.SdaHipError(f'conv_wgrad: cotangent must be planar contiguous {(conv.n, conv.cout, conv.ho, conv.wo)}, got {tuple(g.shape)}')
@@ -327,19 +333,23 @@ def conv_wgrad(conv: ConvDesc, g: Tensor, dw: Tensor, db: Optional[Tensor], accu
         raise _lib.SdaHipError('conv_wgrad: dw / db do not match the layer')
     lib = _lib.load()
     d = wgrad_desc(conv, g, dw, db, accumulate, slabs)
-    floats = lib.sda_conv_wgrad_work_floats(ctypes.byref(d))
-    _lib.check(int(min(floats, 0)), 'sda_conv_wgrad_work_floats')
+    if route == 'tiled' and lib.sda_conv_wgrad3_serves(ctypes.byref(d)):
+        planner, launch, name, family = lib.sda_conv_wgrad3_work_floats, lib.sda_conv_wgrad3, 'sda_conv_wgrad3', 'wgrad3'
+    else:
+        planner, launch, name, family = lib.sda_conv_wgrad_work_floats, lib.sda_conv_wgrad, 'sda_conv_wgrad', 'wgrad'
+    floats = planner(ctypes.byref(d))
+    _lib.check(int(min(floats, 0)), name + '_work_floats')
     work = torch.empty(int(floats), device=g.device, dtype=torch.float32)
     d.work = work.data_ptr()
     prof = conv_profile
     if prof is not None:
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
-        _lib.check(lib.sda_conv_wgrad(ctypes.byref(d), _stream()), 'sda_conv_wgrad')
+        _lib.check(launch(ctypes.byref(d), _stream()), name)
         e1.record()
-        prof.records.append((e0, e1, wgrad_flops(conv), 'wgrad'))
+        prof.records.append((e0, e1, wgrad_flops(conv), family))
         return
-    _lib.check(lib.sda_conv_wgrad(ctypes.byref(d), _stream()), 'sda_conv_wgrad')
+    _lib.check(launch(ctypes.byref(d), _stream()), name)
 
 
 def plane_sum(x: Tensor, y: Optional[Tensor], out: Tensor, out_sn: int, sum_images: bool, accumulate: bool):

@@ -22,6 +22,10 @@ layers, one slab reduction; sda_amd/mlp.py), the time embedding trains through t
 ``ResMLP`` must be one the whole-MLP kernels take (widths <= 256, biases, one activation, one LayerNorm eps); the fused window
 kernels of the samplers stay sampling-only.  ``sda_amd.utils.loop`` switches both on.
 
+A third opt-in, ``parameter_gradients(wgrad='tiled')`` (or ``enable(wgrad='tiled')``), sends the weight gradients of the 3 x 3,
+stride-1 block convolutions (36 of the 42 launches of a Kolmogorov step) to the tiled kernel csrc/conv_wgrad3.hip; heads, tails, 1-D
+nets and anything else outside its served set stay on the general kernel.  The default ``'general'`` is bitwise what it always was.
+
 :class:`AdamW` is the optimizer step of this route as one launch (csrc/optim.hip) that keeps the ResMLP weight slabs packed."""
 import contextlib
 import math
@@ -37,21 +41,33 @@ SUPPORTED_MLP = ('ScoreNet (TimeEmbedding + ResMLP of Linear layers and LayerNor
                  'activation, one LayerNorm eps), alone or as the kernel of MCScoreNet, on the device, '
                  "with the fp32 multiply (ops.MULTIPLY == 'f32'), under parameter_gradients(mlp=True)")
 
+WGRAD_ROUTES = ('general', 'tiled')
+
 _enabled = False
 _mlp = False
+_wgrad = 'general'
 _local = threading.local()
 
 
-def enable(mlp: bool = False) -> None:
-    """Form parameter gradients in the U-Net backward from now on; ``mlp=True``: in the ScoreNet / ResMLP backward as well."""
-    global _enabled, _mlp
-    _enabled, _mlp = True, bool(mlp)
+def _check_route(wgrad: str) -> str:
+    if wgrad not in WGRAD_ROUTES:
+        raise ValueError(f"wgrad route {wgrad!r} (expected 'general' or 'tiled')")
+    return wgrad
+
+
+def enable(mlp: bool = False, wgrad: str = 'general') -> None:
+    """Form parameter gradients in the U-Net backward from now on; ``mlp=True``: in the ScoreNet / ResMLP backward as well.
+    ``wgrad='tiled'``: the 3 x 3 block convolutions' weight gradients on the tiled kernel (csrc/conv_wgrad3.hip) where it serves the
+    launch; every other layer, and everything under the default ``'general'``, on the general kernel."""
+    global _enabled, _mlp, _wgrad
+    route = _check_route(wgrad)
+    _enabled, _mlp, _wgrad = True, bool(mlp), route
 
 
 def disable() -> None:
-    """Back to the default: input gradients only."""
-    global _enabled, _mlp
-    _enabled, _mlp = False, False
+    """Back to the default: input gradients only (and the general weight-gradient route)."""
+    global _enabled, _mlp, _wgrad
+    _enabled, _mlp, _wgrad = False, False, 'general'
 
 
 def enabled() -> bool:
@@ -63,17 +79,23 @@ def mlp_enabled() -> bool:
     return _enabled and _mlp
 
 
+def wgrad_route() -> str:
+    """The weight-gradient route of the convolutions: 'general' (default) or 'tiled' (the third opt-in)."""
+    return _wgrad
+
+
 @contextlib.contextmanager
-def parameter_gradients(on: bool = True, mlp: bool = False):
-    """Switch parameter gradients on (or off) inside the block, those of ScoreNet / ResMLP with ``mlp=True``; the previous state of
-    both switches is restored on exit."""
-    global _enabled, _mlp
-    prev = (_enabled, _mlp)
-    _enabled, _mlp = bool(on), bool(on) and bool(mlp)
+def parameter_gradients(on: bool = True, mlp: bool = False, wgrad: str = 'general'):
+    """Switch parameter gradients on (or off) inside the block, those of ScoreNet / ResMLP with ``mlp=True``, the block convolutions'
+    weight gradients on the tiled kernel with ``wgrad='tiled'``; the previous state of all three switches is restored on exit."""
+    global _enabled, _mlp, _wgrad
+    route = _check_route(wgrad)
+    prev = (_enabled, _mlp, _wgrad)
+    _enabled, _mlp, _wgrad = bool(on), bool(on) and bool(mlp), route
     try:
         yield
     finally:
-        _enabled, _mlp = prev
+        _enabled, _mlp, _wgrad = prev
 
 
 @contextlib.contextmanager

@@ -1,6 +1,6 @@
 """Training-step benchmark of the opt-in parameter-gradient route (sda_amd.training).  bench.py (sampling) is not involved.
 
-    python tools/train_bench.py [--steps 10] [--warmup 3] [--out profiles/train_bench.json]
+    python tools/train_bench.py [--steps 10] [--warmup 3] [--wgrad general|tiled|both] [--blocks 5] [--out profiles/train_bench.json]
 
 Reports, per configuration (Kolmogorov training net: LocalScoreUNet (96, 192, 384) x (3, 3, 3), embedding 64, batch 32 of
 10 + 1 x 64 x 64; Lorenz global net: 1-D (64,) x (3,), batch 64 x 3 x 32):
@@ -9,10 +9,17 @@ Reports, per configuration (Kolmogorov training net: LocalScoreUNet (96, 192, 38
   * per-family kernel time of one step (ops.ConvProfile): forward convolutions, input-VJP convolutions, weight gradients,
     LayerNorm / modulation reductions, and the share of the torch-autograd modulation / time-embedding GEMMs;
 and, for the Kolmogorov block shapes (96 ch @ 64^2, 192 @ 32^2, 384 @ 16^2, batch 32), the weight-gradient kernel's TFLOP/s and
-its fraction of the fp32 matrix peak (256 CUs x 4 SIMDs x 256 flop/clk x 2.4 GHz = 157.3 TFLOP/s)."""
+its fraction of the fp32 matrix peak (256 CUs x 4 SIMDs x 256 flop/clk x 2.4 GHz = 157.3 TFLOP/s).
+
+--wgrad selects the weight-gradient route of the block convolutions (sda_amd.training: 'general' = csrc/conv_wgrad.hip everywhere,
+'tiled' = csrc/conv_wgrad3.hip where it serves the launch).  --wgrad both times the block shapes and the Kolmogorov step (and the
+oracle's eager step) for the two routes ALTERNATING in one process, block by block (the scheme of tools/mlp_train_bench.py): per
+block warm-up steps, then `steps` steps between two events; reported are the median of `blocks` blocks and the fastest and slowest
+block.  The tiled route earns its place on a shape only where its median is below the general route's FASTEST block."""
 import argparse
 import json
 import os
+import statistics
 import sys
 import time
 
@@ -57,14 +64,14 @@ def configs(dev):
     ]
 
 
-def hip_step(cfg, dev):
+def hip_step(cfg, dev, wgrad='general'):
     net = cfg['net']
     sde = VPSDE(net, shape=cfg['shape']).to(dev)
     opt = torch.optim.AdamW(net.parameters(), lr=1e-4, weight_decay=1e-3)
     x = torch.randn(cfg['batch'], *cfg['shape'], device=dev)
 
     def step():
-        with training.parameter_gradients():
+        with training.parameter_gradients(wgrad=wgrad):
             loss = sde.loss(x)
             loss.backward()
         opt.step()
@@ -93,12 +100,12 @@ def oracle_step(cfg, dev):
     return step
 
 
-def family_profile(sde, x):
+def family_profile(sde, x, wgrad='general'):
     """One training step under ops.ConvProfile: kernel time by family, forward and backward apart."""
     prof = ops.ConvProfile()
     ops.conv_profile = prof
     try:
-        with training.parameter_gradients():
+        with training.parameter_gradients(wgrad=wgrad):
             e0, e1, e2 = (torch.cuda.Event(enable_timing=True) for _ in range(3))
             e0.record()
             loss = sde.loss(x)
@@ -112,7 +119,7 @@ def family_profile(sde, x):
         ops.conv_profile = None
     fam = {}
     for i, (a, b, flops, f) in enumerate(prof.records):
-        key = ('forward.' if i < fwd_n else ('wgrad' if f == 'wgrad' else 'input_vjp.')) + ('' if f == 'wgrad' else f)
+        key = f if f in ('wgrad', 'wgrad3') else ('forward.' if i < fwd_n else 'input_vjp.') + f
         r = fam.setdefault(key, dict(launches=0, ms=0.0, tflop=0.0))
         r['launches'] += 1
         r['ms'] += a.elapsed_time(b)
@@ -127,9 +134,9 @@ def family_profile(sde, x):
         r['ms'] = round(r['ms'], 4)
         if 'tflop' in r:
             r['tflop_s'] = round(r['tflop'] / max(r['ms'], 1e-9) * 1e3, 2)
-    wg = fam.get('wgrad')
-    if wg:
-        wg['fraction_of_fp32_peak'] = round(wg['tflop_s'] * 1e12 / PEAK_FP32_MATRIX, 3)
+    for wg in (fam.get('wgrad'), fam.get('wgrad3')):
+        if wg:
+            wg['fraction_of_fp32_peak'] = round(wg['tflop_s'] * 1e12 / PEAK_FP32_MATRIX, 3)
     return dict(families=fam, loss_ms=round(e0.elapsed_time(e1), 3), backward_ms=round(e1.elapsed_time(e2), 3))
 
 
@@ -148,7 +155,21 @@ def modulation_share(cfg, dev, steps):
     return _timed(run, steps, 2)
 
 
-def wgrad_shapes(dev, steps):
+def _blocks(fns, steps, warmup, blocks):
+    """{route: [ms per step of each block]}: the routes alternate block by block in this one process."""
+    out = {k: [] for k in fns}
+    for _ in range(blocks):
+        for k, fn in fns.items():
+            out[k].append(_timed(fn, steps, warmup))
+    return out
+
+
+def _stat(ms):
+    return dict(median_ms=round(statistics.median(ms), 4), fastest_ms=round(min(ms), 4), slowest_ms=round(max(ms), 4),
+                blocks_ms=[round(v, 4) for v in ms])
+
+
+def wgrad_shapes(dev, steps, routes=('general',), blocks=1):
     """The block conv1 weight gradient (modulation + LayerNorm loader, circular) at the three Kolmogorov block shapes."""
     from sda_amd.ops import make_conv_desc
     rows = []
@@ -164,11 +185,35 @@ def wgrad_shapes(dev, steps):
         d = make_conv_desc(x_ptr=a.data_ptr(), n=n, cx=c, hs=s, ws=s, x_sc=s * s, x_sy=s, x_sx=1, x_sn_outer=c * s * s, w_ptr=0,
                            cin_pad=0, cout_pad=0, cout=c, kh=3, kw=3, out_ptr=0, ho=s, wo=s, mt=1, circular=True,
                            mod_ptr=mod.data_ptr(), mod_sn=c, ln_mean_ptr=mean.data_ptr(), ln_rstd_ptr=rstd.data_ptr())
-        ms = _timed(lambda: ops.conv_wgrad(d, g, dw, db, False), steps, 3)
         flops = ops.wgrad_flops(d)
-        rows.append(dict(channels=c, size=s, batch=n, ms=round(ms, 4), tflop_s=round(flops / ms / 1e9, 2),
-                         fraction_of_fp32_peak=round(flops / ms / 1e9 * 1e12 / PEAK_FP32_MATRIX, 3)))
+        if len(routes) == 1:
+            ms = _timed(lambda: ops.conv_wgrad(d, g, dw, db, False, route=routes[0]), steps, 3)
+            rows.append(dict(channels=c, size=s, batch=n, route=routes[0], ms=round(ms, 4), tflop_s=round(flops / ms / 1e9, 2),
+                             fraction_of_fp32_peak=round(flops / ms / 1e9 * 1e12 / PEAK_FP32_MATRIX, 3)))
+            continue
+        times = _blocks({r: (lambda r=r: ops.conv_wgrad(d, g, dw, db, False, route=r)) for r in routes}, steps, 3, blocks)
+        row = dict(channels=c, size=s, batch=n)
+        for r in routes:
+            st = _stat(times[r])
+            st['tflop_s'] = round(flops / st['median_ms'] / 1e9, 2)
+            st['fraction_of_fp32_peak'] = round(flops / st['median_ms'] / 1e9 * 1e12 / PEAK_FP32_MATRIX, 3)
+            row[r] = st
+        row['general_median_over_tiled_median'] = round(row['general']['median_ms'] / row['tiled']['median_ms'], 3)
+        row['tiled_median_below_general_fastest'] = row['tiled']['median_ms'] < row['general']['fastest_ms']
+        rows.append(row)
     return rows
+
+
+def kolmogorov_both(cfg, dev, steps, warmup, blocks):
+    """The Kolmogorov training step on the two weight-gradient routes and the oracle's eager step, alternating block by block."""
+    fns = {r: hip_step(cfg, dev, r)[0] for r in ('general', 'tiled')}
+    fns['eager'] = oracle_step(cfg, dev)
+    times = _blocks(fns, steps, warmup, blocks)
+    out = {k: _stat(v) for k, v in times.items()}
+    out['tiled_over_eager'] = round(out['eager']['median_ms'] / out['tiled']['median_ms'], 3)
+    out['general_over_eager'] = round(out['eager']['median_ms'] / out['general']['median_ms'], 3)
+    out['tiled_step_below_eager'] = out['tiled']['median_ms'] < out['eager']['median_ms']
+    return out
 
 
 def main():
@@ -176,21 +221,34 @@ def main():
     ap.add_argument('--steps', type=int, default=10)
     ap.add_argument('--warmup', type=int, default=3)
     ap.add_argument('--out', default=None)
+    ap.add_argument('--wgrad', choices=('general', 'tiled', 'both'), default='general')
+    ap.add_argument('--blocks', type=int, default=5, help='--wgrad both: blocks per route (median, fastest and slowest are reported)')
     args = ap.parse_args()
     dev = torch.device('cuda:0')
-    result = dict(device=torch.cuda.get_device_name(dev), steps=args.steps, warmup=args.warmup, configs={})
+    route = 'tiled' if args.wgrad in ('tiled', 'both') else 'general'
+    result = dict(device=torch.cuda.get_device_name(dev), steps=args.steps, warmup=args.warmup, wgrad=args.wgrad, configs={})
+    if args.wgrad == 'both':
+        result['blocks'] = args.blocks
+        result['wgrad_block_shapes'] = wgrad_shapes(dev, args.steps, ('general', 'tiled'), args.blocks)
+        print(json.dumps({'wgrad_block_shapes': result['wgrad_block_shapes']}), flush=True)
     for cfg in configs(dev):
-        step, sde, x = hip_step(cfg, dev)
+        if args.wgrad == 'both' and cfg['name'] != 'kolmogorov_train':
+            continue                                     # (1-D nets keep the general kernel under either setting)
+        step, sde, x = hip_step(cfg, dev, route)
         ms = _timed(step, args.steps, args.warmup)
-        prof = family_profile(sde, x)
+        prof = family_profile(sde, x, route)
         mod_ms = modulation_share(cfg, dev, args.steps)
         base_ms = _timed(oracle_step(cfg, dev), args.steps, args.warmup)
         result['configs'][cfg['name']] = dict(
             batch=cfg['batch'], shape=list(cfg['shape']), ms_per_step=round(ms, 3), oracle_fp32_autograd_ms_per_step=round(base_ms, 3),
             speedup_vs_oracle=round(base_ms / ms, 3), modulation_autograd_ms=round(mod_ms, 4),
             modulation_share_of_step=round(mod_ms / ms, 4), profile=prof)
+        if args.wgrad == 'both':
+            result['configs'][cfg['name']]['profiled_route'] = route
+            result['configs'][cfg['name']]['routes'] = kolmogorov_both(cfg, dev, args.steps, args.warmup, args.blocks)
         print(json.dumps({cfg['name']: result['configs'][cfg['name']]}), flush=True)
-    result['wgrad_block_shapes'] = wgrad_shapes(dev, args.steps)
+    if args.wgrad != 'both':
+        result['wgrad_block_shapes'] = wgrad_shapes(dev, args.steps, (args.wgrad,))
     result['time'] = time.strftime('%Y-%m-%dT%H:%M:%S')
     line = json.dumps(result)
     print(line)
