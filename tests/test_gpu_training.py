@@ -259,12 +259,13 @@ def _oracle_grads(module, eps_fn, x, t, e, weight):
     return loss.detach(), dict(zip(names, grads)), sd
 
 
-def _hip_grads(module, shape, x, weight, seed, dev):
+def _hip_grads(module, shape, x, weight, seed, dev, **switch):
+    """``switch``: keywords of ``training.parameter_gradients`` (none: the default route)."""
     from sda_amd.score import VPSDE
     sde = VPSDE(module, shape=shape).to(dev)
     module.zero_grad(set_to_none=True)
     torch.manual_seed(seed)
-    with training.parameter_gradients():
+    with training.parameter_gradients(**switch):
         loss = sde.loss(x, w=weight)
         loss.backward()
     torch.manual_seed(seed)
@@ -273,8 +274,8 @@ def _hip_grads(module, shape, x, weight, seed, dev):
     return loss.detach(), {k: p.grad for k, p in module.named_parameters()}, t, e
 
 
-def _check_net(module, shape, eps_fn, x, weight, dev, seed=11):
-    loss, g, t, e = _hip_grads(module, shape, x, weight, seed, dev)
+def _check_net(module, shape, eps_fn, x, weight, dev, seed=11, **switch):
+    loss, g, t, e = _hip_grads(module, shape, x, weight, seed, dev, **switch)
     loss64, g64, _ = _oracle_grads(module, eps_fn, x, t, e, weight)
     assert abs(loss.item() - loss64.item()) <= 1e-5 * abs(loss64.item())
     for k, ref in g64.items():

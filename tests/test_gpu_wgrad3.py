@@ -1,17 +1,23 @@
-"""Device: the tiled 3 x 3 weight-gradient kernel (csrc/conv_wgrad3.hip) through ``ops.conv_wgrad(route='tiled')`` and through a
-U-Net's backward under ``training.parameter_gradients(wgrad='tiled')``.
+"""Device: the tiled 3 x 3 weight-gradient kernel (csrc/conv_wgrad3.hip) through its C entry, through
+``ops.conv_wgrad(route='tiled')`` and through a U-Net's backward under ``training.parameter_gradients(wgrad='tiled')``.
 
-Layer cases (tests/wgrad3_cases.py) against the float64 reference of tests/wgrad_ref.py within the bound test_gpu_training.py uses
-for the general kernel's layer cases (1e-5 of the largest element); the net-level comparison uses that file's net-level tolerance
-(1e-4 of the largest element of each gradient)."""
+Layer cases (tests/wgrad3_cases.py: every plan dimension off its trivial value), the widest served layers and a sample of
+tests/fuzz/wgrad3_fuzz.py against the float64 reference of tests/wgrad_ref.py within the bound test_gpu_training.py uses for the
+general kernel's layer cases (1e-5 of the largest element); the net-level comparisons use that file's net-level tolerances (1e-4 of
+the largest element of each gradient and 1e-5 on the loss against the float64 oracle, 1e-6 between chunked and unchunked)."""
+import ctypes
+
 import pytest
 import torch
 import torch.nn as nn
 
+from oracle import sda_oracle as O
+from sda_amd import engine as E
 from sda_amd import ops, training
+from sda_amd._lib import load as load_lib
 from tests.util import rel_err
-from tests.wgrad3_cases import CASES, build
-from tests.wgrad_ref import make_case, reference
+from tests.wgrad3_cases import BOUNDARY, CASES, boundary_case, build
+from tests.wgrad_ref import make_case, reference, wgrad_desc
 
 pytestmark = pytest.mark.gpu
 
@@ -42,6 +48,22 @@ def launch(case, dev, route, slabs=0, accumulate=False, dw=None, db=None):
     return dw, db
 
 
+def device_wgrad3(case, dev, slabs=0, accumulate=False, dw=None, db=None):
+    """One launch of the C entry: dw / db start NaN-filled unless given; ``work`` is NaN-filled to exactly the planned size, so an
+    unwritten cell shows."""
+    lib = load_lib()
+    cout, cin = case['cout'], case['v64'].shape[1]
+    dw = torch.full((cout, cin, 3, 3), float('nan'), device=dev) if dw is None else dw
+    db = torch.full((cout,), float('nan'), device=dev) if db is None else db
+    floats = int(lib.sda_conv_wgrad3_work_floats(ctypes.byref(wgrad_desc(case, dw, db, slabs=slabs, accumulate=accumulate))))
+    assert floats > 0, floats
+    work = torch.full((floats,), float('nan'), device=dev)
+    d = wgrad_desc(case, dw, db, work, slabs=slabs, accumulate=accumulate)
+    assert lib.sda_conv_wgrad3(ctypes.byref(d), torch.cuda.current_stream().cuda_stream) == 0
+    torch.cuda.synchronize()
+    return dw, db
+
+
 def family_of(case, dev, route):
     prof = ops.ConvProfile()
     ops.conv_profile = prof
@@ -56,12 +78,14 @@ def family_of(case, dev, route):
 def test_layer_matches_float64_and_the_general_route(dev, cases, name):
     case, rw, rb = cases[name]
     assert family_of(case, dev, 'tiled') == ['wgrad3'] and family_of(case, dev, 'general') == ['wgrad']
-    dw, db = launch(case, dev, 'tiled')
+    dw, db = device_wgrad3(case, dev)
     assert torch.isfinite(dw).all() and torch.isfinite(db).all()
     print(name, 'tiled vs float64: dw', rel_err(dw, rw), 'db', rel_err(db, rb))
     assert rel_err(dw, rw) <= TOL and rel_err(db, rb) <= TOL, (rel_err(dw, rw), rel_err(db, rb))
-    dw2, db2 = launch(case, dev, 'tiled')
+    dw2, db2 = device_wgrad3(case, dev)
     assert torch.equal(dw, dw2) and torch.equal(db, db2)
+    ow, ob = launch(case, dev, 'tiled')                                     # (the route the engine takes: same launch)
+    assert torch.equal(dw, ow) and torch.equal(db, ob)
     gw, gb = launch(case, dev, 'general')
     print(name, 'tiled vs general: dw', rel_err(dw, gw), 'db', rel_err(db, gb))
     assert rel_err(dw, gw) <= TOL and rel_err(db, gb) <= TOL, (rel_err(dw, gw), rel_err(db, gb))
@@ -101,11 +125,60 @@ def test_unserved_descriptor_falls_back_to_the_general_kernel(dev):
     assert rel_err(dw, rw) <= TOL and rel_err(db, rb) <= TOL
 
 
+@pytest.mark.parametrize('cout', list(BOUNDARY))
+def test_widest_served_layer_matches_float64(dev, cout):
+    """The kernel's largest LDS requests (just under 160 KiB): the widest layer of each cout tile, one row per stage."""
+    case = boundary_case(cout, dev)
+    assert family_of(case, dev, 'tiled') == ['wgrad3']
+    rw, rb = reference(case)
+    dw, db = device_wgrad3(case, dev)
+    print(cout, BOUNDARY[cout], 'tiled vs float64: dw', rel_err(dw, rw), 'db', rel_err(db, rb))
+    assert rel_err(dw, rw) <= TOL and rel_err(db, rb) <= TOL, (rel_err(dw, rw), rel_err(db, rb))
+    dw2, db2 = device_wgrad3(case, dev)
+    assert torch.equal(dw, dw2) and torch.equal(db, db2)
+
+
+@pytest.mark.parametrize('cout', list(BOUNDARY))
+def test_one_past_the_widest_falls_back_to_the_general_kernel(dev, cout):
+    case = boundary_case(cout, dev, over=1)
+    assert family_of(case, dev, 'tiled') == ['wgrad']
+    dw, db = launch(case, dev, 'tiled')
+    gw, gb = launch(case, dev, 'general')
+    assert torch.equal(dw, gw) and torch.equal(db, gb)
+    rw, rb = reference(case)
+    assert rel_err(dw, rw) <= TOL and rel_err(db, rb) <= TOL, (rel_err(dw, rw), rel_err(db, rb))
+
+
+def test_wgrad3_fuzz_sample(dev):
+    """The draws of test_wgrad3_host.test_wgrad3_fuzz_sample on the device (tests/fuzz/wgrad3_fuzz.py), each within 1e-5 of float64;
+    the largest |device - emulator| / max |ref| over the sample is printed and goes into any failure message (not asserted: the
+    accumulation order inside the MFMA is not documented to equal the emulator's fmaf chain)."""
+    import random
+    from tests.test_wgrad3_host import FUZZ_CASES, FUZZ_SEED, load_wgrad3_fuzz
+    fuzz = load_wgrad3_fuzz()
+    device, emu = fuzz.device(), fuzz.emulator()
+    rng = random.Random(FUZZ_SEED)
+    bad, gap, worst = [], 0.0, 0.0
+    for i in range(FUZZ_CASES):
+        spec = fuzz.draw_case(rng, i)
+        dw, db, msg = fuzz.run_case(spec, device)
+        if msg is None:
+            ref = fuzz.reference(spec)
+            ew, eb = fuzz.errors(spec, dw, db, ref)
+            worst = max(worst, ew, eb)
+            if not (torch.isfinite(dw).all() and (db is None or torch.isfinite(db).all()) and ew <= fuzz.TOL and eb <= fuzz.TOL):
+                msg = f'dw err {ew:.3e}, db err {eb:.3e}'
+            edw, edb, emsg = fuzz.run_case(spec, emu)
+            assert emsg is None, emsg
+            gap = max(gap, (dw - edw).abs().max().item() / ref[2], 0.0 if db is None else (db - edb).abs().max().item() / ref[3])
+        if msg:
+            bad.append((i, msg, spec['cfg']))
+    print(f'wgrad3 fuzz sample: worst error vs float64 {worst:.3e}, max |device - emulator| / max |ref| = {gap:.3e}')
+    assert not bad, f'max |device - emulator| / max |ref| = {gap:.3e}\n' + '\n'.join(f'case {i}: {m}\n    {c}' for i, m, c in bad)
+
+
 def test_the_c_entry_refuses_an_unserved_descriptor(dev):
-    import ctypes
-    from sda_amd._lib import load
-    from tests.wgrad_ref import wgrad_desc
-    lib = load()
+    lib = load_lib()
     case = make_case('head_s2', dev, cin=32, cout=32, n=2, h=8, w=8, circular=False, seed=46)
     dw, db = torch.full((32, 32, 3, 3), float('nan'), device=dev), torch.full((32,), float('nan'), device=dev)
     work = torch.zeros(1 << 16, device=dev)
@@ -169,3 +242,67 @@ def test_default_switch_is_the_general_route_bitwise(dev):
     assert 'wgrad3' not in fam
     for k in default:
         assert torch.equal(default[k], general[k]), k
+
+
+# ---------------------------------------------------------------------------------------- the workload's widths, float64 oracle
+
+WIDE = (96, 192)
+
+
+def _wide_net(dev):
+    from sda_amd.score import ScoreUNet
+    torch.manual_seed(12)
+    return ScoreUNet(3, embedding=16, hidden_channels=WIDE, hidden_blocks=(1, 1), activation=nn.SiLU, spatial=2,
+                     padding_mode='circular').to(dev)
+
+
+class WgradLaunches:
+    """Stands in for ``ops.conv_wgrad`` and passes every call on: (family, cout, accumulate) of each weight-gradient launch."""
+
+    def __init__(self, monkeypatch):
+        self.calls, self.prof, inner = [], ops.ConvProfile(), ops.conv_wgrad
+
+        def conv_wgrad(conv, g, dw, db, accumulate, *args, **kwargs):
+            before = len(self.prof.records)
+            inner(conv, g, dw, db, accumulate, *args, **kwargs)
+            (record,) = self.prof.records[before:]
+            self.calls.append((record[3], conv.cout, bool(accumulate)))
+        monkeypatch.setattr(ops, 'conv_wgrad', conv_wgrad)
+        monkeypatch.setattr(ops, 'conv_profile', self.prof)
+
+
+def test_wide_net_gradients_on_the_tiled_route_match_the_float64_oracle(dev, monkeypatch):
+    """Cout tiles above the first at net level: every parameter gradient and the loss against torch.autograd of the oracle's float64
+    ``score_unet``, at test_gpu_training's net-level bounds."""
+    from tests.test_gpu_training import _check_net, _kernel_eps
+    net = _wide_net(dev)
+    cfg = O.UNetConfig(3, 3, 16, WIDE, (1, 1), 3, 2, 'SiLU', 2, 'circular')
+    torch.manual_seed(13)
+    x = torch.randn(3, 3, 16, 16, device=dev)
+    seen = WgradLaunches(monkeypatch)
+    _check_net(net, (3, 16, 16), _kernel_eps(cfg), x, None, dev, wgrad='tiled')
+    tiled = [c for c in seen.calls if c[0] == 'wgrad3']
+    assert tiled and any(cout == 192 for _f, cout, _a in tiled), seen.calls
+    assert {cout for _f, cout, _a in tiled} == set(WIDE), seen.calls
+    assert any(f == 'wgrad' for f, _c, _a in seen.calls), seen.calls       # (heads and tails: the general kernel)
+
+
+def test_wide_net_chunked_recompute_on_the_tiled_route(dev, monkeypatch):
+    """Batch 6 recomputed in chunks of 2: the later chunks add into the gradient buffers (``accumulate``) on the tiled route."""
+    from tests.test_gpu_training import _hip_grads
+    net = _wide_net(dev)
+    torch.manual_seed(14)
+    x = torch.randn(6, 3, 16, 16, device=dev)
+    _, g1, _, _ = _hip_grads(net, (3, 16, 16), x, None, 21, dev, wgrad='tiled')
+    g1 = {k: v.clone() for k, v in g1.items()}
+    monkeypatch.setattr(E, 'KEEP_HBM_FRACTION', 1e-12)
+    monkeypatch.setattr(E, 'CHUNK_HBM_FRACTION', 2.5 * net.network.engine().bytes_per_image(16, 16, True) /
+                        torch.cuda.get_device_properties(dev).total_memory)
+    seen = WgradLaunches(monkeypatch)
+    _, g3, _, _ = _hip_grads(net, (3, 16, 16), x, None, 21, dev, wgrad='tiled')
+    tiled = [c for c in seen.calls if c[0] == 'wgrad3']
+    per_conv = len(tiled) // 3
+    assert len(tiled) == 3 * per_conv and sum(a for _f, _c, a in tiled) == 2 * per_conv, seen.calls    # three chunks: write, add, add
+    assert any(cout == 192 and a for _f, cout, a in tiled), seen.calls
+    for k in g1:
+        assert rel_err(g3[k], g1[k]) <= 1e-6, (k, rel_err(g3[k], g1[k]))
