@@ -207,6 +207,16 @@ int64_t sda_conv_wgrad_work_floats(const sda_wgrad_desc* d);
 int sda_conv_wgrad3_serves(const sda_wgrad_desc* d);
 int64_t sda_conv_wgrad3_work_floats(const sda_wgrad_desc* d);
 int sda_conv_wgrad3(const sda_wgrad_desc* d, void* stream);
+/* OPT-IN tiled route for the stride-2 heads and up-sampling tails (csrc/conv_wgrad3x.hip; additions that keep ABI v14): the design,
+ * descriptor, result layout, slab range and reduction of sda_conv_wgrad3 for two more geometries.  Served: as sda_conv_wgrad3 but
+ *   up2: up_h = up_w = 2, stride 1, ho = 2 hs, wo = 2 ws, loader = ln_mean / ln_rstd alone (no mod, no act_in) or none;
+ *   s2:  stride_h = stride_w = 2, up = 1, hs and ws even, ho = hs / 2, wo = ws / 2, plain loader (no ln, mod, act_in);
+ * a tile within the 160 KiB LDS.  `work` holds sda_conv_wgrad3x_work_floats floats.
+ *   sda_conv_wgrad3x_serves: 1 when the launch is in the served set, else 0 (planning only, nothing is launched)
+ *   sda_conv_wgrad3x: SDA_E_UNSUPPORTED outside the served set (run sda_conv_wgrad3 or sda_conv_wgrad) */
+int sda_conv_wgrad3x_serves(const sda_wgrad_desc* d);
+int64_t sda_conv_wgrad3x_work_floats(const sda_wgrad_desc* d);
+int sda_conv_wgrad3x(const sda_wgrad_desc* d, void* stream);
 /* Gradient of the modulation rows (sda/nn.py:28 ``x + project(y)`` before the LayerNorm): spatial sums of the cotangent at the
  * LayerNorm's input.  x, y: planar [n][c][hw]; out[i * out_sn + ch] (+)= sum_pix (x - y)[i][ch][pix] (y = NULL: x alone), or
  * with sum_images = 1 (a time embedding shared by all images) out[ch] (+)= sum_i sum_pix, images summed in order.

@@ -266,6 +266,9 @@ SIGNATURES = {
     'sda_conv_wgrad3_serves': (c_int, [POINTER(WgradDesc)]),
     'sda_conv_wgrad3_work_floats': (c_int64, [POINTER(WgradDesc)]),
     'sda_conv_wgrad3': (c_int, [POINTER(WgradDesc), c_void_p]),
+    'sda_conv_wgrad3x_serves': (c_int, [POINTER(WgradDesc)]),
+    'sda_conv_wgrad3x_work_floats': (c_int64, [POINTER(WgradDesc)]),
+    'sda_conv_wgrad3x': (c_int, [POINTER(WgradDesc), c_void_p]),
     'sda_plane_sum': (c_int, [c_fp, c_fp, c_int, c_int, c_int64, c_fp, c_int64, c_int, c_int, c_void_p]),
     'sda_conv_igemm_lds_bytes': (c_int64, [POINTER(ConvDesc)]),
     'sda_pack_conv_weight': (c_int, [c_fp, c_int, c_int, c_int, c_int, c_int, c_int, c_fp, c_int, c_int, c_void_p]),

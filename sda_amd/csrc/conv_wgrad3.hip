@@ -25,31 +25,7 @@
 //
 // Index arithmetic is in __host__ __device__ helpers; the emulator at the bottom (libsda_emu.so, tests only) replays the planner,
 // the staging walk and maps (halo, wrap, zero pad), the tap offsets, the MFMA lane maps and the reduction order on the CPU.
-#include "conv_wgrad.hpp"
-
-#define WG3_THREADS 256
-#define WG3_CI 32                 // input channels per workgroup
-#define WG3_Q 128                 // target positions (pad columns included) per stage
-#define WG3_MAX_SLABS 256
-#define WG3_TARGET_BLOCKS 512     // two workgroups on each of 256 CUs
-#define WG3_LDS_MAX (160 * 1024)
-
-struct Wg3Geom {
-    int H, W, W2;        // image size, row pitch W + 2 of both tiles
-    int R, nrb;          // rows per stage, row blocks per image
-    int S;               // stages = n * nrb
-    int per, slabs;      // stages per slab
-    int mt, bm;          // cout tile = 32 mt
-    int n_ct, n_cit;     // cout tiles, cin tiles
-    int q4;              // K extent of a stage: R * W2 rounded up to 4
-    int gp, vp;          // LDS channel pitches (floats) of the g and V tiles
-    int lds_bytes;
-    int grid;
-};
-
-__host__ __device__ inline int wg3_pitch(int need) {          // smallest pitch >= need that is 2 (mod 32)
-    return (need + 29) / 32 * 32 + 2;
-}
+#include "conv_wgrad3.hpp"
 
 // -> SDA_OK and the plan, SDA_E_UNSUPPORTED outside the served set, SDA_E_BADARG as the general planner
 static int wg3_plan(const sda_wgrad_desc* wd, Wg3Geom* t, WgradGeom* g) {
@@ -105,47 +81,6 @@ static int wg3_plan(const sda_wgrad_desc* wd, Wg3Geom* t, WgradGeom* g) {
     return SDA_OK;
 }
 
-// ---------------------------------------------------------------- index helpers (host + device)
-
-// D-fragment row of accumulator register r for v_mfma_f32_16x16x4_f32 (col = lane & 15)
-__host__ __device__ inline int wg3_mfma_row(int r, int lane) { return 4 * (lane >> 4) + r; }
-
-// workgroup b -> (slab, cout tile, cin tile)
-__host__ __device__ inline void wg3_decode_block(const Wg3Geom& t, int b, int& slab, int& ct, int& cit) {
-    cit = b % t.n_cit;
-    int r = b / t.n_cit;
-    ct = r % t.n_ct;
-    slab = r / t.n_ct;
-}
-
-// The staging walk: thread tid visits the elements tid, tid + 256, ... of a [channel][row][col] tile in that order; the
-// decomposition of the step is formed once, the walk itself is adds and compares.
-struct Wg3Walk {
-    int cols, rows;
-    int dcol, drow, dch;
-    int col, row, ch;
-};
-__host__ __device__ inline Wg3Walk wg3_walk_begin(int tid, int cols, int rows) {
-    Wg3Walk w;
-    w.cols = cols; w.rows = rows;
-    const int units = WG3_THREADS / cols;
-    w.dcol = WG3_THREADS - units * cols;
-    w.dch = units / rows;
-    w.drow = units - w.dch * rows;
-    w.col = tid % cols;
-    const int u = tid / cols;
-    w.ch = u / rows;
-    w.row = u - w.ch * rows;
-    return w;
-}
-__host__ __device__ inline void wg3_walk_next(Wg3Walk& w) {
-    w.col += w.dcol;
-    if (w.col >= w.cols) { w.col -= w.cols; ++w.row; }
-    w.row += w.drow;
-    if (w.row >= w.rows) { w.row -= w.rows; ++w.ch; }
-    w.ch += w.dch;
-}
-
 // element (row, col) of channel ci of the staged input tile of stage (n, y0): V(n, ci, y0 - 1 + row, col - 1), wrapped or zero-padded
 __host__ __device__ inline float wg3_stage_v(const sda_conv_desc& d, const Wg3Geom& t, int n, int y0, int ci, int row, int col) {
     int y = y0 - 1 + row, x = col - 1;                        // y in [-1, H + R), x in [-1, W]
@@ -158,13 +93,6 @@ __host__ __device__ inline float wg3_stage_v(const sda_conv_desc& d, const Wg3Ge
         return 0.f;
     }
     return wgrad_load_src(d, n, ci, y, x);
-}
-
-// element (row, col) of channel co of the staged cotangent tile: zero in the two pad columns and below the image
-__host__ __device__ inline float wg3_stage_g(const sda_wgrad_desc& wd, const Wg3Geom& t, int n, int y0, int co, int row, int col) {
-    const int y = y0 + row;
-    if (col >= t.W || y >= t.H) return 0.f;
-    return wd.g[(((int64_t)n * wd.conv.cout + co) * t.H + y) * t.W + col];
 }
 
 // LDS offset of tap (ky, kx) relative to the position index

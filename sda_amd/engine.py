@@ -842,7 +842,7 @@ class ParamGrads:
         self.gmod = torch.empty_like(mod_all) if (need_mod and mod_all is not None) else None
         self._mod_written = set()
         from . import training
-        self.route = training.wgrad_route()                 # 'tiled': the block convolutions on csrc/conv_wgrad3.hip
+        self.route = training.wgrad_route()                 # 'tiled': the block convolutions on csrc/conv_wgrad3.hip; 'tiled_ht': heads and tails too
 
     def conv(self, cc: _ConvCache, desc, g: Tensor):
         hit = self.conv_grads.get(id(cc))

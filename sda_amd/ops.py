@@ -317,14 +317,16 @@ def wgrad_flops(conv: ConvDesc) -> float:
     return 2.0 * conv.n * conv.ho * conv.wo * conv.cout * (conv.cx + conv.cctx) * conv.kh * conv.kw
 
 
-WGRAD_ROUTES = ('general', 'tiled')
+WGRAD_ROUTES = ('general', 'tiled', 'tiled_ht')
 
 
 def conv_wgrad(conv: ConvDesc, g: Tensor, dw: Tensor, db: Optional[Tensor], accumulate: bool, slabs: int = 0, route: str = 'general'):
     """dw (+)= the weight gradient of the layer ``conv`` describes for the output cotangent ``g``; db (+)= its bias gradient.
-    route 'tiled': the tiled 3 x 3 kernel (csrc/conv_wgrad3.hip) where sda_conv_wgrad3_serves says so, the general kernel otherwise."""
+    route 'tiled': the tiled 3 x 3 kernel (csrc/conv_wgrad3.hip) where sda_conv_wgrad3_serves says so, the general kernel otherwise;
+    route 'tiled_ht': that, then the heads' and tails' kernel (csrc/conv_wgrad3x.hip) where sda_conv_wgrad3x_serves says so, then the
+    general kernel."""
     if route not in WGRAD_ROUTES:
-        raise ValueError(f"conv_wgrad route {route!r} (expected 'general' or 'tiled')")
+        raise ValueError(f"conv_wgrad route {route!r} (expected 'general', 'tiled' or 'tiled_ht')")
     _dev(g, dw, db)
     if not g.is_contiguous() or tuple(g.shape) != (conv.n, conv.cout, conv.ho, conv.wo):
         raise _lib.SdaHipError(f'conv_wgrad: cotangent must be planar contiguous {(conv.n, conv.cout, conv.ho, conv.wo)}, got {tuple(g.shape)}')
@@ -333,8 +335,10 @@ def conv_wgrad(conv: ConvDesc, g: Tensor, dw: Tensor, db: Optional[Tensor], accu
         raise _lib.SdaHipError('conv_wgrad: dw / db do not match the layer')
     lib = _lib.load()
     d = wgrad_desc(conv, g, dw, db, accumulate, slabs)
-    if route == 'tiled' and lib.sda_conv_wgrad3_serves(ctypes.byref(d)):
+    if route != 'general' and lib.sda_conv_wgrad3_serves(ctypes.byref(d)):
         planner, launch, name, family = lib.sda_conv_wgrad3_work_floats, lib.sda_conv_wgrad3, 'sda_conv_wgrad3', 'wgrad3'
+    elif route == 'tiled_ht' and lib.sda_conv_wgrad3x_serves(ctypes.byref(d)):
+        planner, launch, name, family = lib.sda_conv_wgrad3x_work_floats, lib.sda_conv_wgrad3x, 'sda_conv_wgrad3x', 'wgrad3x'
     else:
         planner, launch, name, family = lib.sda_conv_wgrad_work_floats, lib.sda_conv_wgrad, 'sda_conv_wgrad', 'wgrad'
     floats = planner(ctypes.byref(d))

@@ -24,7 +24,10 @@ kernels of the samplers stay sampling-only.  ``sda_amd.utils.loop`` switches bot
 
 A third opt-in, ``parameter_gradients(wgrad='tiled')`` (or ``enable(wgrad='tiled')``), sends the weight gradients of the 3 x 3,
 stride-1 block convolutions (36 of the 42 launches of a Kolmogorov step) to the tiled kernel csrc/conv_wgrad3.hip; heads, tails, 1-D
-nets and anything else outside its served set stay on the general kernel.  The default ``'general'`` is bitwise what it always was.
+nets and anything else outside its served set stay on the general kernel.  ``wgrad='tiled_ht'`` (heads and tails) is that route and,
+beside it, csrc/conv_wgrad3x.hip for the 3 x 3 stride-2 heads and the up-sampling tails with channel counts in multiples of 32 (4 more
+of the 42 launches); the first head (context plane) and the last tail stay on the general kernel.  The default ``'general'`` is bitwise
+what it always was, and so is ``'tiled'``.
 
 :class:`AdamW` is the optimizer step of this route as one launch (csrc/optim.hip) that keeps the ResMLP weight slabs packed."""
 import contextlib
@@ -41,7 +44,7 @@ SUPPORTED_MLP = ('ScoreNet (TimeEmbedding + ResMLP of Linear layers and LayerNor
                  'activation, one LayerNorm eps), alone or as the kernel of MCScoreNet, on the device, '
                  "with the fp32 multiply (ops.MULTIPLY == 'f32'), under parameter_gradients(mlp=True)")
 
-WGRAD_ROUTES = ('general', 'tiled')
+WGRAD_ROUTES = ('general', 'tiled', 'tiled_ht')
 
 _enabled = False
 _mlp = False
@@ -51,14 +54,15 @@ _local = threading.local()
 
 def _check_route(wgrad: str) -> str:
     if wgrad not in WGRAD_ROUTES:
-        raise ValueError(f"wgrad route {wgrad!r} (expected 'general' or 'tiled')")
+        raise ValueError(f"wgrad route {wgrad!r} (expected 'general', 'tiled' or 'tiled_ht')")
     return wgrad
 
 
 def enable(mlp: bool = False, wgrad: str = 'general') -> None:
     """Form parameter gradients in the U-Net backward from now on; ``mlp=True``: in the ScoreNet / ResMLP backward as well.
     ``wgrad='tiled'``: the 3 x 3 block convolutions' weight gradients on the tiled kernel (csrc/conv_wgrad3.hip) where it serves the
-    launch; every other layer, and everything under the default ``'general'``, on the general kernel."""
+    launch; ``wgrad='tiled_ht'``: also the stride-2 heads and up-sampling tails on theirs (csrc/conv_wgrad3x.hip); every other layer,
+    and everything under the default ``'general'``, on the general kernel."""
     global _enabled, _mlp, _wgrad
     route = _check_route(wgrad)
     _enabled, _mlp, _wgrad = True, bool(mlp), route
@@ -80,14 +84,15 @@ def mlp_enabled() -> bool:
 
 
 def wgrad_route() -> str:
-    """The weight-gradient route of the convolutions: 'general' (default) or 'tiled' (the third opt-in)."""
+    """The weight-gradient route of the convolutions: 'general' (default), 'tiled' or 'tiled_ht' (the third opt-in)."""
     return _wgrad
 
 
 @contextlib.contextmanager
 def parameter_gradients(on: bool = True, mlp: bool = False, wgrad: str = 'general'):
     """Switch parameter gradients on (or off) inside the block, those of ScoreNet / ResMLP with ``mlp=True``, the block convolutions'
-    weight gradients on the tiled kernel with ``wgrad='tiled'``; the previous state of all three switches is restored on exit."""
+    weight gradients on the tiled kernel with ``wgrad='tiled'``, the heads' and tails' as well with ``wgrad='tiled_ht'``; the previous
+    state of all three switches is restored on exit."""
     global _enabled, _mlp, _wgrad
     route = _check_route(wgrad)
     prev = (_enabled, _mlp, _wgrad)

@@ -84,7 +84,8 @@ def loop(sde: 'VPSDE', trainset, validset, epochs: int = 256, batch_size: int = 
     the mean training loss, the mean validation loss (under ``no_grad``) and the learning rate the epoch ran with.  Parameter
     gradients are switched on (``sda_amd.training.parameter_gradients(mlp=True)``: the U-Nets and ScoreNet) while the training steps run.
     ``fused=True`` takes ``sda_amd.training.AdamW`` (one launch per step, the ResMLP weight slabs stay packed) for ``torch.optim.AdamW``;
-    ``wgrad='tiled'`` sends the block convolutions' weight gradients to the tiled kernel (``sda_amd.training``)."""
+    ``wgrad='tiled'`` sends the block convolutions' weight gradients to the tiled kernel, ``wgrad='tiled_ht'`` the stride-2 heads' and
+    up-sampling tails' as well (``sda_amd.training``)."""
     from torch.utils.data import DataLoader
     loaders = [DataLoader(ds, batch_size=batch_size, shuffle=True) for ds in (trainset, validset)]
     if optimizer != 'AdamW':

@@ -1,6 +1,6 @@
 """Training-step benchmark of the opt-in parameter-gradient route (sda_amd.training).  bench.py (sampling) is not involved.
 
-    python tools/train_bench.py [--steps 10] [--warmup 3] [--wgrad general|tiled|both] [--blocks 5] [--out profiles/train_bench.json]
+    python tools/train_bench.py [--steps 10] [--warmup 3] [--wgrad general|tiled|tiled_ht|both|all] [--blocks 5] [--out profiles/train_bench.json]
 
 Reports, per configuration (Kolmogorov training net: LocalScoreUNet (96, 192, 384) x (3, 3, 3), embedding 64, batch 32 of
 10 + 1 x 64 x 64; Lorenz global net: 1-D (64,) x (3,), batch 64 x 3 x 32):
@@ -8,14 +8,18 @@ Reports, per configuration (Kolmogorov training net: LocalScoreUNet (96, 192, 38
   * the same step with the oracle's functional net in fp32 under torch autograd on the same GPU (the stated baseline);
   * per-family kernel time of one step (ops.ConvProfile): forward convolutions, input-VJP convolutions, weight gradients,
     LayerNorm / modulation reductions, and the share of the torch-autograd modulation / time-embedding GEMMs;
-and, for the Kolmogorov block shapes (96 ch @ 64^2, 192 @ 32^2, 384 @ 16^2, batch 32), the weight-gradient kernel's TFLOP/s and
-its fraction of the fp32 matrix peak (256 CUs x 4 SIMDs x 256 flop/clk x 2.4 GHz = 157.3 TFLOP/s).
+and, for the Kolmogorov block shapes (96 ch @ 64^2, 192 @ 32^2, 384 @ 16^2, batch 32) and its four head and tail shapes (stride-2
+heads 96 -> 192 @ 64^2 and 192 -> 384 @ 32^2, up-sampling tails 384 -> 192 @ 16^2 and 192 -> 96 @ 32^2), the weight-gradient kernel's
+TFLOP/s and its fraction of the fp32 matrix peak (256 CUs x 4 SIMDs x 256 flop/clk x 2.4 GHz = 157.3 TFLOP/s).
 
 --wgrad selects the weight-gradient route of the block convolutions (sda_amd.training: 'general' = csrc/conv_wgrad.hip everywhere,
-'tiled' = csrc/conv_wgrad3.hip where it serves the launch).  --wgrad both times the block shapes and the Kolmogorov step (and the
+'tiled' = csrc/conv_wgrad3.hip where it serves the launch, 'tiled_ht' = that and csrc/conv_wgrad3x.hip for the heads and tails).
+--wgrad both times the block shapes and the Kolmogorov step (and the
 oracle's eager step) for the two routes ALTERNATING in one process, block by block (the scheme of tools/mlp_train_bench.py): per
 block warm-up steps, then `steps` steps between two events; reported are the median of `blocks` blocks and the fastest and slowest
-block.  The tiled route earns its place on a shape only where its median is below the general route's FASTEST block."""
+block.  The tiled route earns its place on a shape only where its median is below the general route's FASTEST block.  --wgrad all
+does the same for general, tiled and tiled_ht (and the eager step), the head and tail shapes included: there tiled_ht is held to the
+general route's fastest block per shape, and its step to the tiled route's fastest block."""
 import argparse
 import json
 import os
@@ -33,6 +37,7 @@ from sda_amd import ops, training  # noqa: E402
 from sda_amd.score import VPSDE  # noqa: E402
 
 PEAK_FP32_MATRIX = 157.3e12
+WGRAD_FAMILIES = ('wgrad', 'wgrad3', 'wgrad3x')
 
 
 def _timed(fn, steps, warmup):
@@ -119,7 +124,7 @@ def family_profile(sde, x, wgrad='general'):
         ops.conv_profile = None
     fam = {}
     for i, (a, b, flops, f) in enumerate(prof.records):
-        key = f if f in ('wgrad', 'wgrad3') else ('forward.' if i < fwd_n else 'input_vjp.') + f
+        key = f if f in WGRAD_FAMILIES else ('forward.' if i < fwd_n else 'input_vjp.') + f
         r = fam.setdefault(key, dict(launches=0, ms=0.0, tflop=0.0))
         r['launches'] += 1
         r['ms'] += a.elapsed_time(b)
@@ -134,7 +139,7 @@ def family_profile(sde, x, wgrad='general'):
         r['ms'] = round(r['ms'], 4)
         if 'tflop' in r:
             r['tflop_s'] = round(r['tflop'] / max(r['ms'], 1e-9) * 1e3, 2)
-    for wg in (fam.get('wgrad'), fam.get('wgrad3')):
+    for wg in (fam.get(f) for f in WGRAD_FAMILIES):
         if wg:
             wg['fraction_of_fp32_peak'] = round(wg['tflop_s'] * 1e12 / PEAK_FP32_MATRIX, 3)
     return dict(families=fam, loss_ms=round(e0.elapsed_time(e1), 3), backward_ms=round(e1.elapsed_time(e2), 3))
@@ -169,50 +174,84 @@ def _stat(ms):
                 blocks_ms=[round(v, 4) for v in ms])
 
 
-def wgrad_shapes(dev, steps, routes=('general',), blocks=1):
-    """The block conv1 weight gradient (modulation + LayerNorm loader, circular) at the three Kolmogorov block shapes."""
+def _block_layer(dev, c, s, n):
+    """A block conv1 (modulation + LayerNorm loader, circular) at c channels, s x s."""
     from sda_amd.ops import make_conv_desc
+    a = torch.randn(n, c, s, s, device=dev)
+    mod = torch.randn(n, c, device=dev)
+    mean = torch.zeros(n * s * s, device=dev)
+    rstd = torch.ones(n * s * s, device=dev)
+    g = torch.randn(n, c, s, s, device=dev)
+    dw = torch.empty(c, c, 3, 3, device=dev)
+    db = torch.empty(c, device=dev)
+    d = make_conv_desc(x_ptr=a.data_ptr(), n=n, cx=c, hs=s, ws=s, x_sc=s * s, x_sy=s, x_sx=1, x_sn_outer=c * s * s, w_ptr=0,
+                       cin_pad=0, cout_pad=0, cout=c, kh=3, kw=3, out_ptr=0, ho=s, wo=s, mt=1, circular=True,
+                       mod_ptr=mod.data_ptr(), mod_sn=c, ln_mean_ptr=mean.data_ptr(), ln_rstd_ptr=rstd.data_ptr())
+    return dict(channels=c, size=s, batch=n), d, g, dw, db, (a, mod, mean, rstd)
+
+
+def _head_tail_layer(dev, kind, cin, cout, s, n):
+    """A stride-2 head (plain loader) or an up-sampling tail (LayerNorm loader) reading cin channels at s x s, circular."""
+    from sda_amd.ops import make_conv_desc
+    so = s // 2 if kind == 'head_s2' else 2 * s
+    a = torch.randn(n, cin, s, s, device=dev)
+    mean = torch.zeros(n * s * s, device=dev)
+    rstd = torch.ones(n * s * s, device=dev)
+    g = torch.randn(n, cout, so, so, device=dev)
+    dw = torch.empty(cout, cin, 3, 3, device=dev)
+    db = torch.empty(cout, device=dev)
+    extra = dict(stride_h=2, stride_w=2) if kind == 'head_s2' else dict(up_h=2, up_w=2, ln_mean_ptr=mean.data_ptr(),
+                                                                         ln_rstd_ptr=rstd.data_ptr())
+    d = make_conv_desc(x_ptr=a.data_ptr(), n=n, cx=cin, hs=s, ws=s, x_sc=s * s, x_sy=s, x_sx=1, x_sn_outer=cin * s * s, w_ptr=0,
+                       cin_pad=0, cout_pad=0, cout=cout, kh=3, kw=3, out_ptr=0, ho=so, wo=so, mt=1, circular=True, **extra)
+    return dict(layer=kind, cin=cin, cout=cout, size=s, out_size=so, batch=n), d, g, dw, db, (a, mean, rstd)
+
+
+BLOCK_SHAPES = ((96, 64), (192, 32), (384, 16))
+HEAD_TAIL_SHAPES = (('head_s2', 96, 192, 64), ('head_s2', 192, 384, 32), ('tail_up', 384, 192, 16), ('tail_up', 192, 96, 32))
+
+
+def wgrad_shapes(dev, steps, routes=('general',), blocks=1, heads_tails=True):
+    """The weight gradient at the three Kolmogorov block shapes (conv1: modulation + LayerNorm loader, circular) and, with
+    ``heads_tails``, at its four head and tail shapes, batch 32.  With several routes: alternating blocks, and per shape whether the
+    median of the route that serves it ('tiled' for the blocks, 'tiled_ht' for heads and tails) is below the general route's fastest
+    block."""
+    layers = [_block_layer(dev, c, s, 32) + ('tiled',) for c, s in BLOCK_SHAPES]
+    if heads_tails:
+        layers += [_head_tail_layer(dev, *spec, 32) + ('tiled_ht',) for spec in HEAD_TAIL_SHAPES]
     rows = []
-    for c, s in ((96, 64), (192, 32), (384, 16)):
-        n = 32
-        a = torch.randn(n, c, s, s, device=dev)
-        mod = torch.randn(n, c, device=dev)
-        mean = torch.zeros(n * s * s, device=dev)
-        rstd = torch.ones(n * s * s, device=dev)
-        g = torch.randn(n, c, s, s, device=dev)
-        dw = torch.empty(c, c, 3, 3, device=dev)
-        db = torch.empty(c, device=dev)
-        d = make_conv_desc(x_ptr=a.data_ptr(), n=n, cx=c, hs=s, ws=s, x_sc=s * s, x_sy=s, x_sx=1, x_sn_outer=c * s * s, w_ptr=0,
-                           cin_pad=0, cout_pad=0, cout=c, kh=3, kw=3, out_ptr=0, ho=s, wo=s, mt=1, circular=True,
-                           mod_ptr=mod.data_ptr(), mod_sn=c, ln_mean_ptr=mean.data_ptr(), ln_rstd_ptr=rstd.data_ptr())
+    for head, d, g, dw, db, _keep, served_by in layers:
         flops = ops.wgrad_flops(d)
         if len(routes) == 1:
             ms = _timed(lambda: ops.conv_wgrad(d, g, dw, db, False, route=routes[0]), steps, 3)
-            rows.append(dict(channels=c, size=s, batch=n, route=routes[0], ms=round(ms, 4), tflop_s=round(flops / ms / 1e9, 2),
+            rows.append(dict(head, route=routes[0], ms=round(ms, 4), tflop_s=round(flops / ms / 1e9, 2),
                              fraction_of_fp32_peak=round(flops / ms / 1e9 * 1e12 / PEAK_FP32_MATRIX, 3)))
             continue
         times = _blocks({r: (lambda r=r: ops.conv_wgrad(d, g, dw, db, False, route=r)) for r in routes}, steps, 3, blocks)
-        row = dict(channels=c, size=s, batch=n)
+        row = dict(head)
         for r in routes:
             st = _stat(times[r])
             st['tflop_s'] = round(flops / st['median_ms'] / 1e9, 2)
             st['fraction_of_fp32_peak'] = round(flops / st['median_ms'] / 1e9 * 1e12 / PEAK_FP32_MATRIX, 3)
             row[r] = st
-        row['general_median_over_tiled_median'] = round(row['general']['median_ms'] / row['tiled']['median_ms'], 3)
-        row['tiled_median_below_general_fastest'] = row['tiled']['median_ms'] < row['general']['fastest_ms']
+        if served_by in routes:
+            row[f'general_median_over_{served_by}_median'] = round(row['general']['median_ms'] / row[served_by]['median_ms'], 3)
+            row[f'{served_by}_median_below_general_fastest'] = row[served_by]['median_ms'] < row['general']['fastest_ms']
         rows.append(row)
     return rows
 
 
-def kolmogorov_both(cfg, dev, steps, warmup, blocks):
-    """The Kolmogorov training step on the two weight-gradient routes and the oracle's eager step, alternating block by block."""
-    fns = {r: hip_step(cfg, dev, r)[0] for r in ('general', 'tiled')}
+def kolmogorov_routes(cfg, dev, steps, warmup, blocks, routes=('general', 'tiled')):
+    """The Kolmogorov training step on the weight-gradient routes and the oracle's eager step, alternating block by block."""
+    fns = {r: hip_step(cfg, dev, r)[0] for r in routes}
     fns['eager'] = oracle_step(cfg, dev)
     times = _blocks(fns, steps, warmup, blocks)
     out = {k: _stat(v) for k, v in times.items()}
-    out['tiled_over_eager'] = round(out['eager']['median_ms'] / out['tiled']['median_ms'], 3)
-    out['general_over_eager'] = round(out['eager']['median_ms'] / out['general']['median_ms'], 3)
+    for r in routes:
+        out[f'{r}_over_eager'] = round(out['eager']['median_ms'] / out[r]['median_ms'], 3)
     out['tiled_step_below_eager'] = out['tiled']['median_ms'] < out['eager']['median_ms']
+    if 'tiled_ht' in routes:
+        out['tiled_ht_median_below_tiled_fastest'] = out['tiled_ht']['median_ms'] < out['tiled']['fastest_ms']
     return out
 
 
@@ -221,18 +260,19 @@ def main():
     ap.add_argument('--steps', type=int, default=10)
     ap.add_argument('--warmup', type=int, default=3)
     ap.add_argument('--out', default=None)
-    ap.add_argument('--wgrad', choices=('general', 'tiled', 'both'), default='general')
-    ap.add_argument('--blocks', type=int, default=5, help='--wgrad both: blocks per route (median, fastest and slowest are reported)')
+    ap.add_argument('--wgrad', choices=('general', 'tiled', 'tiled_ht', 'both', 'all'), default='general')
+    ap.add_argument('--blocks', type=int, default=5, help='--wgrad both / all: blocks per route (median, fastest and slowest are reported)')
     args = ap.parse_args()
     dev = torch.device('cuda:0')
-    route = 'tiled' if args.wgrad in ('tiled', 'both') else 'general'
+    route = {'both': 'tiled', 'all': 'tiled_ht'}.get(args.wgrad, args.wgrad)
+    compared = {'both': ('general', 'tiled'), 'all': ('general', 'tiled', 'tiled_ht')}.get(args.wgrad)
     result = dict(device=torch.cuda.get_device_name(dev), steps=args.steps, warmup=args.warmup, wgrad=args.wgrad, configs={})
-    if args.wgrad == 'both':
+    if compared:
         result['blocks'] = args.blocks
-        result['wgrad_block_shapes'] = wgrad_shapes(dev, args.steps, ('general', 'tiled'), args.blocks)
+        result['wgrad_block_shapes'] = wgrad_shapes(dev, args.steps, compared, args.blocks, heads_tails='tiled_ht' in compared)
         print(json.dumps({'wgrad_block_shapes': result['wgrad_block_shapes']}), flush=True)
     for cfg in configs(dev):
-        if args.wgrad == 'both' and cfg['name'] != 'kolmogorov_train':
+        if compared and cfg['name'] != 'kolmogorov_train':
             continue                                     # (1-D nets keep the general kernel under either setting)
         step, sde, x = hip_step(cfg, dev, route)
         ms = _timed(step, args.steps, args.warmup)
@@ -243,11 +283,11 @@ def main():
             batch=cfg['batch'], shape=list(cfg['shape']), ms_per_step=round(ms, 3), oracle_fp32_autograd_ms_per_step=round(base_ms, 3),
             speedup_vs_oracle=round(base_ms / ms, 3), modulation_autograd_ms=round(mod_ms, 4),
             modulation_share_of_step=round(mod_ms / ms, 4), profile=prof)
-        if args.wgrad == 'both':
+        if compared:
             result['configs'][cfg['name']]['profiled_route'] = route
-            result['configs'][cfg['name']]['routes'] = kolmogorov_both(cfg, dev, args.steps, args.warmup, args.blocks)
+            result['configs'][cfg['name']]['routes'] = kolmogorov_routes(cfg, dev, args.steps, args.warmup, args.blocks, compared)
         print(json.dumps({cfg['name']: result['configs'][cfg['name']]}), flush=True)
-    if args.wgrad != 'both':
+    if not compared:
         result['wgrad_block_shapes'] = wgrad_shapes(dev, args.steps, (args.wgrad,))
     result['time'] = time.strftime('%Y-%m-%dT%H:%M:%S')
     line = json.dumps(result)
