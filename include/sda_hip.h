@@ -317,6 +317,74 @@ int sda_net1d_fwd_fused(const sda_net1d_desc* d, const sda_net1d_fuse* f, void* 
 int sda_net1d_bwd_fused(const sda_net1d_desc* d, const sda_net1d_fuse* f, void* stream);
 int sda_net1d_tiles(const sda_net1d_desc* d);          /* tiles per sequence of the launch serving `d` (host, no launch) */
 
+/* Parameter gradients of such a network (opt-in training, sda_amd/training.py with net1d = True; csrc/net1d_train.hip; additive
+ * to ABI v14).  A training step is one forward launch, three backward launches and, after the optimizer, one pack launch.
+ *
+ * sda_net1d_fwd_train: sda_net1d_fwd with saves -- the same out, a_save, z_save, mean_save, rstd_save bit for bit (all four saves
+ *   are required when nblocks > 0) -- that also writes the tail convolution's input (the last block's output) to
+ *   tail_in[n][c][len].  g_save / mod_part are not read.
+ * sda_net1d_bwd_train: sda_net1d_bwd -- the same input gradient bit for bit -- that also stores the cotangent at every
+ *   convolution's output as planes [n][c][len] in g_save, slot s at g_save + s * g_stride (g_stride >= n * c * len):
+ *     s = 2 k: g at entry to block k (conv2's output cotangent);  s = 2 k + 1: q = conv2^T(g) act'(z) (conv1's);
+ *     s = 2 nblocks: the stream cotangent in front of head^T (the head's).  The tail's output cotangent is net.x itself.
+ *   and the modulation-row gradient of block k, sum over positions of rstd (gh - mean_c(gh) - xhat mean'_c(gh xhat)), as per-tile
+ *   partial sums in the fixed slot mod_part[k][n][tile][c], tile < mod_tiles = sda_net1d_tiles(&net) (no atomics; every slot of a
+ *   launch is written).  mod_part is required when nblocks > 0, g_save always; tail_in is not read. */
+typedef struct sda_net1d_train_desc {
+    sda_net1d_desc net;
+    float* tail_in;
+    float* g_save; int64_t g_stride;
+    float* mod_part; int32_t mod_tiles;
+} sda_net1d_train_desc;
+int sda_net1d_fwd_train(const sda_net1d_train_desc* t, void* stream);
+int sda_net1d_bwd_train(const sda_net1d_train_desc* t, void* stream);
+
+/* sda_net1d_wgrad: the weight and bias gradients of all 2 + 2 nblocks convolutions in ONE launch on the fp32 matrix cores
+ * (v_mfma_f32_16x16x4_f32) and ONE reduction launch behind it; bitwise reproducible.  For convolution v (FORWARD order: head,
+ * (conv1, conv2) of block 0 .. nblocks - 1, tail)
+ *     dw[v][co][ci][tap] = sum_{n, x} G[n][co][x] U[n][ci][x + tap - 1],   db[v][co] = sum_{n, x} G[n][co][x]
+ * (x + tap - 1 outside the sequence: zero, or wrapped when net.circular) in torch's unpadded Conv1d layouts (cout, cin, 3) / (cout).
+ * U is rebuilt from what sda_net1d_fwd_train saved -- head: net.x through (x_sn, x_sc, x_sx); conv1 of block k:
+ * (a_k + mod_k - mean_k) rstd_k; conv2: act(z_k); tail: tail_in -- and G is read from g_save (see sda_net1d_bwd_train), the tail's
+ * from gout through its strides.  The contraction axis (n len) is cut into `slabs` contiguous ranges (0: the planner's count, a
+ * function of the shapes only; 1 .. 64 forces one, capped by the number of 32-row stages); workgroup (slab, convolution, column
+ * tile) writes its unreduced 64 x 128 tile to work[sda_net1d_wgrad_work_floats(d)], the reduction sums the slabs in slab order.
+ * It also finishes the modulation gradients: dmod[k][i * dmod_sn + ch] = sum over tiles (in tile order) of mod_part[k][i][tile][ch]
+ * per image i when net.mod_sn != 0, or one row dmod[k][ch] summed over images in image order (tiles inside) when net.mod_sn == 0.
+ * A NULL dw[v] / db[v] / dmod[k] skips that output (frozen parameters); nothing outside the unpadded extents is written.
+ * Of `net`: the shapes, circular, act, x and its strides, mod / mod_sn, the four saves and their strides are read; w, bias, out are not.
+ * Served: what sda_net1d_fwd serves, n len < 2^31.  SDA_E_UNSUPPORTED / SDA_E_BADARG as its siblings.
+ * sda_net1d_wgrad_slabs / _work_floats: planning only (host): the slab count / the floats of `work` of that launch (< 0: error). */
+typedef struct sda_net1d_wgrad_desc {
+    sda_net1d_desc net;
+    const float* tail_in;
+    const float* g_save; int64_t g_stride;
+    const float* gout; int64_t gout_sn, gout_sc, gout_sx;
+    const float* mod_part; int32_t mod_tiles;
+    float* dw[2 + 2 * SDA_NET1D_MAXB];
+    float* db[2 + 2 * SDA_NET1D_MAXB];
+    float* dmod[SDA_NET1D_MAXB]; int64_t dmod_sn;
+    float* work;
+    int32_t slabs;
+} sda_net1d_wgrad_desc;
+int sda_net1d_wgrad(const sda_net1d_wgrad_desc* d, void* stream);
+int sda_net1d_wgrad_slabs(const sda_net1d_wgrad_desc* d);
+int64_t sda_net1d_wgrad_work_floats(const sda_net1d_wgrad_desc* d);
+
+/* sda_net1d_pack: every packing the whole-net kernels read, in ONE launch, from the 2 + 2 nblocks torch-layout weights (cout, cin, 3)
+ * and biases (cout; NULL = none) given in FORWARD order (head cin -> c, the blocks' c -> c, tail c -> cout):
+ *   wf:   the forward buffer of sda_net1d_fwd ([3][64][64] per convolution, forward order);
+ *   wb:   the backward-data buffer of sda_net1d_bwd (transposed packings in its execution order; head^T keeps cin_keep input channels);
+ *   bias: [2 + 2 nblocks][64] zero-padded rows, forward order.
+ * A pure permutation: the bytes sda_pack_conv_weight (k_pad = m_pad = 64) and a bias copy produce.  NULL wf / wb / bias: not written. */
+typedef struct sda_net1d_pack_desc {
+    int32_t nblocks, cin, c, cout, cin_keep;
+    const float* w[2 + 2 * SDA_NET1D_MAXB];
+    const float* b[2 + 2 * SDA_NET1D_MAXB];
+    float* wf; float* wb; float* bias;
+} sda_net1d_pack_desc;
+int sda_net1d_pack(const sda_net1d_pack_desc* p, void* stream);
+
 /* Everything a predictor-corrector step needs before its score evaluations, in ONE launch (sda/score.py:250-253 scalars,
  * TimeEmbedding score.py:15-35, every block's `project` nn.py:132-135), for up to two time values:
  *   table != NULL: row = table[istep[0]] = {t, t - dt, r, c1, sigma(t - dt)} (the host-evaluated schedule of VPSDE.sample);

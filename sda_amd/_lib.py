@@ -112,6 +112,40 @@ class Net1dDesc(Structure):
     ]
 
 
+class Net1dTrainDesc(Structure):
+    """Mirror of `struct sda_net1d_train_desc` (include/sda_hip.h)."""
+    _fields_ = [('net', Net1dDesc), ('tail_in', c_fp), ('g_save', c_fp), ('g_stride', c_int64), ('mod_part', c_fp), ('mod_tiles', c_int32)]
+
+
+NET1D_MAXV = 2 + 2 * NET1D_MAXB
+
+
+class Net1dWgradDesc(Structure):
+    """Mirror of `struct sda_net1d_wgrad_desc` (include/sda_hip.h)."""
+    _fields_ = [
+        ('net', Net1dDesc),
+        ('tail_in', c_fp),
+        ('g_save', c_fp), ('g_stride', c_int64),
+        ('gout', c_fp), ('gout_sn', c_int64), ('gout_sc', c_int64), ('gout_sx', c_int64),
+        ('mod_part', c_fp), ('mod_tiles', c_int32),
+        ('dw', c_fp * NET1D_MAXV),
+        ('db', c_fp * NET1D_MAXV),
+        ('dmod', c_fp * NET1D_MAXB), ('dmod_sn', c_int64),
+        ('work', c_fp),
+        ('slabs', c_int32),
+    ]
+
+
+class Net1dPackDesc(Structure):
+    """Mirror of `struct sda_net1d_pack_desc` (include/sda_hip.h)."""
+    _fields_ = [
+        ('nblocks', c_int32), ('cin', c_int32), ('c', c_int32), ('cout', c_int32), ('cin_keep', c_int32),
+        ('w', c_fp * NET1D_MAXV),
+        ('b', c_fp * NET1D_MAXV),
+        ('wf', c_fp), ('wb', c_fp), ('bias', c_fp),
+    ]
+
+
 MLP_MAXG = 32
 
 
@@ -254,6 +288,12 @@ SIGNATURES = {
     'sda_net1d_fwd_fused': (c_int, [POINTER(Net1dDesc), POINTER(Net1dFuse), c_void_p]),
     'sda_net1d_bwd_fused': (c_int, [POINTER(Net1dDesc), POINTER(Net1dFuse), c_void_p]),
     'sda_net1d_tiles': (c_int, [POINTER(Net1dDesc)]),
+    'sda_net1d_fwd_train': (c_int, [POINTER(Net1dTrainDesc), c_void_p]),
+    'sda_net1d_bwd_train': (c_int, [POINTER(Net1dTrainDesc), c_void_p]),
+    'sda_net1d_wgrad': (c_int, [POINTER(Net1dWgradDesc), c_void_p]),
+    'sda_net1d_wgrad_slabs': (c_int, [POINTER(Net1dWgradDesc)]),
+    'sda_net1d_wgrad_work_floats': (c_int64, [POINTER(Net1dWgradDesc)]),
+    'sda_net1d_pack': (c_int, [POINTER(Net1dPackDesc), c_void_p]),
     'sda_step1d_prologue': (c_int, [c_fp, c_int, c_fp, c_fp, c_int, c_int, c_float, c_float, c_int, c_fp, c_int, c_fp, c_fp, c_int,
                                     c_fp, c_fp, c_int, c_fp, c_fp, c_int, c_fp, c_fp, c_fp, c_void_p]),
     'sda_pc_correct_keyed': (c_int, [c_fp, c_fp, c_int, c_int64, c_fp, c_int, c_float, c_float, c_fp, c_uint64, c_int64, c_fp, c_int64,

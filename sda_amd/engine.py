@@ -324,8 +324,9 @@ class UNetEngine:
             hit = pg.conv_grads.get(id(cc))
             if hit is None:
                 continue
-            by_id[id(cc.conv.weight)] = hit[0].view(cc.conv.weight.shape)
-            if cc.conv.bias is not None:
+            if hit[0] is not None:                       # (None: frozen on the whole-net route, no gradient was formed)
+                by_id[id(cc.conv.weight)] = hit[0].view(cc.conv.weight.shape)
+            if cc.conv.bias is not None and hit[1] is not None:
                 by_id[id(cc.conv.bias)] = hit[1]
         return [by_id.get(id(p)) if p.requires_grad else None for p in params]
 
@@ -462,6 +463,36 @@ class UNetEngine:
             return None
         return dict(lev=lev, blocks=blocks)
 
+    def net1d_train_plan(self, src: Source, device) -> Optional[dict]:
+        """The plan of a training step on the whole-net kernels (csrc/net1d_train.hip), or None: the switch is off
+        (training.net1d_enabled), the kernel declines the net, or the batch's activations do not fit the keep budget in one piece --
+        the chunked / recompute route stays on the per-layer kernels, whose gradient buffers accumulate over chunks."""
+        from . import training
+        if not training.net1d_enabled():
+            return None
+        plan = self.net1d_plan(src)
+        if plan is None or self.chunk_size(src.n, src.hs, src.ws, True, device, KEEP_HBM_FRACTION) < src.n:
+            return None
+        return plan
+
+    def _net1d_pack(self, plan, convs, backward: bool, cin_keep: int, w: Tensor, bias: Optional[Tensor]):
+        """The forward buffer + bias rows, or the backward-data buffer, of every convolution in ONE launch (sda_net1d_pack)."""
+        from ._lib import Net1dPackDesc
+        lev = plan['lev']
+        p = Net1dPackDesc()
+        p.nblocks, p.cin, p.c, p.cout, p.cin_keep = len(plan['blocks']), lev.head.cin, lev.C, lev.tail.cout, cin_keep
+        keep = []
+        for v, cc in enumerate(convs):
+            wt = cc.conv.weight.detach().contiguous()
+            bt = None if cc.conv.bias is None else cc.conv.bias.detach().contiguous()
+            keep += [wt, bt]
+            p.w[v], p.b[v] = wt.data_ptr(), None if bt is None else bt.data_ptr()
+        if backward:
+            p.wb = w.data_ptr()
+        else:
+            p.wf, p.bias = w.data_ptr(), bias.data_ptr()
+        ops.net1d_pack(p)
+
     def _net1d_weights(self, plan, backward: bool, cin_keep: int = 0):
         """Every convolution of the net as a [3][64][64] packing (zero padded) in the kernel's execution order, in one buffer
         (+ the biases, [conv][64], for the forward); cached until a parameter changes."""
@@ -480,6 +511,12 @@ class UNetEngine:
         else:
             order = [(cc, None) for cc in convs]
         w = torch.empty(len(order), 3 * 64 * 64, device=dev, dtype=torch.float32)
+        from . import training
+        if training.net1d_enabled():                     # the same bytes in one launch (only under the switch: the default route's launches stay what they were)
+            bias = None if backward else torch.empty(len(order), 64, device=dev, dtype=torch.float32)
+            self._net1d_pack(plan, convs, backward, cin_keep, w, bias)
+            cache[backward] = (key, w, bias)
+            return w, bias
         bias = None if backward else torch.zeros(len(order), 64, device=dev, dtype=torch.float32)
         for i, (cc, keep) in enumerate(order):
             wt = cc.conv.weight.detach().contiguous()
@@ -512,7 +549,9 @@ class UNetEngine:
             keep.append(mod)
         return d, keep
 
-    def _net1d_forward(self, plan, src: Source, lo: int, hi: int, mod_all, per_image: bool, out: Tensor, save: bool):
+    def _net1d_forward(self, plan, src: Source, lo: int, hi: int, mod_all, per_image: bool, out: Tensor, save: bool,
+                       train: bool = False):
+        """train: the launch that also keeps the tail convolution's input (sda_net1d_fwd_train; needs ``save``)."""
         n, length = hi - lo, src.ws
         d, keep = self._net1d_desc(plan, n, length, mod_all, lo, per_image, False)
         d.x = src.x.data_ptr() + 4 * lo * src.sn_outer
@@ -529,6 +568,14 @@ class UNetEngine:
             d.a_save, d.z_save, d.save_stride = a_s.data_ptr(), z_s.data_ptr(), n * C * length
             d.mean_save, d.rstd_save, d.stat_stride = m_s.data_ptr(), r_s.data_ptr(), n * length
             saved = dict(net1d=(plan, a_s, z_s, m_s, r_s), dims=[(1, length)])
+        if train:
+            from ._lib import Net1dTrainDesc
+            t = Net1dTrainDesc()
+            t.net = d
+            saved['net1d_train'] = tail_in = torch.empty(n, plan['lev'].C, length, device=out.device, dtype=torch.float32)
+            t.tail_in = tail_in.data_ptr()
+            ops.net1d_fwd_train(t)
+            return saved
         ops.net1d_launch(d, False)
         return saved
 
@@ -546,6 +593,59 @@ class UNetEngine:
         d.a_save, d.z_save, d.save_stride = a_s.data_ptr(), z_s.data_ptr(), n * C * length
         d.mean_save, d.rstd_save, d.stat_stride = m_s.data_ptr(), r_s.data_ptr(), n * length
         ops.net1d_launch(d, True)
+
+    def _net1d_backward_train(self, saved, g_out: Tensor, src: Source, lo: int, mod_all, per_image: bool, g_in: Optional[Tensor],
+                              pg: 'ParamGrads'):
+        """The backward of a training step on the whole-net kernels: sda_net1d_bwd_train (input VJP + every convolution's output
+        cotangent + the modulation sums), then sda_net1d_wgrad (one multiply launch, one ordered reduction) fills ``pg``."""
+        from ._lib import Net1dTrainDesc, Net1dWgradDesc
+        plan, a_s, z_s, m_s, r_s = saved['net1d']
+        lev, blocks = plan['lev'], plan['blocks']
+        n, length, C, nb, dev = g_out.shape[0], src.ws, lev.C, len(blocks), g_out.device
+        if not _net1d_span_ok(g_out.stride(1), g_out.stride(3), g_out.shape[1], length):
+            g_out = g_out.contiguous()
+        if g_in is None:                                 # (the kernel always finishes with head^T: a few kilobytes nobody reads)
+            g_in = torch.empty(n, src.cx, 1, length, device=dev, dtype=torch.float32)
+        d, keep = self._net1d_desc(plan, n, length, mod_all, lo, per_image, True, cin_keep=src.cx)
+        d.x = g_out.data_ptr()
+        d.x_sn, d.x_sc, d.x_sx = g_out.stride(0), g_out.stride(1), g_out.stride(3)
+        d.out = g_in.data_ptr()
+        d.out_sn, d.out_sc, d.out_sx = g_in.stride(0), g_in.stride(1), g_in.stride(3)
+        d.a_save, d.z_save, d.save_stride = a_s.data_ptr(), z_s.data_ptr(), n * C * length
+        d.mean_save, d.rstd_save, d.stat_stride = m_s.data_ptr(), r_s.data_ptr(), n * length
+        tiles = ops.net1d_tiles(d)
+        g_s = torch.empty(2 * nb + 1, n, C, length, device=dev, dtype=torch.float32)
+        mod_part = torch.empty(max(nb, 1), n, tiles, C, device=dev, dtype=torch.float32)
+        t = Net1dTrainDesc()
+        t.net = d
+        t.g_save, t.g_stride = g_s.data_ptr(), n * C * length
+        t.mod_part, t.mod_tiles = mod_part.data_ptr(), tiles
+        ops.net1d_bwd_train(t)
+        # the weight gradients read the forward's operands: the forward-shaped descriptor (input view, modulation rows, saves)
+        fd, fkeep = self._net1d_desc(plan, n, length, mod_all, lo, per_image, False)
+        fd.x = src.x.data_ptr() + 4 * lo * src.sn_outer
+        fd.x_sn, fd.x_sc, fd.x_sx = src.sn_outer, src.sc, src.sx
+        fd.a_save, fd.z_save, fd.save_stride = d.a_save, d.z_save, d.save_stride
+        fd.mean_save, fd.rstd_save, fd.stat_stride = d.mean_save, d.rstd_save, d.stat_stride
+        wd = Net1dWgradDesc()
+        wd.net = fd
+        wd.tail_in = saved['net1d_train'].data_ptr()
+        wd.g_save, wd.g_stride = t.g_save, t.g_stride
+        wd.gout, wd.gout_sn, wd.gout_sc, wd.gout_sx = g_out.data_ptr(), g_out.stride(0), g_out.stride(1), g_out.stride(3)
+        wd.mod_part, wd.mod_tiles = t.mod_part, tiles
+        convs = [lev.head] + [c for b in blocks for c in (b.conv1, b.conv2)] + [lev.tail]
+        for v, cc in enumerate(convs):                   # (a frozen tensor: NULL, the reduction skips it)
+            w, b = cc.conv.weight, cc.conv.bias
+            dw = torch.empty(w.shape, device=dev, dtype=torch.float32) if w.requires_grad else None
+            db = torch.empty(b.shape, device=dev, dtype=torch.float32) if (b is not None and b.requires_grad) else None
+            wd.dw[v], wd.db[v] = None if dw is None else dw.data_ptr(), None if db is None else db.data_ptr()
+            pg.conv_grads[id(cc)] = (dw, db)
+        if pg.gmod is not None:
+            rows = pg.gmod[lo:] if per_image else pg.gmod
+            for k, blk in enumerate(blocks):
+                wd.dmod[k] = rows[:, blk.mod_off:].data_ptr()
+            wd.dmod_sn = self.mod_total
+        ops.net1d_wgrad(wd, dev)
 
     # -------------------------------------------------------------------------------- forward
     def _mod_for(self, blk: _Block, mod_all: Optional[Tensor], lo: int, per_image: bool):
@@ -721,7 +821,9 @@ class UNetEngine:
         no input gradient).  pg: also the parameter gradients, each launched as soon as its layer's cotangent exists."""
         if 'net1d' in saved:
             if pg is not None:
-                raise SdaHipError('the whole-net 1-D kernel forms no parameter gradients (training-route forwards do not use it)')
+                if 'net1d_train' not in saved:
+                    raise SdaHipError('this whole-net 1-D forward kept nothing for parameter gradients (it ran outside the net1d training route)')
+                return self._net1d_backward_train(saved, g_out, src, lo, mod_all, per_image, g_in, pg)
             return self._net1d_backward(saved, g_out, src, lo, mod_all, per_image, g_in)
         g_out = g_out.contiguous()
         L, D = self.levels, self.depth
@@ -882,8 +984,11 @@ class _UNetFunction(torch.autograd.Function):
         # a channel-last trajectory (MCScoreWrapper's transposed view of a (B, L, C) tensor) through the whole-net 1-D kernel:
         # the output is laid out channel-last too, so that the wrapper's transpose back is a contiguous tensor -- the kernel
         # writes through strides, no copy kernel on either side (and likewise for the cotangent / input gradient below)
-        ctx.channel_last = bool(not train and src.hs == 1 and src.sc == 1 and src.sx == src.cx and src.cx > 1 and
-                                engine.net1d_plan(src) is not None)
+        # (training: only on the whole-net training route, training.enable(net1d=True); the per-layer kernels write planar tensors)
+        n1t = engine.net1d_train_plan(src, dev) if (train and need) else None
+        ctx.net1d_train = n1t is not None
+        ctx.channel_last = bool(src.hs == 1 and src.sc == 1 and src.sx == src.cx and src.cx > 1 and
+                                (n1t is not None if train else engine.net1d_plan(src) is not None))
         if ctx.channel_last:
             out = torch.empty(n, ho, wo, out_channels, device=dev, dtype=torch.float32).permute(0, 3, 1, 2)
         else:
@@ -891,7 +996,10 @@ class _UNetFunction(torch.autograd.Function):
         ctx.engine, ctx.src, ctx.mod_all, ctx.per_image = engine, src, mod_all, per_image
         ctx.x_shape = x.shape
         ctx.params = params
-        ctx.vjp_state = engine.forward_all(src, mod_all, per_image, out, need, train)
+        if n1t is not None:                              # one launch, everything kept
+            ctx.vjp_state = [(0, n, engine._net1d_forward(n1t, src, 0, n, mod_all, per_image, out, True, train=True))]
+        else:
+            ctx.vjp_state = engine.forward_all(src, mod_all, per_image, out, need, train)
         return out
 
     @staticmethod
@@ -914,8 +1022,11 @@ def _train_backward(ctx, g_out: Tensor):
     engine, src = ctx.engine, ctx.src
     need_x, need_mod = ctx.needs_input_grad[0], ctx.needs_input_grad[3]
     need_p = any(ctx.needs_input_grad[6:])
-    g_out = g_out.contiguous()
-    g_in = torch.empty(src.n, src.cx, src.hs, src.ws, device=g_out.device, dtype=torch.float32) if need_x else None
+    if ctx.net1d_train and ctx.channel_last:             # (strided cotangent in, channel-last gradient out: as on the sampling path)
+        g_in = torch.empty(src.n, src.hs, src.ws, src.cx, device=g_out.device, dtype=torch.float32).permute(0, 3, 1, 2) if need_x else None
+    else:
+        g_out = g_out.contiguous()
+        g_in = torch.empty(src.n, src.cx, src.hs, src.ws, device=g_out.device, dtype=torch.float32) if need_x else None
     pg = ParamGrads(ctx.mod_all, ctx.per_image, need_mod) if (need_p or need_mod) else None
     engine.backward_all(ctx.vjp_state, g_out, src, ctx.mod_all, ctx.per_image, g_in, pg)
     ctx.vjp_state = None

@@ -622,6 +622,65 @@ def net1d_launch(d: '_lib.Net1dDesc', backward: bool):
     prof.records.append((e0, e1, flops, 'net1d_bwd' if backward else 'net1d_fwd'))
 
 
+def _net1d_bracket(tag: str, flops: float, launch):
+    prof = conv_profile
+    if prof is None:
+        launch()
+        return
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    launch()
+    e1.record()
+    prof.records.append((e0, e1, flops, tag))
+
+
+def _net1d_flops(d: '_lib.Net1dDesc') -> float:
+    return 2.0 * d.n * d.len * 3 * (d.cin * d.c + 2 * d.nblocks * d.c * d.c + d.c * d.cout)
+
+
+def net1d_fwd_train(t: '_lib.Net1dTrainDesc'):
+    """sda_net1d_fwd with the saves of a training step (csrc/net1d_train.hip): also writes the tail convolution's input."""
+    lib = _lib.load()
+    _net1d_bracket('net1d_fwd', _net1d_flops(t.net),
+                   lambda: _lib.check(lib.sda_net1d_fwd_train(ctypes.byref(t), _stream()), 'sda_net1d_fwd_train'))
+
+
+def net1d_bwd_train(t: '_lib.Net1dTrainDesc'):
+    """sda_net1d_bwd that also stores every convolution's output cotangent and the per-tile modulation-gradient sums."""
+    lib = _lib.load()
+    _net1d_bracket('net1d_bwd', _net1d_flops(t.net),
+                   lambda: _lib.check(lib.sda_net1d_bwd_train(ctypes.byref(t), _stream()), 'sda_net1d_bwd_train'))
+
+
+def net1d_tiles(d: '_lib.Net1dDesc') -> int:
+    """Tiles per sequence of the whole-net launch serving ``d`` (host only)."""
+    tiles = _lib.load().sda_net1d_tiles(ctypes.byref(d))
+    if tiles < 1:
+        _lib.check(tiles, 'sda_net1d_tiles')
+    return tiles
+
+
+def net1d_wgrad(d: '_lib.Net1dWgradDesc', device) -> Tensor:
+    """Weight, bias and modulation gradients of a whole single-level 1-D U-Net: one multiply launch over all convolutions + one
+    ordered slab reduction (sda_net1d_wgrad).  Allocates the slab partials (d.work) and returns them (the caller keeps them alive
+    no longer than the stream order needs: torch's caching allocator is stream-ordered)."""
+    lib = _lib.load()
+    floats = int(lib.sda_net1d_wgrad_work_floats(ctypes.byref(d)))
+    if floats < 0:
+        _lib.check(floats, 'sda_net1d_wgrad_work_floats')
+    work = torch.empty(floats, device=device, dtype=torch.float32)
+    d.work = work.data_ptr()
+    t = d.net
+    flops = 2.0 * t.n * t.len * 3 * (t.cin * t.c + 2 * t.nblocks * t.c * t.c + t.c * t.cout)
+    _net1d_bracket('net1d_wgrad', flops, lambda: _lib.check(lib.sda_net1d_wgrad(ctypes.byref(d), _stream()), 'sda_net1d_wgrad'))
+    return work
+
+
+def net1d_pack(p: '_lib.Net1dPackDesc'):
+    """Every packing of a whole-net launch (forward buffer, backward-data buffer, bias rows: the non-NULL ones) in one launch."""
+    _lib.check(_lib.load().sda_net1d_pack(ctypes.byref(p), _stream()), 'sda_net1d_pack')
+
+
 def net1d_launch_fused(d: '_lib.Net1dDesc', f: '_lib.Net1dFuse', backward: bool):
     """One half of a fused guided evaluation (sda_net1d_fwd_fused / sda_net1d_bwd_fused; sda_amd/fused1d.py)."""
     lib = _lib.load()

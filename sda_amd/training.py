@@ -29,6 +29,13 @@ beside it, csrc/conv_wgrad3x.hip for the 3 x 3 stride-2 heads and the up-samplin
 of the 42 launches); the first head (context plane) and the last tail stay on the general kernel.  The default ``'general'`` is bitwise
 what it always was, and so is ``'tiled'``.
 
+A fourth opt-in, ``parameter_gradients(net1d=True)`` (or ``enable(net1d=True)``), trains a single-level 1-D U-Net the whole-net kernel
+serves (csrc/net1d.hip: <= 64 channels, one padding mode, no context -- the Lorenz global net of the reference's ``train_global``) on
+csrc/net1d_train.hip: one forward launch, three backward launches (the input VJP that also stores every convolution's output cotangent,
+one weight-gradient launch for all convolutions, one slab reduction) and one pack launch after each parameter update.  Nets that
+kernel declines, and a batch whose activations do not fit the memory budget in one piece, keep the per-layer route; the default
+``False`` leaves every route bit for bit what it is.
+
 :class:`AdamW` is the optimizer step of this route as one launch (csrc/optim.hip) that keeps the ResMLP weight slabs packed."""
 import contextlib
 import math
@@ -49,6 +56,7 @@ WGRAD_ROUTES = ('general', 'tiled', 'tiled_ht')
 _enabled = False
 _mlp = False
 _wgrad = 'general'
+_net1d = False
 _local = threading.local()
 
 
@@ -58,20 +66,21 @@ def _check_route(wgrad: str) -> str:
     return wgrad
 
 
-def enable(mlp: bool = False, wgrad: str = 'general') -> None:
+def enable(mlp: bool = False, wgrad: str = 'general', net1d: bool = False) -> None:
     """Form parameter gradients in the U-Net backward from now on; ``mlp=True``: in the ScoreNet / ResMLP backward as well.
     ``wgrad='tiled'``: the 3 x 3 block convolutions' weight gradients on the tiled kernel (csrc/conv_wgrad3.hip) where it serves the
     launch; ``wgrad='tiled_ht'``: also the stride-2 heads and up-sampling tails on theirs (csrc/conv_wgrad3x.hip); every other layer,
-    and everything under the default ``'general'``, on the general kernel."""
-    global _enabled, _mlp, _wgrad
+    and everything under the default ``'general'``, on the general kernel.  ``net1d=True``: single-level 1-D U-Nets the whole-net
+    kernel serves train on csrc/net1d_train.hip."""
+    global _enabled, _mlp, _wgrad, _net1d
     route = _check_route(wgrad)
-    _enabled, _mlp, _wgrad = True, bool(mlp), route
+    _enabled, _mlp, _wgrad, _net1d = True, bool(mlp), route, bool(net1d)
 
 
 def disable() -> None:
     """Back to the default: input gradients only (and the general weight-gradient route)."""
-    global _enabled, _mlp, _wgrad
-    _enabled, _mlp, _wgrad = False, False, 'general'
+    global _enabled, _mlp, _wgrad, _net1d
+    _enabled, _mlp, _wgrad, _net1d = False, False, 'general', False
 
 
 def enabled() -> bool:
@@ -88,19 +97,24 @@ def wgrad_route() -> str:
     return _wgrad
 
 
+def net1d_enabled() -> bool:
+    """Do single-level 1-D U-Nets train on the whole-net kernels (the fourth opt-in)?"""
+    return _enabled and _net1d
+
+
 @contextlib.contextmanager
-def parameter_gradients(on: bool = True, mlp: bool = False, wgrad: str = 'general'):
+def parameter_gradients(on: bool = True, mlp: bool = False, wgrad: str = 'general', net1d: bool = False):
     """Switch parameter gradients on (or off) inside the block, those of ScoreNet / ResMLP with ``mlp=True``, the block convolutions'
-    weight gradients on the tiled kernel with ``wgrad='tiled'``, the heads' and tails' as well with ``wgrad='tiled_ht'``; the previous
-    state of all three switches is restored on exit."""
-    global _enabled, _mlp, _wgrad
+    weight gradients on the tiled kernel with ``wgrad='tiled'``, the heads' and tails' as well with ``wgrad='tiled_ht'``, single-level
+    1-D U-Nets on the whole-net kernels with ``net1d=True``; the previous state of all four switches is restored on exit."""
+    global _enabled, _mlp, _wgrad, _net1d
     route = _check_route(wgrad)
-    prev = (_enabled, _mlp, _wgrad)
-    _enabled, _mlp, _wgrad = bool(on), bool(on) and bool(mlp), route
+    prev = (_enabled, _mlp, _wgrad, _net1d)
+    _enabled, _mlp, _wgrad, _net1d = bool(on), bool(on) and bool(mlp), route, bool(on) and bool(net1d)
     try:
         yield
     finally:
-        _enabled, _mlp, _wgrad = prev
+        _enabled, _mlp, _wgrad, _net1d = prev
 
 
 @contextlib.contextmanager

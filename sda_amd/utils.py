@@ -76,7 +76,7 @@ _SCHEDULES = {
 
 def loop(sde: 'VPSDE', trainset, validset, epochs: int = 256, batch_size: int = 64, optimizer: str = 'AdamW',
          learning_rate: float = 1e-3, weight_decay: float = 1e-3, scheduler: str = 'linear', device: str = 'cpu',
-         fused: bool = False, wgrad: str = 'general', **absorb) -> Iterator:
+         fused: bool = False, wgrad: str = 'general', net1d: bool = False, **absorb) -> Iterator:
     """Train ``sde`` (its score network) on ``trainset`` and yield ``(loss_train, loss_valid, lr)`` once per epoch.
 
     As the reference's loop: shuffled DataLoaders whose items are ``(x, kwargs)`` pairs (``kwargs`` go on to ``sde.loss``),
@@ -85,7 +85,7 @@ def loop(sde: 'VPSDE', trainset, validset, epochs: int = 256, batch_size: int = 
     gradients are switched on (``sda_amd.training.parameter_gradients(mlp=True)``: the U-Nets and ScoreNet) while the training steps run.
     ``fused=True`` takes ``sda_amd.training.AdamW`` (one launch per step, the ResMLP weight slabs stay packed) for ``torch.optim.AdamW``;
     ``wgrad='tiled'`` sends the block convolutions' weight gradients to the tiled kernel, ``wgrad='tiled_ht'`` the stride-2 heads' and
-    up-sampling tails' as well (``sda_amd.training``)."""
+    up-sampling tails' as well; ``net1d=True`` trains a single-level 1-D U-Net on the whole-net kernels (``sda_amd.training``)."""
     from torch.utils.data import DataLoader
     loaders = [DataLoader(ds, batch_size=batch_size, shuffle=True) for ds in (trainset, validset)]
     if optimizer != 'AdamW':
@@ -100,7 +100,7 @@ def loop(sde: 'VPSDE', trainset, validset, epochs: int = 256, batch_size: int = 
     for _ in range(epochs):
         losses_train, losses_valid = [], []
         sde.train()
-        with training.parameter_gradients(mlp=True, wgrad=wgrad):
+        with training.parameter_gradients(mlp=True, wgrad=wgrad, net1d=net1d):
             for batch in loaders[0]:
                 x, kwargs = _to(batch, device=device)
                 loss = sde.loss(x, **kwargs)

@@ -19,7 +19,13 @@ oracle's eager step) for the two routes ALTERNATING in one process, block by blo
 block warm-up steps, then `steps` steps between two events; reported are the median of `blocks` blocks and the fastest and slowest
 block.  The tiled route earns its place on a shape only where its median is below the general route's FASTEST block.  --wgrad all
 does the same for general, tiled and tiled_ht (and the eager step), the head and tail shapes included: there tiled_ht is held to the
-general route's fastest block per shape, and its step to the tiled route's fastest block."""
+general route's fastest block per shape, and its step to the tiled route's fastest block.
+
+--net1d times the Lorenz global net (lorenz_global_train) on the per-layer route (`layers`: what every training step of that net took
+before training.enable(net1d=True) existed), on the whole-net kernels (`net1d`, csrc/net1d_train.hip) and on the oracle's eager step,
+alternating block by block in one process, at batch 64 of (32, 3) and batch 1024 of (65, 3), each without and with the AdamW step (with
+it the re-pack of the whole-net packings is in the number), plus the per-family launch counts and kernel times of one profiled `net1d`
+step.  The `net1d` route earns its place where its median is below the `layers` route's FASTEST block."""
 import argparse
 import json
 import os
@@ -69,22 +75,23 @@ def configs(dev):
     ]
 
 
-def hip_step(cfg, dev, wgrad='general'):
+def hip_step(cfg, dev, wgrad='general', net1d=False, optimizer=True):
     net = cfg['net']
     sde = VPSDE(net, shape=cfg['shape']).to(dev)
     opt = torch.optim.AdamW(net.parameters(), lr=1e-4, weight_decay=1e-3)
     x = torch.randn(cfg['batch'], *cfg['shape'], device=dev)
 
     def step():
-        with training.parameter_gradients(wgrad=wgrad):
+        with training.parameter_gradients(wgrad=wgrad, net1d=net1d):
             loss = sde.loss(x)
             loss.backward()
-        opt.step()
+        if optimizer:
+            opt.step()
         opt.zero_grad()
     return step, sde, x
 
 
-def oracle_step(cfg, dev):
+def oracle_step(cfg, dev, optimizer=True):
     """The same step on the oracle's functional net (fp32, torch autograd, the framework's own GPU kernels)."""
     names = {k for k, _ in cfg['net'].named_parameters()}
     sd = {k: v.detach().clone().float().to(dev).requires_grad_(k in names) for k, v in cfg['net'].state_dict().items()}
@@ -100,17 +107,18 @@ def oracle_step(cfg, dev):
             xt = sched.mu(tb) * x + sched.sigma(tb) * e
             loss = (cfg['eps'](sd, xt, t) - e).square().mean()
             loss.backward()
-        opt.step()
+        if optimizer:
+            opt.step()
         opt.zero_grad()
     return step
 
 
-def family_profile(sde, x, wgrad='general'):
+def family_profile(sde, x, wgrad='general', net1d=False):
     """One training step under ops.ConvProfile: kernel time by family, forward and backward apart."""
     prof = ops.ConvProfile()
     ops.conv_profile = prof
     try:
-        with training.parameter_gradients(wgrad=wgrad):
+        with training.parameter_gradients(wgrad=wgrad, net1d=net1d):
             e0, e1, e2 = (torch.cuda.Event(enable_timing=True) for _ in range(3))
             e0.record()
             loss = sde.loss(x)
@@ -124,7 +132,7 @@ def family_profile(sde, x, wgrad='general'):
         ops.conv_profile = None
     fam = {}
     for i, (a, b, flops, f) in enumerate(prof.records):
-        key = f if f in WGRAD_FAMILIES else ('forward.' if i < fwd_n else 'input_vjp.') + f
+        key = f if f in WGRAD_FAMILIES + ('net1d_wgrad',) else ('forward.' if i < fwd_n else 'input_vjp.') + f
         r = fam.setdefault(key, dict(launches=0, ms=0.0, tflop=0.0))
         r['launches'] += 1
         r['ms'] += a.elapsed_time(b)
@@ -255,6 +263,32 @@ def kolmogorov_routes(cfg, dev, steps, warmup, blocks, routes=('general', 'tiled
     return out
 
 
+NET1D_CONFIGS = ((64, (32, 3)), (1024, (65, 3)))
+
+
+def net1d_routes(dev, steps, warmup, blocks):
+    """The Lorenz global net's training step on the per-layer route, the whole-net route and the oracle's eager step."""
+    base = [c for c in configs(dev) if c['name'] == 'lorenz_global_train'][0]
+    rows = []
+    for batch, shape in NET1D_CONFIGS:
+        cfg = dict(base, batch=batch, shape=shape)
+        row = dict(batch=batch, shape=list(shape))
+        for optimizer in (False, True):
+            fns = dict(layers=hip_step(cfg, dev, optimizer=optimizer)[0], net1d=hip_step(cfg, dev, net1d=True, optimizer=optimizer)[0],
+                       eager=oracle_step(cfg, dev, optimizer=optimizer))
+            out = {k: _stat(v) for k, v in _blocks(fns, steps, warmup, blocks).items()}
+            out['layers_median_over_net1d_median'] = round(out['layers']['median_ms'] / out['net1d']['median_ms'], 3)
+            out['eager_median_over_net1d_median'] = round(out['eager']['median_ms'] / out['net1d']['median_ms'], 3)
+            out['net1d_median_below_layers_fastest'] = out['net1d']['median_ms'] < out['layers']['fastest_ms']
+            row['with_adamw_step' if optimizer else 'loss_and_backward'] = out
+        step, sde, x = hip_step(cfg, dev, net1d=True)
+        step()
+        row['net1d_profile'] = family_profile(sde, x, net1d=True)
+        rows.append(row)
+        print(json.dumps(row), flush=True)
+    return rows
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--steps', type=int, default=10)
@@ -262,8 +296,16 @@ def main():
     ap.add_argument('--out', default=None)
     ap.add_argument('--wgrad', choices=('general', 'tiled', 'tiled_ht', 'both', 'all'), default='general')
     ap.add_argument('--blocks', type=int, default=5, help='--wgrad both / all: blocks per route (median, fastest and slowest are reported)')
+    ap.add_argument('--net1d', action='store_true', help='the Lorenz global net: per-layer route, whole-net route and eager, alternating')
     args = ap.parse_args()
     dev = torch.device('cuda:0')
+    if args.net1d:
+        result = dict(device=torch.cuda.get_device_name(dev), steps=args.steps, warmup=args.warmup, blocks=args.blocks,
+                      lorenz_global_train=net1d_routes(dev, args.steps, args.warmup, args.blocks), time=time.strftime('%Y-%m-%dT%H:%M:%S'))
+        if args.out:
+            with open(args.out, 'w') as f:
+                json.dump(result, f, indent=1)
+        return
     route = {'both': 'tiled', 'all': 'tiled_ht'}.get(args.wgrad, args.wgrad)
     compared = {'both': ('general', 'tiled'), 'all': ('general', 'tiled', 'tiled_ht')}.get(args.wgrad)
     result = dict(device=torch.cuda.get_device_name(dev), steps=args.steps, warmup=args.warmup, wgrad=args.wgrad, configs={})
