@@ -207,8 +207,8 @@ int64_t sda_conv_wgrad_work_floats(const sda_wgrad_desc* d);
 int sda_conv_wgrad3_serves(const sda_wgrad_desc* d);
 int64_t sda_conv_wgrad3_work_floats(const sda_wgrad_desc* d);
 int sda_conv_wgrad3(const sda_wgrad_desc* d, void* stream);
-/* OPT-IN tiled route for the stride-2 heads and up-sampling tails (csrc/conv_wgrad3x.hip; additions that keep ABI v14): the design,
- * descriptor, result layout, slab range and reduction of sda_conv_wgrad3 for two more geometries.  Served: as sda_conv_wgrad3 but
+/* OPT-IN tiled route for the stride-2 heads and up-sampling tails (csrc/conv_wgrad3.hip, the same kernel template; additions that
+ * keep ABI v14): the design, descriptor, result layout, slab range and reduction of sda_conv_wgrad3 for two more geometries.  Served: as sda_conv_wgrad3 but
  *   up2: up_h = up_w = 2, stride 1, ho = 2 hs, wo = 2 ws, loader = ln_mean / ln_rstd alone (no mod, no act_in) or none;
  *   s2:  stride_h = stride_w = 2, up = 1, hs and ws even, ho = hs / 2, wo = ws / 2, plain loader (no ln, mod, act_in);
  * a tile within the 160 KiB LDS.  `work` holds sda_conv_wgrad3x_work_floats floats.

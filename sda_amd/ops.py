@@ -323,7 +323,7 @@ WGRAD_ROUTES = ('general', 'tiled', 'tiled_ht')
 def conv_wgrad(conv: ConvDesc, g: Tensor, dw: Tensor, db: Optional[Tensor], accumulate: bool, slabs: int = 0, route: str = 'general'):
     """dw (+)= the weight gradient of the layer ``conv`` describes for the output cotangent ``g``; db (+)= its bias gradient.
     route 'tiled': the tiled 3 x 3 kernel (csrc/conv_wgrad3.hip) where sda_conv_wgrad3_serves says so, the general kernel otherwise;
-    route 'tiled_ht': that, then the heads' and tails' kernel (csrc/conv_wgrad3x.hip) where sda_conv_wgrad3x_serves says so, then the
+    route 'tiled_ht': that, then the same kernel's heads' and tails' geometries where sda_conv_wgrad3x_serves says so, then the
     general kernel."""
     if route not in WGRAD_ROUTES:
         raise ValueError(f"conv_wgrad route {route!r} (expected 'general', 'tiled' or 'tiled_ht')")

@@ -25,7 +25,7 @@ kernels of the samplers stay sampling-only.  ``sda_amd.utils.loop`` switches bot
 A third opt-in, ``parameter_gradients(wgrad='tiled')`` (or ``enable(wgrad='tiled')``), sends the weight gradients of the 3 x 3,
 stride-1 block convolutions (36 of the 42 launches of a Kolmogorov step) to the tiled kernel csrc/conv_wgrad3.hip; heads, tails, 1-D
 nets and anything else outside its served set stay on the general kernel.  ``wgrad='tiled_ht'`` (heads and tails) is that route and,
-beside it, csrc/conv_wgrad3x.hip for the 3 x 3 stride-2 heads and the up-sampling tails with channel counts in multiples of 32 (4 more
+beside it, the same kernel's two other geometries (sda_conv_wgrad3x) for the 3 x 3 stride-2 heads and the up-sampling tails with channel counts in multiples of 32 (4 more
 of the 42 launches); the first head (context plane) and the last tail stay on the general kernel.  The default ``'general'`` is bitwise
 what it always was, and so is ``'tiled'``.
 
@@ -69,7 +69,7 @@ def _check_route(wgrad: str) -> str:
 def enable(mlp: bool = False, wgrad: str = 'general', net1d: bool = False) -> None:
     """Form parameter gradients in the U-Net backward from now on; ``mlp=True``: in the ScoreNet / ResMLP backward as well.
     ``wgrad='tiled'``: the 3 x 3 block convolutions' weight gradients on the tiled kernel (csrc/conv_wgrad3.hip) where it serves the
-    launch; ``wgrad='tiled_ht'``: also the stride-2 heads and up-sampling tails on theirs (csrc/conv_wgrad3x.hip); every other layer,
+    launch; ``wgrad='tiled_ht'``: also the stride-2 heads and up-sampling tails on its two other geometries (sda_conv_wgrad3x); every other layer,
     and everything under the default ``'general'``, on the general kernel.  ``net1d=True``: single-level 1-D U-Nets the whole-net
     kernel serves train on csrc/net1d_train.hip."""
     global _enabled, _mlp, _wgrad, _net1d

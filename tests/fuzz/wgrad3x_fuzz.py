@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Randomised parity sweep of the heads' and tails' tiled weight-gradient kernel (csrc/conv_wgrad3x.hip) over its served set against
+"""Randomised parity sweep of the heads' and tails' tiled weight-gradient kernel (csrc/conv_wgrad3.hip, sda_conv_wgrad3x) over its served set against
 float64 torch.autograd, on the device or on its host replay (libsda_emu.so).
 
     python tests/fuzz/wgrad3x_fuzz.py [--cases 200] [--seed 0] [--emu]

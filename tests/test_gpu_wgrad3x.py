@@ -1,4 +1,4 @@
-"""Device: the tiled weight-gradient kernel of the stride-2 heads and up-sampling tails (csrc/conv_wgrad3x.hip) through its C entry,
+"""Device: the tiled weight-gradient kernel of the stride-2 heads and up-sampling tails (csrc/conv_wgrad3.hip, sda_conv_wgrad3x) through its C entry,
 through ``ops.conv_wgrad(route='tiled_ht')`` and through a U-Net's backward under ``training.parameter_gradients(wgrad='tiled_ht')``.
 
 Layer cases (tests/wgrad3x_cases.py), the widest served layers and a sample of tests/fuzz/wgrad3x_fuzz.py against the float64

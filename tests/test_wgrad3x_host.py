@@ -1,4 +1,4 @@
-"""CPU: the tiled weight-gradient kernel of the stride-2 heads and up-sampling tails (csrc/conv_wgrad3x.hip) -- its served set and the
+"""CPU: the tiled weight-gradient kernel of the stride-2 heads and up-sampling tails (csrc/conv_wgrad3.hip, sda_conv_wgrad3x) -- its served set and the
 widths at which the LDS cap ends it, its plan and host replay against float64 over the case table (tests/wgrad3x_cases.py) and a
 sample of tests/fuzz/wgrad3x_fuzz.py, and the ``wgrad='tiled_ht'`` switch.
 

@@ -3,8 +3,10 @@ and its device tests (test_gpu_wgrad3.py).  Built by tests/wgrad_ref.py: the flo
 
 Every case carries, beside its shape, the plan its author expects of the kernel's planner: rows per stage R, row
 blocks per image nrb, the cout tile 32 mt, the tile counts n_ct / n_cit, the slab count and whether R (W + 2) is no multiple of
-the four positions of a K step (``q4_rounds``: the last K step then reads the zeroed tail of the cotangent tile).  ``plan`` below
-works the same plan out in plain Python; the host test holds the table, ``plan`` and the library against one another."""
+the four positions of a K step (``q4_rounds``: the last K step then reads the zeroed tail of the cotangent tile).  ``plan``
+(tests/wgrad3_plan.py) works the same plan out in plain Python; the host test holds the table, ``plan`` and the library against one
+another."""
+from tests.wgrad3_plan import LDS_MAX, S1, pitch, plan as _plan  # noqa: F401
 from tests.wgrad_ref import make_case
 
 ACTS = ('ReLU', 'ELU', 'GELU', 'SELU')
@@ -69,7 +71,6 @@ PLANS = {name: entry['plan'] for name, entry in _TABLE.items()}
 #: cout tile -> the largest W the kernel serves (cin 32, n = 1, h = 2: one row per stage): the 160 KiB LDS cap of the plan
 BOUNDARY = {32: 306, 64: 242, 96: 190}
 _BOUNDARY_KIND = {32: ('plain', True), 64: ('conv1', True), 96: ('conv2', False)}
-LDS_MAX = 160 * 1024
 
 
 def build(name, dev):
@@ -83,23 +84,6 @@ def boundary_case(cout, dev, over=0):
     return make_case(kind, dev, cin=32, cout=cout, n=1, h=2, w=BOUNDARY[cout] + over, circular=circular, seed=90 + cout // 32 + 4 * over)
 
 
-def pitch(need):
-    """The smallest LDS channel pitch >= need that is 2 (mod 32) floats."""
-    return (need + 29) // 32 * 32 + 2
-
-
 def plan(cin, cout, n, h, w, slabs=0):
-    """The plan of DESIGN.md 5.1h by hand -> dict(R, nrb, S, mt, n_ct, n_cit, q4, q4_rounds, lds_bytes, per, slabs)."""
-    w2 = w + 2
-    R = min(max(128 // w2, 1), h)
-    nrb = -(-h // R)
-    S = n * nrb
-    mt = 3 if cout % 96 == 0 else 2 if cout % 64 == 0 else 1
-    n_ct, n_cit = cout // (32 * mt), cin // 32
-    q4 = (R * w2 + 3) // 4 * 4
-    lds = 4 * (32 * pitch(q4 + 2 * w2 + 2) + 32 * mt * pitch(q4))
-    s = slabs or min(512 // (n_ct * n_cit), 256)
-    s = max(min(s, S), 1)
-    per = -(-S // s)
-    return dict(R=R, nrb=nrb, S=S, mt=mt, n_ct=n_ct, n_cit=n_cit, q4=q4, q4_rounds=q4 != R * w2, lds_bytes=lds, per=per,
-                slabs=-(-S // per))
+    """tests.wgrad3_plan.plan at the stride-1 geometry."""
+    return _plan(S1, cin, cout, n, h, w, slabs)

@@ -1,15 +1,15 @@
-"""Layer cases of the tiled weight-gradient kernel of the stride-2 heads and up-sampling tails (csrc/conv_wgrad3x.hip), shared by its
+"""Layer cases of the tiled weight-gradient kernel of the stride-2 heads and up-sampling tails (csrc/conv_wgrad3.hip), shared by its
 host replay (test_wgrad3x_host.py) and its device tests (test_gpu_wgrad3x.py).  Built by tests/wgrad_ref.py ('tail_up', 'head_s2'):
 the float64 reference is that module's.  ``h`` and ``w`` are the SOURCE size: the output is (2 h, 2 w) for 'tail_up' and
 (h / 2, w / 2) for 'head_s2'.  'tail_up_plain' is 'tail_up' without the LayerNorm (the kernel's second up2 loader).
 
 Every case carries, beside its shape, the plan its author expects of the kernel's planner: rows per stage R, row
 blocks per image nrb, the cout tile 32 mt, the tile counts n_ct / n_cit, the slab count and whether R (wo + 2) is no multiple of
-the four positions of a K step (``q4_rounds``).  ``plan`` below works the same plan out in plain Python; the host test holds the
-table, ``plan`` and the library against one another."""
+the four positions of a K step (``q4_rounds``).  ``plan`` (tests/wgrad3_plan.py) works the same plan out in plain Python; the
+host test holds the table, ``plan`` and the library against one another."""
+from tests.wgrad3_plan import LDS_MAX, S2, UP2, out_size, pitch, plan  # noqa: F401
 from tests.wgrad_ref import make_case
 
-UP2, S2 = 'tail_up', 'head_s2'
 UP2_PLAIN = 'tail_up_plain'
 
 
@@ -70,8 +70,6 @@ _TABLE = {
 CASES = {name: entry['cfg'] for name, entry in _TABLE.items()}
 PLANS = {name: entry['plan'] for name, entry in _TABLE.items()}
 
-LDS_MAX = 160 * 1024
-
 #: (geometry, cout tile) -> the largest SOURCE width the kernel serves at one row per stage (cin 32, n = 1; source height 1 for
 #: up2, 2 for s2), from the LDS formula of ``plan`` (test_wgrad3x_host.test_lds_cap_by_hand works them out again):
 #:   up2, wo = 2 w: 4 (32 pitch(q4 + 2 (wo + 2) + 2) + 32 mt pitch(q4)), q4 = wo + 2 rounded up to 4 -> wo = 306 / 242 / 190
@@ -102,34 +100,3 @@ def boundary_case(kind, cout, dev, over=0):
     w = BOUNDARY[(kind, cout)] + over * _BOUNDARY_STEP[kind]
     return make_case(kind, dev, cin=32, cout=cout, n=1, h=_BOUNDARY_H[kind], w=w, circular=cout != 64,
                      seed=190 + cout // 32 + 4 * over + (8 if kind == S2 else 0))
-
-
-def out_size(kind, h, w):
-    return (h // 2, w // 2) if kind == S2 else (2 * h, 2 * w)
-
-
-def pitch(need):
-    """The smallest LDS channel pitch >= need that is 2 (mod 32) floats."""
-    return (need + 29) // 32 * 32 + 2
-
-
-def plan(kind, cin, cout, n, h, w, slabs=0):
-    """The plan of DESIGN.md 5.1h by hand -> dict(R, nrb, S, mt, n_ct, n_cit, q4, q4_rounds, lds_bytes, per, slabs)."""
-    ho, wo = out_size(kind, h, w)
-    w2 = wo + 2
-    R = min(max(128 // w2, 1), ho)
-    nrb = -(-ho // R)
-    S = n * nrb
-    mt = 3 if cout % 96 == 0 else 2 if cout % 64 == 0 else 1
-    n_ct, n_cit = cout // (32 * mt), cin // 32
-    q4 = (R * w2 + 3) // 4 * 4
-    if kind == S2:                        # four parity planes of R + 1 rows; the last tap reads plane 3 at q4 - 1 + w2 + 1
-        vp = pitch(3 * (R + 1) * w2 + q4 + w2 + 1)
-    else:                                 # R + 2 rows of the up-sampled image
-        vp = pitch(q4 + 2 * w2 + 2)
-    lds = 4 * (32 * vp + 32 * mt * pitch(q4))
-    s = slabs or min(512 // (n_ct * n_cit), 256)
-    s = max(min(s, S), 1)
-    per = -(-S // s)
-    return dict(R=R, nrb=nrb, S=S, mt=mt, n_ct=n_ct, n_cit=n_cit, q4=q4, q4_rounds=q4 != R * w2, lds_bytes=lds, per=per,
-                slabs=-(-S // per), vp=vp, gp=pitch(q4))

@@ -13,7 +13,7 @@ heads 96 -> 192 @ 64^2 and 192 -> 384 @ 32^2, up-sampling tails 384 -> 192 @ 16^
 TFLOP/s and its fraction of the fp32 matrix peak (256 CUs x 4 SIMDs x 256 flop/clk x 2.4 GHz = 157.3 TFLOP/s).
 
 --wgrad selects the weight-gradient route of the block convolutions (sda_amd.training: 'general' = csrc/conv_wgrad.hip everywhere,
-'tiled' = csrc/conv_wgrad3.hip where it serves the launch, 'tiled_ht' = that and csrc/conv_wgrad3x.hip for the heads and tails).
+'tiled' = csrc/conv_wgrad3.hip where it serves the launch, 'tiled_ht' = that and its stride-2 / up-sampling geometries for the heads and tails).
 --wgrad both times the block shapes and the Kolmogorov step (and the
 oracle's eager step) for the two routes ALTERNATING in one process, block by block (the scheme of tools/mlp_train_bench.py): per
 block warm-up steps, then `steps` steps between two events; reported are the median of `blocks` blocks and the fastest and slowest
