@@ -250,6 +250,9 @@ typedef struct sda_block1d_desc {
 } sda_block1d_desc;
 int sda_block1d_fwd(const sda_block1d_desc* d, void* stream);
 int sda_block1d_bwd(const sda_block1d_desc* d, void* stream);
+/* positions per workgroup (16, 32 or 64) of the launch serving `d`, forward and VJP alike, or SDA_E_UNSUPPORTED
+ * (host, no launch; reads the shape fields only, pointers may be NULL) */
+int sda_block1d_tile(const sda_block1d_desc* d);
 
 /* ------------------------------------------------------------------------------------------
  * A whole SINGLE-LEVEL 1-D U-Net in ONE launch (the Lorenz score networks, experiments/lorenz/utils.py:26-42;

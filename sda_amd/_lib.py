@@ -283,6 +283,7 @@ SIGNATURES = {
     'sda_gauss_cotangent': (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_float, c_float, c_float, c_float, c_void_p, c_void_p, c_void_p]),
     'sda_block1d_fwd': (c_int, [POINTER(Block1dDesc), c_void_p]),
     'sda_block1d_bwd': (c_int, [POINTER(Block1dDesc), c_void_p]),
+    'sda_block1d_tile': (c_int, [POINTER(Block1dDesc)]),
     'sda_net1d_fwd': (c_int, [POINTER(Net1dDesc), c_void_p]),
     'sda_net1d_bwd': (c_int, [POINTER(Net1dDesc), c_void_p]),
     'sda_net1d_fwd_fused': (c_int, [POINTER(Net1dDesc), POINTER(Net1dFuse), c_void_p]),

@@ -407,13 +407,21 @@ __global__ __launch_bounds__(256) void block1d_bwd_kernel(const sda_block1d_desc
     }
 }
 
-static int block1d_check(const sda_block1d_desc* d, bool bwd) {
+// the shape half of block1d_check: all that the choice of a tile depends on (no pointer is looked at)
+static int block1d_check_shape(const sda_block1d_desc* d) {
     if (!d || d->n < 1 || d->c < 2 || d->c > B1_MAXC || d->len < 1 || d->k_pad > B1_MAXC || d->k_pad % 4 || d->k_pad < d->c ||
-        d->m_pad > B1_MAXC || d->m_pad % 16 || d->m_pad < d->c || !d->a || !d->w1 || !d->w2)
+        d->m_pad > B1_MAXC || d->m_pad % 16 || d->m_pad < d->c)
         return SDA_E_UNSUPPORTED;
+    if ((int64_t)d->n * ((d->len + 15) / 16) > 0x7fffffffLL) return SDA_E_UNSUPPORTED;
+    return SDA_OK;
+}
+
+static int block1d_check(const sda_block1d_desc* d, bool bwd) {
+    const int rc = block1d_check_shape(d);
+    if (rc != SDA_OK) return rc;
+    if (!d->a || !d->w1 || !d->w2) return SDA_E_UNSUPPORTED;
     if (bwd ? (!d->g || !d->gx || !d->z || !d->mean || !d->rstd) : (!d->y || ((d->mean == nullptr) != (d->rstd == nullptr))))
         return SDA_E_BADARG;
-    if ((int64_t)d->n * ((d->len + 15) / 16) > 0x7fffffffLL) return SDA_E_UNSUPPORTED;
     return SDA_OK;
 }
 
@@ -427,6 +435,13 @@ static int block1d_tile(const sda_block1d_desc* d) {
     if ((int64_t)d->n * ((d->len + 15) / 16) <= 1024) return 16;
     if ((int64_t)d->n * ((d->len + 31) / 32) <= 1024) return 32;
     return 64;
+}
+
+// positions per workgroup (16 / 32 / 64) of the launch that serves `d`, forward and VJP alike: host only, no launch, reads
+// the shape fields alone (pointers may be NULL)
+extern "C" int sda_block1d_tile(const sda_block1d_desc* d) {
+    const int rc = block1d_check_shape(d);
+    return rc != SDA_OK ? rc : block1d_tile(d);
 }
 
 extern "C" int sda_block1d_fwd(const sda_block1d_desc* d, void* stream) {

@@ -600,6 +600,15 @@ def block1d_bwd(g: Tensor, a: Tensor, z: Tensor, mean: Tensor, rstd: Tensor, mod
     _bracket_block1d('block1d_bwd', d, lambda: _lib.check(_lib.load().sda_block1d_bwd(ctypes.byref(d), _stream()), 'sda_block1d_bwd'))
 
 
+def block1d_tile(d: '_lib.Block1dDesc') -> int:
+    """Positions per workgroup (16, 32 or 64) of the block1d launch serving ``d``, forward and VJP alike (host only: the shape
+    fields decide, pointers may be unset)."""
+    tile = _lib.load().sda_block1d_tile(ctypes.byref(d))
+    if tile < 1:
+        _lib.check(tile, 'sda_block1d_tile')
+    return tile
+
+
 # ------------------------------------------------------------------------------------------ whole single-level 1-D net
 
 NET1D = os.environ.get('SDA_NET1D', '1') != '0'

@@ -63,6 +63,36 @@ def test_bad_arguments_are_rejected_without_a_gpu():
     assert lib.sda_fold(None, 1, 1, 1, 1, 1, None, None) == -1
 
 
+@pytest.mark.parametrize('n,length,tile', [(1024, 16, 16), (512, 32, 16), (513, 32, 32), (1024, 32, 32), (1025, 16, 64),
+                                           (1025, 32, 64), (342, 97, 64), (1, 16 * 1024, 16), (1, 16 * 1024 + 1, 32),
+                                           (1, 32 * 1024, 32), (1, 32 * 1024 + 1, 64)])
+def test_block1d_tile_boundaries(n, length, tile):
+    """sda_block1d_tile (host only, pointers unset): 16 positions per workgroup while n * ceil(len / 16) <= 1024, else 32 while
+    n * ceil(len / 32) <= 1024, else 64 -- unless SDA_BLOCK1D_TP forces one (the suite runs without it)."""
+    from sda_amd import _lib, ops
+    assert os.environ.get('SDA_BLOCK1D_TP') is None
+    d = _lib.Block1dDesc()
+    d.n, d.c, d.len, d.k_pad, d.m_pad = n, 48, length, 48, 64
+    assert ops.block1d_tile(d) == tile
+    assert _lib.load().sda_block1d_tile(ctypes.byref(d)) == tile
+
+
+def test_block1d_tile_rejects_what_the_launch_rejects():
+    from sda_amd import _lib, ops
+    lib = _lib.load()
+    assert lib.sda_block1d_tile(None) == -2
+    good = dict(n=4, c=48, len=100, k_pad=48, m_pad=64)
+    for bad in (dict(n=0), dict(c=1), dict(c=65, k_pad=68), dict(len=0), dict(k_pad=46), dict(k_pad=44), dict(k_pad=68),
+                dict(m_pad=40), dict(m_pad=32), dict(m_pad=80), dict(n=2 ** 31 - 1, len=17)):
+        d = _lib.Block1dDesc()
+        for f, v in {**good, **bad}.items():
+            setattr(d, f, v)
+        assert lib.sda_block1d_tile(ctypes.byref(d)) == -2, bad
+        with pytest.raises(_lib.SdaHipError):
+            ops.block1d_tile(d)
+        assert lib.sda_block1d_fwd(ctypes.byref(d), None) == -2, bad      # (rejected before anything is launched)
+
+
 def test_lds_plan_for_reference_shapes():
     """K64 layer shapes fit the 160 KiB LDS with room for >= 2 workgroups per CU."""
     from sda_amd import _lib
