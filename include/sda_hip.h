@@ -596,15 +596,22 @@ int sda_adamw_step(const sda_adamw_desc* d, void* stream);
 
 /* The same two launches as the halves of a Gaussian-guided evaluation of a LOCAL score network -- MCScoreNet over a ScoreNet kernel
  * (sda/score.py:134-164, 53-63; experiments/lorenz/utils.py:45-59) inside GaussianScore (score.py:375-396) --, the rows being the
- * nw = len - 2k windows of each of rows / nw trajectories x (B, len, c), (2k + 1) c <= 16:
+ * nw = len - 2k windows of each of rows / nw trajectories x (B, len, c), wc = (2k + 1) c <= 32 (a window's values fill one or two 16-feature
+ * fragments of the kernels; above 32 sda_mlp_fwd_win / sda_mlp_bwd_win return SDA_E_UNSUPPORTED and sda_mc_finish SDA_E_BADARG):
  *   sda_mlp_fwd_win: the loader gathers a window's (2k + 1) c consecutive values and appends the time embedding emb[emb_n]
  *                    (`unfold`, `cat`: in_f[0] = (2k + 1) c + emb_n); the epilogue applies `fold` (score.py:155-164), forms
  *                    eps = (cx0 + cx1 sigma) x + cn s and the likelihood cotangent ghat exactly as sda_net1d_fwd_fused does, and writes both
  *                    as (B, len, c) tensors (d.x / d.out are unused);
- *   sda_mlp_bwd_win: the loader applies fold's adjoint to cn ghat; the window part of the input gradient leaves as gwin [rows][16];
- *   sda_mc_finish:   sums the overlapping windows (unfold's adjoint), adds the affine part, forms the guided score
+ *   sda_mlp_bwd_win: the loader applies fold's adjoint to cn ghat; the window part of the input gradient leaves as gwin [rows][16] when
+ *                    wc <= 16 and as gwin [rows][32] when 16 < wc <= 32 (16-byte aligned; value f of a row at offset f, the rest of the
+ *                    row up to the last whole fragment is written too).  Both sides derive the row stride from nw, len / k and c:
+ *                    there is no stride argument;
+ *   sda_mc_finish:   reads gwin with that stride (wc <= 16 ? 16 : 32), sums the overlapping windows (unfold's adjoint, in ascending slot
+ *                    order), adds the affine part, forms the guided score
  *                    eps - (sigma/mu)(ghat - sigma J_eps^T ghat) and, by mode (as sda_net1d_bwd_fused): 0 writes it; 1 x <- r x + c1 . in
- *                    place; 2 writes it and partial[b] = its sum of squares over the trajectory (one chunk per sample). */
+ *                    place; 2 writes it and partial[b] = its sum of squares over the trajectory (one chunk per sample).
+ * A last GEMM of 17 .. 32 outputs (and its transpose, the VJP's first) is a 128-feature slab like any width above 16: at wc = 21 or 27 these
+ * two multiplies do 128-wide work for 21 or 27 useful columns. */
 typedef struct sda_mlp_win {
     int32_t nw, len, c, emb_n;
     const float* x; const float* emb;

@@ -36,6 +36,10 @@
 //     (tests/test_isa_guard_mlp.py holds that);
 //   * LDS: 2 x 64 KiB unit buffers + 16 KiB of biases = 144 KiB of 160, as the narrow kernels.  The bias region holds every GEMM's
 //     padded bias: sixteen 256-wide GEMMs; beyond that SDA_E_UNSUPPORTED.
+// Window mode (sda_mlp_fwd_win / sda_mlp_bwd_win, sda_hip.h) keeps a row's window values in the first one or two D fragments: windows of at most
+// 16 values run the <true> instances of the four kernels, windows of 17 .. 32 values (Lorenz k = 3, 4) the mlp_win2_* kernels -- the same
+// bodies (mlp1d_kernels.hpp) compiled with ML_WF = 2; the VJP's window gradient gwin has a row of 16 ML_WF floats.  A last GEMM of 17 .. 32
+// outputs is a 128-feature slab, as every width above 16.
 // Roofline: the Lorenz local net is 0.34 MFLOP per window and direction; at 62 464 windows (eval.py's batch) 21.5 GFLOP = 0.14 ms of
 // fp32 MFMA time per direction.
 #include "sda_common.hpp"
@@ -59,411 +63,41 @@ extern "C" int sda_ml_trace_read(long long* out, int reset) {
 #endif
 #include "mlp1d_common.hpp"
 
-// ------------------------------------------------------------------------------------------------------------ forward
-template <bool WIN>
-__global__ __launch_bounds__(256) void mlp_fwd_kernel(const sda_mlp_desc d, const sda_mlp_win w) {
-    extern __shared__ __attribute__((aligned(16))) float ml_lds[];         // two slab buffers
-    MlCtx c;
-    ml_ctx(c, d);
-    ML_T0();
-    MlStage st;
-    // slab 0 -> buffer 0
-    st.src = ml_rsrc(d.w + d.w_off[0]); st.toff = 16u * c.tid;
-    st.dst = reinterpret_cast<ml_f32x4*>(ml_lds) + c.tid;
-    st.npieces = ml_slab_floats(d.in_f[0], d.out_f[0]) / ML_PIECE;
-    for (int p = 0; p < st.npieces; ++p) { ml_f32x4 t[4]; st.issue(t, p); st.commit(t, p); }
-    // every GEMM's bias -> LDS, once (read per GEMM as the C operand of its first MFMAs: from global memory each first MFMA waited a
-    // full L2 round trip -- 14 x ~2 000 cycles of a tile's 120 000 in the GEMM phase)
-    float* const bl = ml_lds + 2 * ML_SLAB;
-    {
-        const int nb = d.b_off[d.ngemm - 1] + 16 * ml_mf(d.out_f[d.ngemm - 1]);
-        for (int i = c.tid; i < nb; i += 256) bl[i] = d.bias[i];
-    }
-    ml_f32x4 h[8], a[8], acc[8], zs[8];
-#pragma unroll
-    for (int m = 0; m < 8; ++m) zs[m] = ml_f32x4{0.f, 0.f, 0.f, 0.f};
-    if constexpr (WIN) {
-        // (inline copy of ml_win_load, see there)  row (b, i): features [0, WC) = x[b][i .. i + 2k][:] -- WC consecutive floats of the trajectory --, then the time embedding
-        const MlWinRow wr = ml_win_row(w, c);
-        const int wc = (w.len - w.nw + 1) * w.c;
-        const float* xr = w.x + ((int64_t)wr.b * w.len + wr.i) * w.c;
-#pragma unroll
-        for (int m = 0; m < 8; ++m)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int f = 16 * m + 4 * c.kq + r;
-                const bool isx = f < wc, ise = !isx && f < wc + w.emb_n;
-                const float xv = xr[isx ? f : 0], ev = w.emb[ise ? f - wc : 0];
-                a[m][r] = !c.rowok ? 0.f : (isx ? xv : (ise ? ev : 0.f));
-            }
-    } else {
-        ml_load_rows(d.x, d.x_ld, d.in_f[0], c, a);
-    }
-    __syncthreads();
-    ML_STAMP(0);                                           // first slab + input rows
-    const bool silu = d.act == SDA_ACT_SILU;
-    int rb = 0;                                            // residual-block counter (index into the saves)
-    MlMeta mc = ml_meta(d, 0), mn = ml_meta(d, 1);
-    for (int g = 0; g < d.ngemm; ++g) {
-        const MlMeta mm = ml_meta(d, g + 2);
-        const float* wl = ml_lds + (g & 1) * ML_SLAB;
-        const bool last = g + 1 == d.ngemm;
-        st.src = ml_rsrc(d.w + (last ? 0 : mn.w_off)); st.toff = 16u * c.tid;
-        st.dst = reinterpret_cast<ml_f32x4*>(ml_lds + ((g + 1) & 1) * ML_SLAB) + c.tid;
-        st.npieces = last ? 0 : ml_slab_floats(mn.in_f, mn.out_f) / ML_PIECE;
-        const int mf = ml_mf(mc.out_f), cw = mc.in_f;
-        // the bias is the C operand of the GEMM's first MFMAs: loaded here, long before it is needed
-        ml_f32x4 bias[8];
-        {
-            const float* bg = bl + mc.b_off + 4 * c.kq;
-#pragma unroll
-            for (int m = 0; m < 8; ++m) bias[m] = m < mf ? *reinterpret_cast<const ml_f32x4*>(bg + 16 * m) : ml_f32x4{0.f, 0.f, 0.f, 0.f};
-        }
-        if (mc.kind == 1) {
-            // ---- residual block, first half: save a; h = LN(a)
-            const float inv_c = 1.f / (float)cw, inv_v = 1.f / (float)(d.unbiased ? cw - 1 : cw);
-            float mean, rstd;
-            auto ln = [&](auto FULL_) { ml_ln<decltype(FULL_)::value>(a, h, cw, c, inv_c, inv_v, d.eps, mean, rstd); };
-            if (cw == 128) ln(std::true_type{});
-            else ln(std::false_type{});
-            if (d.mean_save && c.kq == 0 && c.rowok) {
-                d.mean_save[(int64_t)rb * d.stat_stride + c.row] = mean;
-                d.rstd_save[(int64_t)rb * d.stat_stride + c.row] = rstd;
-            }
-            ML_STAMP(3);                                   // a_save, LayerNorm
-        }
-        ML_STAMP(1);                                       // GEMM set-up (stage descriptor, bias fragments)
-        // the save streams ride the 128 -> 128 multiplies (one store per K quad, see ml_mm): the block input under the block's first
-        // multiply, the pre-activation -- a copy, the accumulators are rewritten -- under its second; other widths store in the epilogue
-        const bool ride = d.z_save && cw == 128 && c.rowok;
-        if (mc.kind == 0) ml_gemm(wl, mc.in_f, mc.out_f, a, acc, bias, st, c, nullptr, a);
-        else if (mc.kind == 1)
-            ml_gemm(wl, mc.in_f, mc.out_f, h, acc, bias, st, c,
-                    ride ? d.a_save + (int64_t)rb * d.save_stride + c.row * d.save_ld + 4 * c.kq : nullptr, a);
-        else
-            ml_gemm(wl, mc.in_f, mc.out_f, h, acc, bias, st, c,
-                    ride ? d.z_save + (int64_t)rb * d.save_stride + c.row * d.save_ld + 4 * c.kq : nullptr, zs);
-        ML_STAMP(2);                                       // GEMM (+ staging)
-        __syncthreads();                                   // slab hand-off: the next slab is complete, this one is free
-        ML_STAMP(5);                                       // hand-off barrier
-        if (mc.kind == 0) {
-#pragma unroll
-            for (int m = 0; m < 8; ++m) a[m] = acc[m];
-        } else if (mc.kind == 1) {
-            // z = W1 LN(a) + b1 (saved); h = act(z)
-            // the saves (block input a, pre-activation z) go out HERE, behind the GEMM whose slab staging has just completed: vmcnt
-            // retires in order, so a store issued in front of staging loads makes the wait for those loads a wait for the store's
-            // round trip to HBM (the block input written before the GEMM cost the forward ~20 %)
-            if (d.z_save && c.rowok && mc.out_f != 128) {
-                float* zp = d.z_save + (int64_t)rb * d.save_stride + c.row * d.save_ld + 4 * c.kq;
-                float* as = d.a_save + (int64_t)rb * d.save_stride + c.row * d.save_ld + 4 * c.kq;
-#pragma unroll
-                for (int m = 0; m < 8; ++m)
-                    if (m < mf) {
-                        *reinterpret_cast<ml_f32x4*>(zp + 16 * m) = acc[m];
-                        *reinterpret_cast<ml_f32x4*>(as + 16 * m) = a[m];
-                    }
-            }
-#pragma unroll
-            for (int m = 0; m < 8; ++m) zs[m] = acc[m];
-            auto epi = [&](auto SILU_) {
-#pragma unroll
-                for (int m = 0; m < 8; ++m)
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) h[m][r] = decltype(SILU_)::value ? sda_act(SDA_ACT_SILU, acc[m][r]) : sda_act(d.act, acc[m][r]);
-            };
-            if (silu) epi(std::true_type{});
-            else epi(std::false_type{});
-        } else {
-#pragma unroll
-            for (int m = 0; m < 8; ++m) a[m] += acc[m];
-            ++rb;
-        }
-        ML_STAMP(4);                                       // epilogue
-        mc = mn; mn = mm;
-    }
-    if constexpr (WIN) ml_win_fold(w, c, a[0]);
-    else ml_store_rows(d.out, d.out_ld, d.out_f[d.ngemm - 1], c, a);
-    ML_STAMP(6);                                           // output
-    ML_DUMP();
-}
+// ------------------------------------------------------------------------------------------------------------ the kernels
+// {forward, VJP} x {rows, windows} x {narrow, wide}; window mode with the window values of a row in one D fragment (at most 16 values) ...
+#define ML_WF 1
+#define ML_K_FWD mlp_fwd_kernel
+#define ML_K_BWD mlp_bwd_kernel
+#define ML_K_FWD_WIDE mlp_fwd_kernel_wide
+#define ML_K_BWD_WIDE mlp_bwd_kernel_wide
+#include "mlp1d_kernels.hpp"
+#undef ML_WF
+#undef ML_K_FWD
+#undef ML_K_BWD
+#undef ML_K_FWD_WIDE
+#undef ML_K_BWD_WIDE
+// ... and in two (17 .. 32 values): only <true> of these is ever instantiated.  Kernels of their own rather than a run-time fragment count in
+// the ones above, so that a window of at most 16 values runs the code it ran, bit for bit (tests/test_isa_guard_mlp_win2.py holds these to
+// the same no-spill rule)
+#define ML_WF 2
+#define ML_K_FWD mlp_win2_fwd
+#define ML_K_BWD mlp_win2_bwd
+#define ML_K_FWD_WIDE mlp_win2_fwd_wide
+#define ML_K_BWD_WIDE mlp_win2_bwd_wide
+#include "mlp1d_kernels.hpp"
+#undef ML_WF
+#undef ML_K_FWD
+#undef ML_K_BWD
+#undef ML_K_FWD_WIDE
+#undef ML_K_BWD_WIDE
 
-// ------------------------------------------------------------------------------------------------------------ input VJP
-// d.w = the slabs of the TRANSPOSED matrices (backward GEMM of forward GEMM g: out_f[g] -> in_f[g], no bias), same offsets table;
-// x = cotangent rows (width out_f[last]), out = input-gradient rows (width in_f[0]); the GEMM list is walked backwards.
-template <bool WIN>
-__global__ __launch_bounds__(256) void mlp_bwd_kernel(const sda_mlp_desc d, const sda_mlp_win w) {
-    extern __shared__ __attribute__((aligned(16))) float ml_lds[];
-    MlCtx c;
-    ml_ctx(c, d);
-    const int gl = d.ngemm - 1;
-    MlStage st;
-    st.src = ml_rsrc(d.w + d.w_off[gl]); st.toff = 16u * c.tid;
-    st.dst = reinterpret_cast<ml_f32x4*>(ml_lds) + c.tid;
-    st.npieces = ml_slab_floats(d.out_f[gl], d.in_f[gl]) / ML_PIECE;
-    for (int p = 0; p < st.npieces; ++p) { ml_f32x4 t[4]; st.issue(t, p); st.commit(t, p); }
-    ml_f32x4 h[8], gacc[8], acc[8], zero[8];
-#pragma unroll
-    for (int m = 0; m < 8; ++m) zero[m] = ml_f32x4{0.f, 0.f, 0.f, 0.f};
-    if constexpr (WIN) {
-        // (inline copy of ml_win_cot, see ml_win_load)  the cotangent of the window outputs = fold's adjoint of cn ghat: slot j of window (b, i) receives ghat[b][i + j] where fold reads it
-        const MlWinRow wr = ml_win_row(w, c);
-        const int k = (w.len - w.nw) / 2, wc = (2 * k + 1) * w.c;
-#pragma unroll
-        for (int m = 0; m < 8; ++m) gacc[m] = ml_f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int f = 4 * c.kq + r, fc = f < wc ? f : 0;
-            const int j = fc / w.c, ch = fc - j * w.c;
-            const bool sel = c.rowok && f < wc && ml_win_sel(wr, j, k);
-            const float gv = w.ghat[sel ? ((int64_t)wr.b * w.len + wr.i + j) * w.c + ch : 0];
-            gacc[0][r] = sel ? gv * w.cn : 0.f;
-        }
-    } else {
-        ml_load_rows(d.x, d.x_ld, d.out_f[gl], c, gacc);
-    }
-    __syncthreads();
-    const bool silu = d.act == SDA_ACT_SILU;
-    int rb = 0;
-    for (int g = 0; g < d.ngemm; ++g) rb += d.kind[g] == 2;
-    int buf = 0;
-    MlMeta mc = ml_meta(d, gl), mn = ml_meta(d, gl - 1);
-    for (int g = gl; g >= 0; --g, buf ^= 1) {
-        const MlMeta mm = ml_meta(d, g - 2);
-        const float* wl = ml_lds + buf * ML_SLAB;
-        const bool last = g == 0;
-        st.src = ml_rsrc(d.w + (last ? 0 : mn.w_off)); st.toff = 16u * c.tid;
-        st.dst = reinterpret_cast<ml_f32x4*>(ml_lds + (buf ^ 1) * ML_SLAB) + c.tid;
-        st.npieces = last ? 0 : ml_slab_floats(mn.out_f, mn.in_f) / ML_PIECE;
-        if (mc.kind == 2) --rb;
-        // what the epilogue reads from the forward: issued before the multiply
-        const int cw = mc.in_f, nm = ml_mf(cw);
-        const int64_t srow = c.rowok ? c.row : 0;
-        ml_f32x4 sv[8];                                    // kind 2: z; kind 1: the block input a
-        float mean = 0.f, rs = 0.f;
-        if (mc.kind != 0) {
-            const float* sp = (mc.kind == 2 ? d.z_save : d.a_save) + (int64_t)rb * d.save_stride + srow * d.save_ld + 4 * c.kq;
-#pragma unroll
-            for (int m = 0; m < 8; ++m) sv[m] = m < nm ? *reinterpret_cast<const ml_f32x4*>(sp + 16 * m) : ml_f32x4{0.f, 0.f, 0.f, 0.f};
-            if (mc.kind == 1) {
-                mean = d.mean_save[(int64_t)rb * d.stat_stride + srow];
-                rs = d.rstd_save[(int64_t)rb * d.stat_stride + srow];
-            }
-        }
-        // the multiply's input: the cotangent g itself (Linear; a block's second half) or q (its first half)
-        if (mc.kind == 1) ml_gemm(wl, mc.out_f, mc.in_f, h, acc, zero, st, c, nullptr, zero);
-        else ml_gemm(wl, mc.out_f, mc.in_f, gacc, acc, zero, st, c, nullptr, zero);
-        __syncthreads();
-        if (mc.kind == 0) {
-#pragma unroll
-            for (int m = 0; m < 8; ++m) gacc[m] = acc[m];
-        } else if (mc.kind == 2) {
-            // q = W2^T g, x act'(z)   (features beyond the width: acc = 0 there, so q = 0 x act'(0) = 0)
-            auto dact = [&](auto SILU_) {
-#pragma unroll
-                for (int m = 0; m < 8; ++m)
-#pragma unroll
-                    for (int r = 0; r < 4; ++r)
-                        h[m][r] = acc[m][r] * (decltype(SILU_)::value ? sda_dact(SDA_ACT_SILU, sv[m][r]) : sda_dact(d.act, sv[m][r]));
-            };
-            if (silu) dact(std::true_type{});
-            else dact(std::false_type{});
-        } else {
-            // gh = W1^T q; g += LN^T(gh) = rstd (gh - mean_c(gh) - x_hat mean'_c(gh x_hat))
-            const float inv_c = 1.f / (float)cw, inv_v = 1.f / (float)(d.unbiased ? cw - 1 : cw);
-            auto lnb = [&](auto FULL_) { ml_ln_bwd<decltype(FULL_)::value>(sv, acc, gacc, cw, c, inv_c, inv_v, mean, rs); };
-            if (cw == 128) lnb(std::true_type{});
-            else lnb(std::false_type{});
-        }
-        mc = mn; mn = mm;
-    }
-    if constexpr (WIN) {
-        // the window part of the input gradient, 16 floats per row (the embedding's part is not formed); sda_mc_finish sums the overlaps
-        if (c.rowok) *reinterpret_cast<ml_f32x4*>(w.gwin + c.row * 16 + 4 * c.kq) = gacc[0];
-    } else {
-        ml_store_rows(d.out, d.out_ld, d.in_f[0], c, gacc);
-    }
-}
-
-template <bool WIN>
-__global__ __launch_bounds__(256) void mlp_fwd_kernel_wide(const sda_mlp_desc d, const sda_mlp_win w) {
-    extern __shared__ __attribute__((aligned(16))) float ml_lds[];         // two unit buffers + the biases
-    MlCtx c;
-    ml_ctx(c, d);
-    MlMeta mc = ml_meta(d, 0), mn = ml_meta(d, 1);
-    MlStage st;
-    st.src = ml_rsrc(d.w + mc.w_off); st.toff = 16u * c.tid;
-    st.dst = reinterpret_cast<ml_f32x4*>(ml_lds) + c.tid;
-    st.npieces = mlw_unit_floats(mc.in_f, mc.out_f) / ML_PIECE;
-    for (int p = 0; p < st.npieces; ++p) { ml_f32x4 t[4]; st.issue(t, p); st.commit(t, p); }
-    float* const bl = ml_lds + 2 * ML_SLAB;
-    {
-        const int nb = d.b_off[d.ngemm - 1] + 16 * mlw_mf(d.out_f[d.ngemm - 1]);
-        for (int i = c.tid; i < nb; i += 256) bl[i] = d.bias[i];
-    }
-    // a = the residual stream, h = a GEMM's input, acc = its output: 3 x 64 registers (+ 64 of A fragments and the staging ones)
-    ml_f32x4 h[16], a[16], acc[16];
-    if constexpr (WIN) ml_win_load(w, c, a);
-    else ml_load_rows(d.x, d.x_ld, d.in_f[0], c, a);
-    __syncthreads();
-    const bool silu = d.act == SDA_ACT_SILU;
-    int rb = 0, buf = 0;
-    for (int g = 0; g < d.ngemm; ++g) {
-        const MlMeta mm = ml_meta(d, g + 2);
-        const bool last = g + 1 == d.ngemm;
-        const int cw = mc.in_f;
-        if (mc.kind == 1) {
-            const float inv_c = 1.f / (float)cw, inv_v = 1.f / (float)(d.unbiased ? cw - 1 : cw);
-            float mean, rstd;
-            if (cw == 256) ml_ln<true>(a, h, cw, c, inv_c, inv_v, d.eps, mean, rstd);
-            else ml_ln<false>(a, h, cw, c, inv_c, inv_v, d.eps, mean, rstd);
-            if (d.mean_save && c.kq == 0 && c.rowok) {
-                d.mean_save[(int64_t)rb * d.stat_stride + c.row] = mean;
-                d.rstd_save[(int64_t)rb * d.stat_stride + c.row] = rstd;
-            }
-        } else if (mc.kind == 0) {
-#pragma unroll
-            for (int m = 0; m < 16; ++m) h[m] = a[m];
-        }
-        mlw_gemm(ml_lds, buf, d.w + mc.w_off, mc.in_f, mc.out_f, d.w + (last ? 0 : mn.w_off),
-                 last ? 0 : mlw_unit_floats(mn.in_f, mn.out_f) / ML_PIECE, h, acc, st, c);
-        {
-            // + the bias, from LDS (as the C operand of the first MFMAs, the narrow kernel's way, its 32 registers come on top of a, h, acc and
-            // the A fragments: spills)
-            const float* bg = bl + mc.b_off + 4 * c.kq;
-            const int nm = mlw_mf(mc.out_f);
-#pragma unroll
-            for (int m = 0; m < 16; ++m)
-                if (m < nm) acc[m] += *reinterpret_cast<const ml_f32x4*>(bg + 16 * m);
-        }
-        if (mc.kind == 0) {
-#pragma unroll
-            for (int m = 0; m < 16; ++m) a[m] = acc[m];
-        } else if (mc.kind == 1) {
-            // z = W1 LN(a) + b1; both saved streams leave here, behind the GEMM (see the narrow kernel); h = act(z)
-            if (d.z_save && c.rowok) {
-                const int nm = mlw_mf(mc.out_f);
-                float* zp = d.z_save + (int64_t)rb * d.save_stride + c.row * d.save_ld + 4 * c.kq;
-                float* as = d.a_save + (int64_t)rb * d.save_stride + c.row * d.save_ld + 4 * c.kq;
-#pragma unroll
-                for (int m = 0; m < 16; ++m)
-                    if (m < nm) {
-                        *reinterpret_cast<ml_f32x4*>(zp + 16 * m) = acc[m];
-                        *reinterpret_cast<ml_f32x4*>(as + 16 * m) = a[m];
-                    }
-            }
-            auto epi = [&](auto SILU_) {
-#pragma unroll
-                for (int m = 0; m < 16; ++m) {
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) h[m][r] = decltype(SILU_)::value ? sda_act(SDA_ACT_SILU, acc[m][r]) : sda_act(d.act, acc[m][r]);
-                    // (64 independent chains: left free, the scheduler interleaves them all and their temporaries spill)
-                    if (m & 1) __builtin_amdgcn_sched_barrier(0);
-                }
-            };
-            if (silu) epi(std::true_type{});
-            else epi(std::false_type{});
-        } else {
-#pragma unroll
-            for (int m = 0; m < 16; ++m) a[m] += acc[m];
-            ++rb;
-        }
-        mc = mn; mn = mm;
-    }
-    if constexpr (WIN) ml_win_fold(w, c, a[0]);
-    else ml_store_rows(d.out, d.out_ld, d.out_f[d.ngemm - 1], c, a);
-}
-
-template <bool WIN>
-__global__ __launch_bounds__(256) void mlp_bwd_kernel_wide(const sda_mlp_desc d, const sda_mlp_win w) {
-    extern __shared__ __attribute__((aligned(16))) float ml_lds[];
-    MlCtx c;
-    ml_ctx(c, d);
-    const int gl = d.ngemm - 1;
-    MlMeta mc = ml_meta(d, gl), mn = ml_meta(d, gl - 1);
-    MlStage st;
-    st.src = ml_rsrc(d.w + mc.w_off); st.toff = 16u * c.tid;
-    st.dst = reinterpret_cast<ml_f32x4*>(ml_lds) + c.tid;
-    st.npieces = mlw_unit_floats(mc.out_f, mc.in_f) / ML_PIECE;
-    for (int p = 0; p < st.npieces; ++p) { ml_f32x4 t[4]; st.issue(t, p); st.commit(t, p); }
-    // gacc = the cotangent of the residual stream, h = a GEMM's input, acc = its output
-    ml_f32x4 h[16], gacc[16], acc[16];
-    if constexpr (WIN) ml_win_cot(w, c, gacc);
-    else ml_load_rows(d.x, d.x_ld, d.out_f[gl], c, gacc);
-    __syncthreads();
-    const bool silu = d.act == SDA_ACT_SILU;
-    int rb = 0, buf = 0;
-    for (int g = 0; g < d.ngemm; ++g) rb += d.kind[g] == 2;
-    for (int g = gl; g >= 0; --g) {
-        const MlMeta mm = ml_meta(d, g - 2);
-        const bool last = g == 0;
-        if (mc.kind == 2) --rb;
-        const int cw = mc.in_f, nm = mlw_mf(cw);
-        const int64_t srow = c.rowok ? c.row : 0;
-        if (mc.kind != 1) {
-#pragma unroll
-            for (int m = 0; m < 16; ++m) h[m] = gacc[m];
-        }
-        mlw_gemm(ml_lds, buf, d.w + mc.w_off, mc.out_f, mc.in_f, d.w + (last ? 0 : mn.w_off),
-                 last ? 0 : mlw_unit_floats(mn.out_f, mn.in_f) / ML_PIECE, h, acc, st, c);
-        // What the epilogue reads from the forward is fetched BEHIND the multiply (in front of it, as the narrow kernel does, its 64 registers
-        // would be live under 1024 MFMAs next to gacc, h, acc and the A fragments).  The vector ALU reads the 256 architectural registers
-        // only: with gacc, acc and h in them the pre-activations come in groups of four fragments, one group ahead of its use.
-        const int64_t soff = (int64_t)rb * d.save_stride + srow * d.save_ld + 4 * c.kq;
-        if (mc.kind == 0) {
-#pragma unroll
-            for (int m = 0; m < 16; ++m) gacc[m] = acc[m];
-        } else if (mc.kind == 2) {
-            const float* sp = d.z_save + soff;
-            // q = W2^T g, x act'(z)   (features beyond the width: acc = 0 there, so q = 0 x act'(0) = 0)
-            auto dact = [&](auto SILU_) {
-                ml_f32x4 zb[2][4];
-                auto fetch = [&](int grp) {
-#pragma unroll
-                    for (int i = 0; i < 4; ++i)
-                        zb[grp & 1][i] = 4 * grp + i < nm ? *reinterpret_cast<const ml_f32x4*>(sp + 16 * (4 * grp + i)) : ml_f32x4{0.f, 0.f, 0.f, 0.f};
-                };
-                fetch(0);
-#pragma unroll
-                for (int grp = 0; grp < 4; ++grp) {
-                    if (grp < 3) fetch(grp + 1);
-#pragma unroll
-                    for (int i = 0; i < 4; ++i)
-#pragma unroll
-                        for (int r = 0; r < 4; ++r) {
-                            const float z = zb[grp & 1][i][r];
-                            h[4 * grp + i][r] = acc[4 * grp + i][r] * (decltype(SILU_)::value ? sda_dact(SDA_ACT_SILU, z) : sda_dact(d.act, z));
-                        }
-                    __builtin_amdgcn_sched_barrier(0);
-                }
-            };
-            if (silu) dact(std::true_type{});
-            else dact(std::false_type{});
-        } else {
-            // gh = W1^T q; g += LN^T(gh)
-            const float* sp = d.a_save + soff;
-            ml_f32x4 sv[16];                               // the block input
-#pragma unroll
-            for (int m = 0; m < 16; ++m) sv[m] = m < nm ? *reinterpret_cast<const ml_f32x4*>(sp + 16 * m) : ml_f32x4{0.f, 0.f, 0.f, 0.f};
-            const float mean = d.mean_save[(int64_t)rb * d.stat_stride + srow], rs = d.rstd_save[(int64_t)rb * d.stat_stride + srow];
-            const float inv_c = 1.f / (float)cw, inv_v = 1.f / (float)(d.unbiased ? cw - 1 : cw);
-            if (cw == 256) ml_ln_bwd<true>(sv, acc, gacc, cw, c, inv_c, inv_v, mean, rs);
-            else ml_ln_bwd<false>(sv, acc, gacc, cw, c, inv_c, inv_v, mean, rs);
-        }
-        mc = mn; mn = mm;
-    }
-    if constexpr (WIN) {
-        if (c.rowok) *reinterpret_cast<ml_f32x4*>(w.gwin + c.row * 16 + 4 * c.kq) = gacc[0];
-    } else {
-        ml_store_rows(d.out, d.out_ld, d.in_f[0], c, gacc);
-    }
-}
-
-
-static int mlp_win_check(const sda_mlp_desc* d, const sda_mlp_win* w, bool bwd) {
+// (*two: the window takes two D fragments -- the mlp_win2 kernels and a gwin row of 32 floats)
+static int mlp_win_check(const sda_mlp_desc* d, const sda_mlp_win* w, bool bwd, bool* two) {
     if (!w || w->nw < 1 || w->c < 1 || w->len < w->nw || ((w->len - w->nw) & 1)) return SDA_E_BADARG;
-    const int wc = (w->len - w->nw + 1) * w->c;
-    if (wc > 16) return SDA_E_UNSUPPORTED;                 // (the window values of a row live in one D fragment)
+    const int64_t wc64 = (int64_t)(w->len - w->nw + 1) * w->c;
+    if (wc64 > 32) return SDA_E_UNSUPPORTED;               // (the window values of a row live in at most two D fragments)
+    const int wc = (int)wc64;
+    *two = wc > 16;
     if (d->rows % w->nw || !w->ghat || !w->coef) return SDA_E_BADARG;
     if (d->out_f[d->ngemm - 1] != wc) return SDA_E_BADARG;
     if (!bwd) {
@@ -479,17 +113,22 @@ static int mlp_win_check(const sda_mlp_desc* d, const sda_mlp_win* w, bool bwd) 
 
 template <bool BWD, bool WIN>
 static int mlp_launch(const sda_mlp_desc* d, const sda_mlp_win* w, hipStream_t stream) {
-    bool wide = false;
+    bool wide = false, two = false;
     int rc = mlp_check(d, BWD, WIN, &wide);
     if (rc != SDA_OK) return rc;
-    if (WIN && (rc = mlp_win_check(d, w, BWD)) != SDA_OK) return rc;
+    if (WIN && (rc = mlp_win_check(d, w, BWD, &two)) != SDA_OK) return rc;
     const int64_t tiles = ((int64_t)d->rows + 63) / 64;
     if (tiles > 0x7fffffffLL) return SDA_E_UNSUPPORTED;
     constexpr int lds = (2 * ML_SLAB + ML_BIAS) * 4;
-    static bool raised[2][SDA_MAX_DEVICES];
-    void (*const kern)(sda_mlp_desc, sda_mlp_win) = wide ? (BWD ? mlp_bwd_kernel_wide<WIN> : mlp_fwd_kernel_wide<WIN>)
-                                                         : (BWD ? mlp_bwd_kernel<WIN> : mlp_fwd_kernel<WIN>);
-    const int rr = sda_raise_dyn_lds(reinterpret_cast<const void*>(kern), lds, raised[wide]);
+    static bool raised[4][SDA_MAX_DEVICES];
+    // (the two-fragment kernels are named first: instantiated in that order, the object's last function stays mlp_fwd_kernel<true>, whose pinned
+    // instruction count -- tests/test_isa_guard_mlp.py -- has no alignment padding behind it)
+    void (*kern)(sda_mlp_desc, sda_mlp_win) = nullptr;
+    if constexpr (WIN) {
+        if (two) kern = wide ? (BWD ? mlp_win2_bwd_wide<true> : mlp_win2_fwd_wide<true>) : (BWD ? mlp_win2_bwd<true> : mlp_win2_fwd<true>);
+    }
+    if (!kern) kern = wide ? (BWD ? mlp_bwd_kernel_wide<WIN> : mlp_fwd_kernel_wide<WIN>) : (BWD ? mlp_bwd_kernel<WIN> : mlp_fwd_kernel<WIN>);
+    const int rr = sda_raise_dyn_lds(reinterpret_cast<const void*>(kern), lds, raised[2 * two + wide]);
     if (rr != SDA_OK) return rr;
     sda_mlp_win wv = {};
     if (WIN) wv = *w;

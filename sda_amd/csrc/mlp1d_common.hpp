@@ -288,8 +288,10 @@ __device__ __forceinline__ void ml_win_load(const sda_mlp_win& w, const MlCtx& c
         }
     }
 }
-// the forward epilogue of window mode; a0 = the wave's output fragment (the window values of a row live in one D fragment)
-__device__ __forceinline__ void ml_win_fold(const sda_mlp_win& w, const MlCtx& c, const ml_f32x4& a0) {
+// the forward epilogue of window mode; a = the wave's output fragments, of which the first WF (1: a window of at most 16 values, 2: of 17 .. 32)
+// hold the window values of a row.  (WF = 1 is the code of the one-fragment version, value for value.)
+template <int WF, int NF>
+__device__ __forceinline__ void ml_win_fold(const sda_mlp_win& w, const MlCtx& c, const ml_f32x4 (&a)[NF]) {
     // fold (score.py:155-164) + eps = (cx0 + cx1 sigma) x + cn s + the likelihood cotangent, as sda_net1d_fwd_fused's epilogue
     if (c.rowok) {
         const MlWinRow wr = ml_win_row(w, c);
@@ -302,29 +304,31 @@ __device__ __forceinline__ void ml_win_fold(const sda_mlp_win& w, const MlCtx& c
         const int n_oc = (w.c_stop - w.c_start + w.c_step - 1) / w.c_step;
         const float* yb = w.y + (int64_t)wr.b * w.y_sn;
 #pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int f = 4 * c.kq + r;
-            if (f >= wc) continue;
-            const int j = f / w.c, ch = f - j * w.c;
-            if (!ml_win_sel(wr, j, k)) continue;
-            const int ps = wr.i + j;
-            const int64_t o = ((int64_t)wr.b * w.len + ps) * w.c + ch;
-            const float xv = w.x[o];
-            const float ov = a0[r];
-            const float e = bare ? ov : (xv * cx) + (w.cn * ov);
-            w.eps[o] = e;
-            const int crel = ch - w.c_start, prel = ps - w.p_start;
-            float gv = 0.f;
-            if (crel >= 0 && ch < w.c_stop && crel % w.c_step == 0 && prel >= 0 && ps < w.p_stop && prel % w.p_step == 0) {
-                const float xh = (xv - sg * e) / mu;
-                gv = __fdiv_rn(yb[(prel / w.p_step) * n_oc + crel / w.c_step] - xh, var);
+        for (int m = 0; m < WF; ++m)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int f = 16 * m + 4 * c.kq + r;
+                if (f >= wc) continue;
+                const int j = f / w.c, ch = f - j * w.c;
+                if (!ml_win_sel(wr, j, k)) continue;
+                const int ps = wr.i + j;
+                const int64_t o = ((int64_t)wr.b * w.len + ps) * w.c + ch;
+                const float xv = w.x[o];
+                const float ov = a[m][r];
+                const float e = bare ? ov : (xv * cx) + (w.cn * ov);
+                w.eps[o] = e;
+                const int crel = ch - w.c_start, prel = ps - w.p_start;
+                float gv = 0.f;
+                if (crel >= 0 && ch < w.c_stop && crel % w.c_step == 0 && prel >= 0 && ps < w.p_stop && prel % w.p_step == 0) {
+                    const float xh = (xv - sg * e) / mu;
+                    gv = __fdiv_rn(yb[(prel / w.p_step) * n_oc + crel / w.c_step] - xh, var);
+                }
+                w.ghat[o] = gv;
             }
-            w.ghat[o] = gv;
-        }
     }
 }
 // the VJP's loader of window mode
-template <int NF>
+template <int WF, int NF>
 __device__ __forceinline__ void ml_win_cot(const sda_mlp_win& w, const MlCtx& c, ml_f32x4 (&gacc)[NF]) {
     // the cotangent of the window outputs = fold's adjoint of cn ghat: slot j of window (b, i) receives ghat[b][i + j] where fold reads it
     const MlWinRow wr = ml_win_row(w, c);
@@ -332,13 +336,23 @@ __device__ __forceinline__ void ml_win_cot(const sda_mlp_win& w, const MlCtx& c,
 #pragma unroll
     for (int m = 0; m < NF; ++m) gacc[m] = ml_f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-    for (int r = 0; r < 4; ++r) {
-        const int f = 4 * c.kq + r, fc = f < wc ? f : 0;
-        const int j = fc / w.c, ch = fc - j * w.c;
-        const bool sel = c.rowok && f < wc && ml_win_sel(wr, j, k);
-        const float gv = w.ghat[sel ? ((int64_t)wr.b * w.len + wr.i + j) * w.c + ch : 0];
-        gacc[0][r] = sel ? gv * w.cn : 0.f;
-    }
+    for (int m = 0; m < WF; ++m)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int f = 16 * m + 4 * c.kq + r, fc = f < wc ? f : 0;
+            const int j = fc / w.c, ch = fc - j * w.c;
+            const bool sel = c.rowok && f < wc && ml_win_sel(wr, j, k);
+            const float gv = w.ghat[sel ? ((int64_t)wr.b * w.len + wr.i + j) * w.c + ch : 0];
+            gacc[m][r] = sel ? gv * w.cn : 0.f;
+        }
+}
+// the VJP's store of window mode: the window part of the input gradient, gwin[row][16 WF] (a row's stride follows its window: 16 floats up
+// to 16 values, 32 above -- sda_mc_finish reads it by the same rule)
+template <int WF, int NF>
+__device__ __forceinline__ void ml_win_gstore(const sda_mlp_win& w, const MlCtx& c, const ml_f32x4 (&gacc)[NF]) {
+    if (!c.rowok) return;
+#pragma unroll
+    for (int m = 0; m < WF; ++m) *reinterpret_cast<ml_f32x4*>(w.gwin + c.row * (16 * WF) + 16 * m + 4 * c.kq) = gacc[m];
 }
 
 // ------------------------------------------------------------------------------------------------------------ wide nets (a width in 129 .. 256)

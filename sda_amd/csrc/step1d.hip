@@ -325,13 +325,15 @@ extern "C" int sda_pc_correct_keyed(float* x, const float* eps, int b, int64_t p
 // of the input gradient (`unfold`'s adjoint, sda/score.py:146-153 -- the one place overlaps add), the estimator's affine part, the
 // guided score eps - (sigma/mu)(ghat - sigma J^T ghat) (score.py:394-396) and, by mode, what sda_net1d_bwd_fused's epilogue does:
 // 0 write it; 1 x <- r x + c1 . in place; 2 write it and the trajectory's sum of squares into partial[b] (one chunk per sample).
-// One workgroup per trajectory (L x C elements: 195 for the Lorenz job).
+// One workgroup per trajectory (L x C elements: 195 for the Lorenz job).  A window is at most 32 values; gwin is [rows][16] for windows of at
+// most 16 values and [rows][32] above.
 __global__ __launch_bounds__(256) void mc_finish_kernel(const float* __restrict__ eps, const float* __restrict__ ghat,
                                                         const float* __restrict__ gwin, int nw, int k, int c, float cx0, float cx1,
                                                         const float* __restrict__ coef, int mode, float* __restrict__ out, float* xs,
                                                         const float* __restrict__ step_coef, float* __restrict__ partial) {
     __shared__ float wsum[4];
     const int b = blockIdx.x, L = nw + 2 * k, per = L * c;
+    const int gld = (2 * k + 1) * c <= 16 ? 16 : 32;       // gwin's row stride: as sda_mlp_bwd_win wrote it (one D fragment per row, or two)
     const float mu = coef[0], sg = coef[1];
     const float cx = cx0 + cx1 * sg, kk = sg / mu;
     const bool bare = cx0 == 0.f && cx1 == 0.f;
@@ -343,7 +345,7 @@ __global__ __launch_bounds__(256) void mc_finish_kernel(const float* __restrict_
         float gx = 0.f;
         for (int j = 0; j <= 2 * k; ++j) {                 // (ascending j: sda_unfold_adjoint's order)
             const int i = l - j;
-            if (i >= 0 && i < nw) gx += gwin[((int64_t)b * nw + i) * 16 + j * c + ch];
+            if (i >= 0 && i < nw) gx += gwin[((int64_t)b * nw + i) * gld + j * c + ch];
         }
         const int64_t o = (int64_t)b * per + e;
         const float gv = ghat[o];
@@ -362,7 +364,7 @@ __global__ __launch_bounds__(256) void mc_finish_kernel(const float* __restrict_
 
 extern "C" int sda_mc_finish(const float* eps, const float* ghat, const float* gwin, int b, int nw, int k, int c, float cx0, float cx1,
                              const float* coef, int mode, float* out, float* xs, const float* step_coef, float* partial, void* stream) {
-    if (!eps || !ghat || !gwin || !coef || b <= 0 || nw <= 0 || k < 0 || c <= 0 || (2 * k + 1) * c > 16 || mode < 0 || mode > 2)
+    if (!eps || !ghat || !gwin || !coef || b <= 0 || nw <= 0 || k < 0 || c <= 0 || (2 * (int64_t)k + 1) * c > 32 || mode < 0 || mode > 2)
         return SDA_E_BADARG;
     if ((mode != 1 && !out) || (mode == 1 && (!xs || !step_coef)) || (mode == 2 && !partial)) return SDA_E_BADARG;
     hipLaunchKernelGGL(mc_finish_kernel, dim3(b), dim3(256), 0, (hipStream_t)stream, eps, ghat, gwin, nw, k, c, cx0, cx1, coef, mode, out,

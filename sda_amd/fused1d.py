@@ -172,7 +172,8 @@ class FusedLocal:
         self.eps = torch.empty(B, L, C, device=dev, dtype=torch.float32)
         self.ghat = torch.empty_like(self.eps)
         self.out = torch.empty_like(self.eps)
-        self.gwin = torch.empty(self.rows, 16, device=dev, dtype=torch.float32)
+        # (the row stride sda_mlp_bwd_win and sda_mc_finish derive from the window: one 16-value fragment per row, or two)
+        self.gwin = torch.empty(self.rows, 16 if (2 * self.k + 1) * C <= 16 else 32, device=dev, dtype=torch.float32)
         nres = max(mplan.nres, 1)
         self.a_s = torch.empty(nres, self.rows, mplan.save_ld, device=dev, dtype=torch.float32)
         self.z_s = torch.empty_like(self.a_s)
@@ -255,7 +256,7 @@ def _plan_local(gs, m, affine, x: Tensor, pos, chan, y_sn: int, sched, key_extra
     B, L, C = x.shape
     k = m.order
     wc = (2 * k + 1) * C
-    if L - 2 * k < 1 or wc > 16:
+    if L - 2 * k < 1 or wc > 32:
         return None
     mplan = mlp._fused_plan(list(kern.network))
     emb = kern.embedding

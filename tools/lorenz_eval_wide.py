@@ -4,7 +4,8 @@
 (experiments/lorenz/train.py:30-44); bench.py's lorenz_eval runs make_local_score()'s default 128.  Same six runs as bench.run_lorenz_eval,
 each replayed from a captured hipGraph; one JSON object on stdout (and in --json FILE).
 
-    python tools/lorenz_eval_wide.py [--width 256] [--repeats 3] [--freq lo] [--json FILE]
+    python tools/lorenz_eval_wide.py [--width 256] [--window 5] [--repeats 3] [--freq lo] [--json FILE]
+    python tools/lorenz_eval_wide.py --window 7 ...             # eval.py's k = 3 checkpoint (k = 4: --window 9)
     SDA_MLP_FUSED=0 python tools/lorenz_eval_wide.py ...        # the per-layer route, the A/B partner
 """
 import argparse
@@ -24,6 +25,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--width', type=int, default=256)
     ap.add_argument('--depth', type=int, default=5)
+    ap.add_argument('--window', type=int, default=5, help='states per window, 2k + 1 (eval.py: 3, 5, 7, 9)')
     ap.add_argument('--repeats', type=int, default=3)
     ap.add_argument('--freq', default='lo', choices=sorted(bench.LORENZ_EVAL_FREQ))
     ap.add_argument('--batch', type=int, default=1024)
@@ -36,7 +38,7 @@ def main():
     step, std = bench.LORENZ_EVAL_FREQ[args.freq]
     B, L, S, steps = args.batch, 65, 3, 256
     torch.manual_seed(0)
-    net = make_local_score(width=args.width, depth=args.depth)
+    net = make_local_score(window=args.window, width=args.width, depth=args.depth)
     score = bench.SyntheticScore(net)
     inner = VPSDE(score, shape=())
     object.__setattr__(score, '_sched', inner)
@@ -63,7 +65,7 @@ def main():
             loop_s += time.perf_counter() - t1
             finite = finite and bool(torch.isfinite(sampler.result()).all().item())
         totals.append(loop_s)
-    out = {'workload': 'lorenz_eval protocol, local net', 'width': args.width, 'depth': args.depth, 'freq': args.freq, 'batch': B,
+    out = {'workload': 'lorenz_eval protocol, local net', 'width': args.width, 'depth': args.depth, 'window': args.window, 'freq': args.freq, 'batch': B,
            'mlp_fused': mlp.FUSED, 'fused1d': fused1d.ENABLED, 'route': route, 'score_evals': steps * 37, 'six_run_sampling_s': totals,
            'min_s': min(totals), 'median_s': statistics.median(totals), 'max_s': max(totals),
            'ms_per_score_eval_median': statistics.median(totals) / (steps * 37) * 1e3, 'samples_finite': finite}
