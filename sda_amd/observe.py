@@ -93,6 +93,8 @@ class Subsample(LinearObservation):
                 n_eff = n
             start.append(a); step.append(c); stop_ok.append(n_eff)
         # fold leading dims so that there are exactly 5
+        if len(size) > 5 and lead == 1:     # five sliced dims and nothing (or only 1s) in front of them
+            del size[0], start[0], step[0]
         while len(size) < 5:
             size.insert(0, 1); start.insert(0, 0); step.insert(0, 1)
         if len(size) > 5:
@@ -136,6 +138,8 @@ class Subsample(LinearObservation):
         if x.dtype != torch.float32 or eps.dtype != torch.float32 or y.dtype != torch.float32:
             return None
         xs, es, ys = x.contiguous(), eps.contiguous(), y.contiguous()
+        if 0 in oshape:                     # nothing observed: A^T of an empty residual
+            return torch.zeros_like(xs)
         size, start, step, stops = self._spec(xs.shape)
         stop = self._stop(size, stops)
         g = torch.empty_like(xs)
@@ -148,6 +152,8 @@ class Subsample(LinearObservation):
     def adjoint(self, r: Tensor, x_shape) -> Tensor:
         ops._dev(r)
         x_shape = tuple(x_shape)
+        if r.numel() == 0:                  # an empty slice observes nothing: the gradient is zero (as autograd gives)
+            return torch.zeros(x_shape, device=r.device, dtype=torch.float32)
         size, start, step, stops = self._spec(x_shape)
         gx = torch.empty(x_shape, device=r.device, dtype=torch.float32)
         _lib.check(_lib.load().sda_obs_subsample_adjoint(r.contiguous().data_ptr(), _I5(*size), _I5(*start), _I5(*step),
@@ -318,7 +324,10 @@ class Mask(LinearObservation):
         ops._dev(x)
         xs = x.contiguous()
         m = self._m(xs.device)
-        if tuple(xs.shape[xs.dim() - m.dim():]) != tuple(m.shape):
+        ms = tuple(m.shape)
+        while ms and ms[0] == 1 and len(ms) <= xs.dim():     # leading 1s broadcast like the dims that are not there
+            ms = ms[1:]
+        if len(ms) > xs.dim() or tuple(xs.shape[xs.dim() - len(ms):]) != ms:
             raise _lib.SdaHipError(f'Mask: mask shape {tuple(m.shape)} does not match the trailing dims of {tuple(xs.shape)}')
         out = torch.empty_like(xs)
         _lib.check(_lib.load().sda_obs_mask(xs.data_ptr(), xs.numel(), m.data_ptr(), m.numel(), out.data_ptr(), _stream()),

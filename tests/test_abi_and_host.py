@@ -63,6 +63,42 @@ def test_bad_arguments_are_rejected_without_a_gpu():
     assert lib.sda_fold(None, 1, 1, 1, 1, 1, None, None) == -1
 
 
+def test_observation_entries_refuse_bad_geometry_before_any_launch():
+    """sda_obs_*: every refused geometry returns SDA_E_BADARG (-1) from the host-side checks; the pointers are never read."""
+    from sda_amd import _lib
+    lib = _lib.load()
+    P, I5 = 0x10000, ctypes.c_int * 5
+    size, zero, one = [1, 1, 2, 4, 4], [0] * 5, [1] * 5
+
+    def sub(start=zero, step=one, stop=size):
+        a = (I5(*size), I5(*start), I5(*step), I5(*stop))
+        return (lib.sda_obs_subsample(P, *a, P, None), lib.sda_obs_subsample_adjoint(P, *a, P, None),
+                lib.sda_obs_subsample_guidance(P, P, P, 1, *a, 0.5, 0.0, 1.0, 0.5, None, P, None))
+    assert sub(step=[1, 1, 1, 0, 1]) == (-1, -1, -1)                  # step <= 0
+    assert sub(step=[1, 1, 1, 1, -2]) == (-1, -1, -1)
+    assert sub(start=[0, 0, 0, 4, 0]) == (-1, -1, -1)                 # start >= size
+    assert sub(start=[0, 0, 0, 0, -1]) == (-1, -1, -1)
+    assert sub(stop=[1, 1, 2, 5, 4]) == (-1, -1, -1)                  # stop past the extent
+    assert sub(start=[0, 0, 0, 2, 0], stop=[1, 1, 2, 2, 4]) == (-1, -1, -1)      # nothing selected
+    a = (I5(*size), I5(*zero), I5(*one), I5(*size))
+    assert lib.sda_obs_subsample_guidance(P, P, P, 5, *a, 0.5, 0.0, 1.0, 0.5, None, P, None) == -1      # 32 % 5 != 0
+    assert lib.sda_obs_subsample_guidance(P, P, P, 0, *a, 0.5, 0.0, 1.0, 0.5, None, P, None) == -1
+    for h, w, f in ((9, 8, 2), (8, 9, 2), (8, 8, 3), (8, 8, 0)):      # h % f != 0, w % f != 0
+        assert lib.sda_obs_coarsen(P, 1, h, w, f, P, None) == -1
+        assert lib.sda_obs_coarsen_adjoint(P, 1, h, w, f, P, None) == -1
+    for h, w in ((2, 8), (8, 2), (0, 8)):                             # h < 3, w < 3
+        assert lib.sda_obs_vorticity(P, 1, h, w, P, None) == -1
+        assert lib.sda_obs_vorticity_adjoint(P, 1, h, w, P, None) == -1
+    for kind in (0, 5):
+        assert lib.sda_obs_pointwise(P, 8, kind, P, None) == -1
+        assert lib.sda_obs_pointwise_vjp(P, P, 8, kind, P, None) == -1
+    assert lib.sda_obs_mask(P, 10, P, 4, P, None) == -1               # the mask does not tile the data
+    for i, j in ((5, 0), (0, 5), (-1, 0)):
+        assert lib.sda_obs_timediff(P, 2, 5, 3, i, j, P, None) == -1
+        assert lib.sda_obs_timediff_adjoint(P, 2, 5, 3, i, j, P, None) == -1
+    assert lib.sda_obs_subsample(None, *a, P, None) == -1 and lib.sda_obs_mask(P, 8, None, 4, P, None) == -1
+
+
 @pytest.mark.parametrize('n,length,tile', [(1024, 16, 16), (512, 32, 16), (513, 32, 32), (1024, 32, 32), (1025, 16, 64),
                                            (1025, 32, 64), (342, 97, 64), (1, 16 * 1024, 16), (1, 16 * 1024 + 1, 32),
                                            (1, 32 * 1024, 32), (1, 32 * 1024 + 1, 64)])
