@@ -593,6 +593,32 @@ typedef struct sda_adamw_desc {
     int32_t blk0[SDA_ADAMW_MAXT + 1];                  /* filled by sda_adamw_step */
 } sda_adamw_desc;
 int sda_adamw_step(const sda_adamw_desc* d, void* stream);
+/* The same launch for a replayed (hipGraph) training step (additive, ABI stays v14): row table[irow[0]] = {decay, step_size, rsqrt_bc2} of a
+ *   device table replaces the descriptor's three by-value fields of those names (which are not read); everything else -- the checks, blk0,
+ *   the per-thread update, the pack epilogue -- is sda_adamw_step's.  irow: a device int64 scalar the caller keeps inside the table and
+ *   advances on the device after the step's last launch.  SDA_E_BADARG also for a null table or irow. */
+int sda_adamw_step_dev(const sda_adamw_desc* d, const float* table, const int64_t* irow, void* stream);
+
+/* The denoising loss of the training route as replayable launches (csrc/train_loss.hip; additive, ABI stays v14): what
+ * `t = torch.rand(B); eps = randn_like(x); xt = mu(t) x + sigma(t) eps; ((net(xt, t) - eps)**2).mean()` (sda/score.py:195-223, 265-276)
+ * makes of some fifteen torch launches and two draws of torch's generator.
+ * sda_loss_perturb: x [rows][per_row] -> t [rows], eps and xt [rows][per_row] in one launch.  eps[b] is BY DEFINITION row row0 + b of
+ *   sda_randn_rows(seed, draw = 2 s); t[b] = ((w0 >> 8) + 0.5) 2^-24 in (0, 1), w0 = word 0 of the same generator at quad 0 of row row0 + b in
+ *   draw 2 s + 1.  s = step_dev[0] (a device int64 scalar: the launch is hipGraph-replayable) or, with step_dev NULL, `step`.  mu(t[b]) and
+ *   sigma(t[b]) are sda_vp_schedule's (same device function, same alpha_kind / eta / k / sigma_kind); xt = mu x + sigma eps, two products and
+ *   a sum, each rounded on its own.  SDA_E_BADARG: a null pointer, rows < 1, per_row < 1, row0 < 0, step < 0, an unknown kind;
+ *   SDA_E_UNSUPPORTED: more than 2^31 - 1 workgroups (rows * ceil(per_row / 1024)).
+ * sda_loss_mse: loss[0] = mean((out - eps)^2) over numel contiguous elements and, with g != NULL, g = (2 / numel) (out - eps) -- the
+ *   loss's cotangent at out for an upstream gradient of 1 (difference, fp32 scale 2 / numel, product: three roundings).  Two ordered stages
+ *   (per-workgroup partial sums into `work`, then one workgroup in index order), no float atomics: bitwise reproducible.  `work` holds
+ *   sda_loss_mse_plan(numel, ...) floats.
+ * sda_loss_mse_plan: floats of `work` = workgroups of stage 1 (*blocks; chunks of 4096 elements), and *chain = the longest chain of
+ *   additions any term passes through: 16 in its thread, 6 + 3 in its workgroup's tree, ceil(blocks / 256) in stage 2's thread, 6 + 3 in
+ *   stage 2's tree.  Either pointer may be NULL.  < 0: SDA_E_BADARG (numel < 1) / SDA_E_UNSUPPORTED (more than 2^31 - 1 workgroups). */
+int sda_loss_perturb(const float* x, int rows, int64_t per_row, uint64_t seed, int64_t row0, int64_t step, const int64_t* step_dev,
+                     int alpha_kind, float eta, float k, int sigma_kind, float* t, float* eps, float* xt, void* stream);
+int64_t sda_loss_mse_plan(int64_t numel, int* blocks, int* chain);
+int sda_loss_mse(const float* out, const float* eps, int64_t numel, float* loss, float* g, float* work, void* stream);
 
 /* The same two launches as the halves of a Gaussian-guided evaluation of a LOCAL score network -- MCScoreNet over a ScoreNet kernel
  * (sda/score.py:134-164, 53-63; experiments/lorenz/utils.py:45-59) inside GaussianScore (score.py:375-396) --, the rows being the

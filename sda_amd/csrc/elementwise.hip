@@ -171,15 +171,8 @@ extern "C" int sda_unfold_adjoint(const float* g_win, int b, int nw, int k, int 
 //   sigma_kind 0 VPSDE: sqrt(1 - a^2 + eta^2)    1 SubVPSDE: 1 - a^2 + eta    2 SubSubVPSDE: 1 - a + eta
 __global__ void vp_schedule_kernel(const float* __restrict__ t, int alpha_kind, float eta, float k, int sigma_kind,
                                    float* __restrict__ out) {
-    const float tv = t[0];
-    float a;
-    if (alpha_kind == 0) a = 1.0f - (1.0f - eta) * tv;
-    else if (alpha_kind == 1) { const float c = cosf(k * tv); a = c * c; }
-    else a = expf(k * (tv * tv));
-    float sg;
-    if (sigma_kind == 0) sg = sqrtf((1.0f - a * a) + eta * eta);
-    else if (sigma_kind == 1) sg = (1.0f - a * a) + eta;
-    else sg = (1.0f - a) + eta;
+    float a, sg;
+    sda_vp_mu_sigma(t[0], alpha_kind, eta, k, sigma_kind, a, sg);       // (sda_common.hpp: shared with sda_loss_perturb)
     out[0] = a;
     out[1] = sg;
 }

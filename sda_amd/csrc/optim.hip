@@ -13,6 +13,8 @@
 //   * a few registers and no LDS: occupancy is bounded by the block size alone.  LOCAL_CONFIG is 690 k elements = 680 workgroups of
 //     4 waves on 256 CUs; the launch is latency-, not bandwidth-bound (14 MB of traffic), so one chunk per workgroup and no grid stride;
 //   * plain vector stores only, every output element (p, m, v, slab positions) has exactly one writer: bitwise reproducible.
+// sda_adamw_step_dev is the same launch for a replayed (hipGraph) training step: the three scalars that change from step to step -- decay,
+// step_size, rsqrt_bc2 -- come from row irow[0] of a device table instead of the descriptor (sda_amd.training.GraphedStep).
 // The element update and the slab position are __host__ __device__; the emulator at the bottom (libsda_emu.so, tests only) runs the same
 // per-thread function on the host.
 #include "sda_common.hpp"
@@ -40,12 +42,16 @@ __host__ __device__ inline int sda_mlp_slab_pos(int rows, int cols, int r, int c
 // ---------------------------------------------------------------- the element update (host + device)
 // torch's single-tensor AdamW, operation by operation (mul_, lerp_, mul_ + addcmul_, sqrt / bias correction + eps, addcdiv_); every product
 // and sum is rounded on its own (the unit is compiled with -ffp-contract=off on both sides)
-__host__ __device__ inline void ao_update(const sda_adamw_desc& d, float g, float& p, float& m, float& v) {
-    p = p * d.decay;
+// the three scalars that change with the step count and the learning rate: by value in the descriptor (sda_adamw_step) or a row of a
+// device table (sda_adamw_step_dev)
+struct ao_step { float decay, step_size, rsqrt_bc2; };
+
+__host__ __device__ inline void ao_update(const sda_adamw_desc& d, const ao_step& s, float g, float& p, float& m, float& v) {
+    p = p * s.decay;
     m = m + (g - m) * d.one_m_beta1;
     v = v * d.beta2 + (d.one_m_beta2 * g) * g;
-    const float denom = sqrtf(v) * d.rsqrt_bc2 + d.eps;
-    p = p - d.step_size * (m / denom);
+    const float denom = sqrtf(v) * s.rsqrt_bc2 + d.eps;
+    p = p - s.step_size * (m / denom);
 }
 
 // the pack epilogue of element idx of a GEMM weight [out_f][in_f]
@@ -57,7 +63,7 @@ __host__ __device__ inline void ao_pack_weight(float* fwd, float* bwd, int out_f
 __host__ __device__ inline bool ao_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 // everything thread `tid` of workgroup `b` does
-__host__ __device__ inline void ao_thread(const sda_adamw_desc& d, int b, int tid) {
+__host__ __device__ inline void ao_thread(const sda_adamw_desc& d, const ao_step& s, int b, int tid) {
     int t = 0;
     while (t + 1 < d.ntensor && b >= d.blk0[t + 1]) ++t;
     const int64_t e0 = (int64_t)(b - d.blk0[t]) * AO_CHUNK, numel = d.numel[t];
@@ -73,10 +79,10 @@ __host__ __device__ inline void ao_thread(const sda_adamw_desc& d, int b, int ti
         if (e >= numel) return;
         float4 p4 = *reinterpret_cast<const float4*>(p + e), m4 = *reinterpret_cast<const float4*>(m + e), v4 = *reinterpret_cast<const float4*>(v + e);
         const float4 g4 = *reinterpret_cast<const float4*>(g + e);
-        ao_update(d, g4.x, p4.x, m4.x, v4.x);
-        ao_update(d, g4.y, p4.y, m4.y, v4.y);
-        ao_update(d, g4.z, p4.z, m4.z, v4.z);
-        ao_update(d, g4.w, p4.w, m4.w, v4.w);
+        ao_update(d, s, g4.x, p4.x, m4.x, v4.x);
+        ao_update(d, s, g4.y, p4.y, m4.y, v4.y);
+        ao_update(d, s, g4.z, p4.z, m4.z, v4.z);
+        ao_update(d, s, g4.w, p4.w, m4.w, v4.w);
         *reinterpret_cast<float4*>(p + e) = p4;
         *reinterpret_cast<float4*>(m + e) = m4;
         *reinterpret_cast<float4*>(v + e) = v4;
@@ -106,7 +112,7 @@ __host__ __device__ inline void ao_thread(const sda_adamw_desc& d, int b, int ti
         const int64_t e = e0 + j * AO_THREADS + tid;
         if (e >= numel) break;
         float pe = p[e], me = m[e], ve = v[e];
-        ao_update(d, g[e], pe, me, ve);
+        ao_update(d, s, g[e], pe, me, ve);
         p[e] = pe; m[e] = me; v[e] = ve;
         if (kind == 2) fwd[e] = pe;
         else if (kind == 1) {
@@ -145,13 +151,31 @@ static_assert(sizeof(sda_adamw_desc) <= 4096, "sda_adamw_desc travels by value: 
 
 #ifndef SDA_HOST_EMU
 
-__global__ __launch_bounds__(AO_THREADS) void adamw_step_kernel(const sda_adamw_desc d) { ao_thread(d, blockIdx.x, threadIdx.x); }
+__global__ __launch_bounds__(AO_THREADS) void adamw_step_kernel(const sda_adamw_desc d) {
+    ao_thread(d, ao_step{d.decay, d.step_size, d.rsqrt_bc2}, blockIdx.x, threadIdx.x);
+}
+
+// the replayable form: the step's three scalars are row irow[0] of a device table (the caller keeps irow[0] inside the table)
+__global__ __launch_bounds__(AO_THREADS) void adamw_dev_kernel(const sda_adamw_desc d, const float* __restrict__ table,
+                                                               const int64_t* __restrict__ irow) {
+    const float* row = table + 3 * irow[0];
+    ao_thread(d, ao_step{row[0], row[1], row[2]}, blockIdx.x, threadIdx.x);
+}
 
 extern "C" int sda_adamw_step(const sda_adamw_desc* dp, void* stream) {
     sda_adamw_desc d;
     const int rc = ao_plan(dp, &d);
     if (rc != SDA_OK) return rc;
     hipLaunchKernelGGL(adamw_step_kernel, dim3((unsigned)d.blk0[d.ntensor]), dim3(AO_THREADS), 0, (hipStream_t)stream, d);
+    return sda_launch_status();
+}
+
+extern "C" int sda_adamw_step_dev(const sda_adamw_desc* dp, const float* table, const int64_t* irow, void* stream) {
+    if (!table || !irow) return SDA_E_BADARG;
+    sda_adamw_desc d;
+    const int rc = ao_plan(dp, &d);
+    if (rc != SDA_OK) return rc;
+    hipLaunchKernelGGL(adamw_dev_kernel, dim3((unsigned)d.blk0[d.ntensor]), dim3(AO_THREADS), 0, (hipStream_t)stream, d, table, irow);
     return sda_launch_status();
 }
 
@@ -162,8 +186,22 @@ extern "C" int sda_adamw_step_emulate(const sda_adamw_desc* dp) {
     sda_adamw_desc d;
     const int rc = ao_plan(dp, &d);
     if (rc != SDA_OK) return rc;
+    const ao_step s{d.decay, d.step_size, d.rsqrt_bc2};
     for (int b = 0; b < d.blk0[d.ntensor]; ++b)
-        for (int tid = 0; tid < AO_THREADS; ++tid) ao_thread(d, b, tid);
+        for (int tid = 0; tid < AO_THREADS; ++tid) ao_thread(d, s, b, tid);
+    return SDA_OK;
+}
+
+// ... and adamw_dev_kernel: table and irow are HOST pointers too
+extern "C" int sda_adamw_step_dev_emulate(const sda_adamw_desc* dp, const float* table, const int64_t* irow) {
+    if (!table || !irow) return SDA_E_BADARG;
+    sda_adamw_desc d;
+    const int rc = ao_plan(dp, &d);
+    if (rc != SDA_OK) return rc;
+    const float* row = table + 3 * irow[0];
+    const ao_step s{row[0], row[1], row[2]};
+    for (int b = 0; b < d.blk0[d.ntensor]; ++b)
+        for (int tid = 0; tid < AO_THREADS; ++tid) ao_thread(d, s, b, tid);
     return SDA_OK;
 }
 #endif

@@ -96,6 +96,23 @@ __host__ __device__ __forceinline__ float sda_dact(int a, float z) {
     }
 }
 
+// ---- mu(t), sigma(t) of the VP schedules (score.py:195-210, 279-302): THE arithmetic of sda_vp_schedule, shared with
+// sda_loss_perturb (csrc/train_loss.hip) so that the two cannot drift
+//   alpha_kind 0 'lin': 1 - (1 - eta) t      1 'cos': cos(k t)^2, k = acos(sqrt(eta))      2 'exp': exp(k t^2), k = log(eta)
+//   sigma_kind 0 VPSDE: sqrt(1 - a^2 + eta^2)    1 SubVPSDE: 1 - a^2 + eta    2 SubSubVPSDE: 1 - a + eta
+__device__ __forceinline__ void sda_vp_mu_sigma(float tv, int alpha_kind, float eta, float k, int sigma_kind, float& mu, float& sigma) {
+    float a;
+    if (alpha_kind == 0) a = 1.0f - (1.0f - eta) * tv;
+    else if (alpha_kind == 1) { const float c = cosf(k * tv); a = c * c; }
+    else a = expf(k * (tv * tv));
+    float sg;
+    if (sigma_kind == 0) sg = sqrtf((1.0f - a * a) + eta * eta);
+    else if (sigma_kind == 1) sg = (1.0f - a * a) + eta;
+    else sg = (1.0f - a) + eta;
+    mu = a;
+    sigma = sg;
+}
+
 // sum_j w[j] v[j] as EIGHT interleaved partial sums (j mod 8), each accumulated in index order, combined as a balanced tree: the
 // dependent-add chain is n / 8 long instead of n (a 256-term sequential chain is ~7 000 cycles on one wave: tools/step1d_trace.py).
 // THE dot product of the time-embedding layers (sda_time_embed and sda_step1d_prologue share it: identical results).

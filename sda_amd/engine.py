@@ -163,7 +163,10 @@ class _ConvCache:
                 out = []
                 for py, ty, ph in taps[0]:
                     for px, tx, pw in taps[1]:
-                        sub = w[:, :, ty][:, :, :, tx].contiguous()
+                        # (the tap lists [1], [0, 2], [0 .. k) as slices: the same values, and no index tensor is uploaded -- a training
+                        # step captured into a hipGraph re-packs here)
+                        sy, sx = (slice(v[0], v[-1] + 1, v[1] - v[0] if len(v) > 1 else 1) for v in (ty, tx))
+                        sub = w[:, :, sy, sx].contiguous()
                         out.append((py, px, PackedConv(sub, None, transpose=True), (ph, pw)))
                 self._parity = out
         return self._parity or None

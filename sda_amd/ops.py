@@ -860,6 +860,60 @@ def adamw_step(d: '_lib.AdamWDesc') -> None:
     _lib.check(_lib.load().sda_adamw_step(ctypes.byref(d), _stream()), 'sda_adamw_step')
 
 
+def adamw_step_dev(d: '_lib.AdamWDesc', table: Tensor, irow: Tensor) -> None:
+    """The same launch with {decay, step_size, rsqrt_bc2} = row ``irow[0]`` of the fp32 device ``table`` [rows][3] (sda_adamw_step_dev:
+    hipGraph-replayable; sda_amd.training.GraphedStep).  The caller keeps ``irow`` (a device int64 scalar) inside the table."""
+    if not (table.is_cuda and table.dtype == torch.float32 and table.is_contiguous() and table.dim() == 2 and table.shape[1] == 3):
+        raise _lib.SdaHipError('adamw_step_dev: table is a contiguous fp32 device tensor [rows][3]')
+    if not (irow.is_cuda and irow.dtype == torch.int64 and irow.numel() == 1):
+        raise _lib.SdaHipError('adamw_step_dev: irow is a device int64 scalar')
+    _lib.check(_lib.load().sda_adamw_step_dev(ctypes.byref(d), table.data_ptr(), irow.data_ptr(), _stream()), 'sda_adamw_step_dev')
+
+
+def loss_perturb(x: Tensor, seed: int, row0: int, alpha_kind: int, eta: float, k: float, sigma_kind: int, step: int = 0,
+                 step_dev: Optional[Tensor] = None):
+    """x (rows, ...) -> (t (rows,), eps, xt) of the keyed denoising loss in one launch (sda_loss_perturb, csrc/train_loss.hip):
+    eps[b] = row ``row0 + b`` of ``randn_rows(seed, draw = 2 s)``, t[b] a uniform in (0, 1) from draw ``2 s + 1`` of the same generator,
+    xt = mu(t) x + sigma(t) eps with ``vp_schedule``'s mu and sigma.  s = ``step_dev[0]`` (a device int64 scalar: graph replay) or ``step``."""
+    _dev(x)
+    if step_dev is not None and (not step_dev.is_cuda or step_dev.dtype != torch.int64 or step_dev.numel() != 1):
+        raise _lib.SdaHipError('step_dev must be a device int64 scalar')
+    x = x.contiguous()
+    rows = x.shape[0] if x.dim() else 0
+    if rows < 1 or x.numel() == 0:
+        raise _lib.SdaHipError('loss_perturb: x has at least one row and one element per row')
+    t = torch.empty(rows, device=x.device, dtype=torch.float32)
+    eps, xt = torch.empty_like(x), torch.empty_like(x)
+    _lib.check(_lib.load().sda_loss_perturb(x.data_ptr(), rows, x.numel() // rows, seed & 0xffffffffffffffff, row0, step, _ptr(step_dev),
+                                            alpha_kind, eta, k, sigma_kind, t.data_ptr(), eps.data_ptr(), xt.data_ptr(), _stream()),
+               'sda_loss_perturb')
+    return t, eps, xt
+
+
+def loss_mse_plan(numel: int):
+    """(workgroups of stage 1 = floats of the work buffer, longest chain of additions a term passes through) of ``loss_mse`` on ``numel``
+    elements (sda_loss_mse_plan)."""
+    blocks, chain = ctypes.c_int(0), ctypes.c_int(0)
+    floats = _lib.load().sda_loss_mse_plan(numel, ctypes.byref(blocks), ctypes.byref(chain))
+    _lib.check(int(min(floats, 0)), 'sda_loss_mse_plan')
+    return blocks.value, chain.value
+
+
+def loss_mse(out: Tensor, eps: Tensor, with_g: bool = True):
+    """(0-dim mean((out - eps)^2), g = (2 / numel) (out - eps) or None): two ordered launches, bitwise reproducible (sda_loss_mse,
+    csrc/train_loss.hip).  ``out`` and ``eps`` are contiguous and of one shape."""
+    _dev(out, eps)
+    if out.shape != eps.shape or not out.is_contiguous() or not eps.is_contiguous():
+        raise _lib.SdaHipError('loss_mse: out and eps are contiguous tensors of one shape')
+    blocks, _chain = loss_mse_plan(out.numel())
+    loss = torch.empty((), device=out.device, dtype=torch.float32)
+    work = torch.empty(blocks, device=out.device, dtype=torch.float32)
+    g = torch.empty_like(out) if with_g else None
+    _lib.check(_lib.load().sda_loss_mse(out.data_ptr(), eps.data_ptr(), out.numel(), loss.data_ptr(), _ptr(g), work.data_ptr(), _stream()),
+               'sda_loss_mse')
+    return loss, g
+
+
 def mlp_wgrad_work_floats(d: '_lib.MlpWgradDesc') -> int:
     """Floats of the ``work`` buffer sda_mlp_wgrad needs for this descriptor (``d.work`` is not read)."""
     floats = _lib.load().sda_mlp_wgrad_work_floats(ctypes.byref(d))

@@ -414,6 +414,9 @@ class VPSDE(nn.Module):
     initial_noise: Optional[Tensor] = None
     #: replay each diffusion step from a captured hipGraph (see PCSampler.capture); off by default
     use_graph: bool = False
+    #: optional ``training.KeyedLossNoise``: ``loss()`` then draws t and eps keyed on (seed, row, training step) in one launch and reduces
+    #: the squared error in two (csrc/train_loss.hip) instead of using torch's generator -- replayable from a hipGraph; None: the torch route
+    loss_noise: Optional['training.KeyedLossNoise'] = None
 
     def sampler(self, shape: Size = (), c: Tensor = None, steps: int = 64, corrections: int = 0,
                 tau: float = 1.0) -> 'PCSampler':
@@ -443,12 +446,47 @@ class VPSDE(nn.Module):
                 raise NotImplementedError('training is outside the sampling hot path: parameter gradients are never formed. '
                                           'Evaluate the loss under torch.no_grad() (validation), or freeze the parameters, or '
                                           'switch parameter gradients on (sda_amd.training.parameter_gradients())')
+        if self.loss_noise is not None:
+            return self._keyed_loss(x, c, w)
         t = torch.rand(x.shape[0], dtype=x.dtype, device=x.device)
         x, eps = self.forward(x, t, train=True)
         err = (self.eps(x, t, c) - eps).square()
         if w is None:
             return err.mean()
         return (err * w).mean() / w.mean()
+
+
+    def _keyed_loss(self, x: Tensor, c: Tensor = None, w: Tensor = None) -> Tensor:
+        """The same loss with ``loss_noise``'s keyed draws: sda_loss_perturb, the network, sda_loss_mse (with its cotangent for backward).
+        Advances neither torch's generator nor the step counter."""
+        from . import fused1d
+        noise = self.loss_noise
+        sched = fused1d.stock_schedule(self)
+        if sched is None:
+            raise NotImplementedError('the keyed denoising loss serves the stock schedules (alpha lin / cos / exp of VPSDE, SubVPSDE, '
+                                      'SubSubVPSDE); a subclass overriding mu / sigma / alpha takes loss_noise = None')
+        ak, eta, k, kind = sched
+        t, eps, xt = ops.loss_perturb(x, noise.seed, noise.row0, ak, eta, k, kind, step_dev=noise.counter(x.device))
+        out = self.eps(xt, t, c)
+        if w is not None:
+            err = (out - eps).square()
+            return (err * w).mean() / w.mean()
+        return _KeyedMSE.apply(out.contiguous(), eps)
+
+
+class _KeyedMSE(torch.autograd.Function):
+    """mean((out - eps)^2) on sda_loss_mse; the cotangent g = (2 / numel)(out - eps) is formed in the forward's launch."""
+
+    @staticmethod
+    def forward(ctx, out, eps):
+        loss, g = ops.loss_mse(out, eps, with_g=True)
+        ctx.save_for_backward(g)
+        return loss
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        (g,) = ctx.saved_tensors
+        return g * grad_output, None
 
 
 class PCSampler:

@@ -76,7 +76,7 @@ _SCHEDULES = {
 
 def loop(sde: 'VPSDE', trainset, validset, epochs: int = 256, batch_size: int = 64, optimizer: str = 'AdamW',
          learning_rate: float = 1e-3, weight_decay: float = 1e-3, scheduler: str = 'linear', device: str = 'cpu',
-         fused: bool = False, wgrad: str = 'general', net1d: bool = False, **absorb) -> Iterator:
+         fused: bool = False, wgrad: str = 'general', net1d: bool = False, graph: bool = False, seed: int = 0, **absorb) -> Iterator:
     """Train ``sde`` (its score network) on ``trainset`` and yield ``(loss_train, loss_valid, lr)`` once per epoch.
 
     As the reference's loop: shuffled DataLoaders whose items are ``(x, kwargs)`` pairs (``kwargs`` go on to ``sde.loss``),
@@ -85,23 +85,39 @@ def loop(sde: 'VPSDE', trainset, validset, epochs: int = 256, batch_size: int = 
     gradients are switched on (``sda_amd.training.parameter_gradients(mlp=True)``: the U-Nets and ScoreNet) while the training steps run.
     ``fused=True`` takes ``sda_amd.training.AdamW`` (one launch per step, the ResMLP weight slabs stay packed) for ``torch.optim.AdamW``;
     ``wgrad='tiled'`` sends the block convolutions' weight gradients to the tiled kernel, ``wgrad='tiled_ht'`` the stride-2 heads' and
-    up-sampling tails' as well; ``net1d=True`` trains a single-level 1-D U-Net on the whole-net kernels (``sda_amd.training``)."""
+    up-sampling tails' as well; ``net1d=True`` trains a single-level 1-D U-Net on the whole-net kernels (``sda_amd.training``).
+    ``graph=True`` (implies ``fused``) replays every training step as one hipGraph (``sda_amd.training.GraphedStep``): the loss draws its
+    noise keyed on ``seed`` and the step index instead of torch's generator, and the epoch's mean loss is read back once; the items'
+    ``kwargs`` must then be empty."""
     from torch.utils.data import DataLoader
     loaders = [DataLoader(ds, batch_size=batch_size, shuffle=True) for ds in (trainset, validset)]
     if optimizer != 'AdamW':
         raise ValueError(f'optimizer {optimizer!r} (the loop knows AdamW)')
-    if fused:
+    if fused or graph:
         opt = training.AdamW(sde.parameters(), lr=learning_rate, weight_decay=weight_decay, net=sde)
     else:
         opt = torch.optim.AdamW(sde.parameters(), lr=learning_rate, weight_decay=weight_decay)
     if scheduler not in _SCHEDULES:
         raise ValueError(f'scheduler {scheduler!r} (expected one of {sorted(_SCHEDULES)})')
     sched = torch.optim.lr_scheduler.LambdaLR(opt, lr_lambda=_SCHEDULES[scheduler](epochs))
+    stepper = training.GraphedStep(sde, opt, seed=seed, mlp=True, wgrad=wgrad, net1d=net1d) if graph else None
+    if graph:
+        opt._opt_called = True       # (the steps run inside the graph: LambdaLR would warn that optimizer.step() was never called)
     for _ in range(epochs):
         losses_train, losses_valid = [], []
         sde.train()
-        with training.parameter_gradients(mlp=True, wgrad=wgrad, net1d=net1d):
+        if graph:
+            stepper.loss_sum.zero_()
+            n = 0
             for batch in loaders[0]:
+                x, kwargs = _to(batch, device=device)
+                if kwargs:
+                    raise NotImplementedError(f'loop(graph=True) trains on items without keyword arguments (got {sorted(kwargs)})')
+                stepper.step(x)
+                n += 1
+            losses_train.append(stepper.loss_sum / max(n, 1))
+        with training.parameter_gradients(mlp=True, wgrad=wgrad, net1d=net1d):
+            for batch in () if graph else loaders[0]:
                 x, kwargs = _to(batch, device=device)
                 loss = sde.loss(x, **kwargs)
                 loss.backward()
