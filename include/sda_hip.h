@@ -522,8 +522,9 @@ int sda_mlp_slab_floats(int in_f, int out_f);         /* host, no launch */
 
 /* Parameter gradients of the same chain (csrc/mlp_train.hip; opt-in training, sda_amd.training.parameter_gradients(mlp=True)).
  *
- * sda_mlp_bwd_train: sda_mlp_bwd on `mlp` (same transposed slabs, same saves, same input gradient bit for bit) that also stores the
- *   cotangent at every GEMM's OUTPUT as rows g_save[g][row][g_ld] (GEMM stride g_stride floats):
+ * sda_mlp_bwd_train: sda_mlp_bwd on `mlp` (ONE kernel text, csrc/mlp1d_vjp_kernels.hpp, compiled into both entries: same transposed slabs,
+ *   same saves, same input gradient bit for bit) that also stores the cotangent at every GEMM's OUTPUT as rows g_save[g][row][g_ld]
+ *   (GEMM stride g_stride floats):
  *     kind 0: the cotangent of the Linear's output;  kind 2: the cotangent of the block's output;
  *     kind 1: gz = (g . W2) * act'(z), the cotangent of the pre-activation.
  *   Rows are written as whole 16-feature fragments: columns [out_f[g], padded width) of a row receive zeros, columns beyond the padded

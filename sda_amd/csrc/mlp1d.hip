@@ -38,7 +38,7 @@
 //     padded bias: sixteen 256-wide GEMMs; beyond that SDA_E_UNSUPPORTED.
 // Window mode (sda_mlp_fwd_win / sda_mlp_bwd_win, sda_hip.h) keeps a row's window values in the first one or two D fragments: windows of at most
 // 16 values run the <true> instances of the four kernels, windows of 17 .. 32 values (Lorenz k = 3, 4) the mlp_win2_* kernels -- the same
-// bodies (mlp1d_kernels.hpp) compiled with ML_WF = 2; the VJP's window gradient gwin has a row of 16 ML_WF floats.  A last GEMM of 17 .. 32
+// bodies (mlp1d_kernels.hpp, mlp1d_vjp_kernels.hpp) compiled with ML_WF = 2; the VJP's window gradient gwin has a row of 16 ML_WF floats.  A last GEMM of 17 .. 32
 // outputs is a 128-feature slab, as every width above 16.
 // Roofline: the Lorenz local net is 0.34 MFLOP per window and direction; at 62 464 windows (eval.py's batch) 21.5 GFLOP = 0.14 ms of
 // fp32 MFMA time per direction.
@@ -65,12 +65,17 @@ extern "C" int sda_ml_trace_read(long long* out, int reset) {
 
 // ------------------------------------------------------------------------------------------------------------ the kernels
 // {forward, VJP} x {rows, windows} x {narrow, wide}; window mode with the window values of a row in one D fragment (at most 16 values) ...
+// (the VJP text's hooks, see mlp1d_vjp_kernels.hpp: both descriptors are parameters and no cotangent stream is stored)
+#define ML_VJP_ARGS const sda_mlp_desc d, const sda_mlp_win w
+#define ML_VJP_ENTRY
+#define ML_COT(g, n, v) do {} while (0)
 #define ML_WF 1
 #define ML_K_FWD mlp_fwd_kernel
 #define ML_K_BWD mlp_bwd_kernel
 #define ML_K_FWD_WIDE mlp_fwd_kernel_wide
 #define ML_K_BWD_WIDE mlp_bwd_kernel_wide
 #include "mlp1d_kernels.hpp"
+#include "mlp1d_vjp_kernels.hpp"
 #undef ML_WF
 #undef ML_K_FWD
 #undef ML_K_BWD
@@ -85,6 +90,7 @@ extern "C" int sda_ml_trace_read(long long* out, int reset) {
 #define ML_K_FWD_WIDE mlp_win2_fwd_wide
 #define ML_K_BWD_WIDE mlp_win2_bwd_wide
 #include "mlp1d_kernels.hpp"
+#include "mlp1d_vjp_kernels.hpp"
 #undef ML_WF
 #undef ML_K_FWD
 #undef ML_K_BWD

@@ -1,5 +1,5 @@
-// The device helpers of the whole-MLP kernels, shared by csrc/mlp1d.hip (forward, input VJP, window mode) and csrc/mlp_train.hip (the VJP
-// that also stores the cotangent streams): slab staging, the multiply ml_mm, LayerNorm and its adjoint, row loaders / stores, window
+// The device helpers of the whole-MLP kernel texts (mlp1d_kernels.hpp: forward; mlp1d_vjp_kernels.hpp: input VJP), included by csrc/mlp1d.hip
+// (both texts, rows and window mode) and csrc/mlp_train.hip (the VJP text, with its cotangent-stream hook filled in): slab staging, the multiply ml_mm, LayerNorm and its adjoint, row loaders / stores, window
 // mode, the wide kernels' unit walk and the descriptor check.  See the header of mlp1d.hip for the design.
 #pragma once
 #include "sda_common.hpp"

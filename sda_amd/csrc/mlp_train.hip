@@ -1,8 +1,8 @@
 // Parameter gradients of a whole residual MLP (the Lorenz LOCAL score kernel; opt-in training, sda_amd/training.py with mlp = True).
 // A training step of the reference's train_local is 64 rows through 12 GEMMs of at most 256 x 256: bound by launch latency, so the
 // backward is THREE launches on top of the forward's, whatever the depth:
-//   1. sda_mlp_bwd_train: the input VJP of the chain, the code of sda_mlp_bwd (csrc/mlp1d.hip: same helpers out of mlp1d_common.hpp,
-//      same slabs, same saves, the same input gradient bit for bit; one wave per 16 rows, one wave per SIMD) that also stores the
+//   1. sda_mlp_bwd_train: the input VJP of the chain, the kernel text of sda_mlp_bwd (csrc/mlp1d_vjp_kernels.hpp, included by csrc/mlp1d.hip
+//      and by this file: same slabs, same saves, the same input gradient bit for bit; one wave per 16 rows, one wave per SIMD) that also stores the
 //      cotangent at every GEMM's output as rows g_save[gemm][row][g_ld]: the cotangent of a Linear's / a block's output (kinds 0, 2) behind
 //      that GEMM's multiply, gz = (g W2) * act'(z) (kind 1) behind the activation derivative.  The stores leave behind the hand-off
 //      barrier, as the forward's saves do (in front of the staging loads a store's round trip is what the wait for those loads waits for);
@@ -216,158 +216,17 @@ __device__ __forceinline__ void mt_store_cot(const sda_mlp_train_desc& t, int g,
         if (m < nm) *reinterpret_cast<ml_f32x4*>(o + 16 * m) = v[m];
 }
 
-// The two kernels below are mlp_bwd_kernel<false> / mlp_bwd_kernel_wide<false> of mlp1d.hip, statement for statement, plus the
-// mt_store_cot calls (they cannot be one template with those: the kernels of mlp1d.o are counted and pinned by name).  AN EDIT OF EITHER
-// BODY BELONGS IN ITS TWIN; the device test that asks for the bitwise-equal input gradient is the guard.
-
-// mlp_bwd_kernel<false> of mlp1d.hip (every GEMM side <= 128) + the three stores
-__global__ __launch_bounds__(256) void mlp_train_vjp_kernel(const sda_mlp_train_desc t) {
-    extern __shared__ __attribute__((aligned(16))) float ml_lds[];
-    const sda_mlp_desc& d = t.mlp;
-    MlCtx c;
-    ml_ctx(c, d);
-    const int gl = d.ngemm - 1;
-    MlStage st;
-    st.src = ml_rsrc(d.w + d.w_off[gl]); st.toff = 16u * c.tid;
-    st.dst = reinterpret_cast<ml_f32x4*>(ml_lds) + c.tid;
-    st.npieces = ml_slab_floats(d.out_f[gl], d.in_f[gl]) / ML_PIECE;
-    for (int p = 0; p < st.npieces; ++p) { ml_f32x4 v[4]; st.issue(v, p); st.commit(v, p); }
-    ml_f32x4 h[8], gacc[8], acc[8], zero[8];
-#pragma unroll
-    for (int m = 0; m < 8; ++m) zero[m] = ml_f32x4{0.f, 0.f, 0.f, 0.f};
-    ml_load_rows(d.x, d.x_ld, d.out_f[gl], c, gacc);
-    __syncthreads();
-    const bool silu = d.act == SDA_ACT_SILU;
-    int rb = 0;
-    for (int g = 0; g < d.ngemm; ++g) rb += d.kind[g] == 2;
-    int buf = 0;
-    MlMeta mc = ml_meta(d, gl), mn = ml_meta(d, gl - 1);
-    for (int g = gl; g >= 0; --g, buf ^= 1) {
-        const MlMeta mm = ml_meta(d, g - 2);
-        const float* wl = ml_lds + buf * ML_SLAB;
-        const bool last = g == 0;
-        st.src = ml_rsrc(d.w + (last ? 0 : mn.w_off)); st.toff = 16u * c.tid;
-        st.dst = reinterpret_cast<ml_f32x4*>(ml_lds + (buf ^ 1) * ML_SLAB) + c.tid;
-        st.npieces = last ? 0 : ml_slab_floats(mn.out_f, mn.in_f) / ML_PIECE;
-        if (mc.kind == 2) --rb;
-        const int cw = mc.in_f, nm = ml_mf(cw);
-        const int64_t srow = c.rowok ? c.row : 0;
-        ml_f32x4 sv[8];                                    // kind 2: z; kind 1: the block input a
-        float mean = 0.f, rs = 0.f;
-        if (mc.kind != 0) {
-            const float* sp = (mc.kind == 2 ? d.z_save : d.a_save) + (int64_t)rb * d.save_stride + srow * d.save_ld + 4 * c.kq;
-#pragma unroll
-            for (int m = 0; m < 8; ++m) sv[m] = m < nm ? *reinterpret_cast<const ml_f32x4*>(sp + 16 * m) : ml_f32x4{0.f, 0.f, 0.f, 0.f};
-            if (mc.kind == 1) {
-                mean = d.mean_save[(int64_t)rb * d.stat_stride + srow];
-                rs = d.rstd_save[(int64_t)rb * d.stat_stride + srow];
-            }
-        }
-        if (mc.kind == 1) ml_gemm(wl, mc.out_f, mc.in_f, h, acc, zero, st, c, nullptr, zero);
-        else ml_gemm(wl, mc.out_f, mc.in_f, gacc, acc, zero, st, c, nullptr, zero);
-        __syncthreads();
-        if (mc.kind != 1) mt_store_cot(t, g, mc.out_f, c, gacc);       // the cotangent this GEMM's output received
-        if (mc.kind == 0) {
-#pragma unroll
-            for (int m = 0; m < 8; ++m) gacc[m] = acc[m];
-        } else if (mc.kind == 2) {
-            auto dact = [&](auto SILU_) {
-#pragma unroll
-                for (int m = 0; m < 8; ++m)
-#pragma unroll
-                    for (int r = 0; r < 4; ++r)
-                        h[m][r] = acc[m][r] * (decltype(SILU_)::value ? sda_dact(SDA_ACT_SILU, sv[m][r]) : sda_dact(d.act, sv[m][r]));
-            };
-            if (silu) dact(std::true_type{});
-            else dact(std::false_type{});
-            mt_store_cot(t, g - 1, cw, c, h);              // gz: the cotangent of the block's first GEMM
-        } else {
-            const float inv_c = 1.f / (float)cw, inv_v = 1.f / (float)(d.unbiased ? cw - 1 : cw);
-            auto lnb = [&](auto FULL_) { ml_ln_bwd<decltype(FULL_)::value>(sv, acc, gacc, cw, c, inv_c, inv_v, mean, rs); };
-            if (cw == 128) lnb(std::true_type{});
-            else lnb(std::false_type{});
-        }
-        mc = mn; mn = mm;
-    }
-    ml_store_rows(d.out, d.out_ld, d.in_f[0], c, gacc);
-}
-
-// mlp_bwd_kernel_wide<false> of mlp1d.hip (a GEMM side in 129 .. 256) + the three stores
-__global__ __launch_bounds__(256) void mlp_train_vjp_kernel_wide(const sda_mlp_train_desc t) {
-    extern __shared__ __attribute__((aligned(16))) float ml_lds[];
-    const sda_mlp_desc& d = t.mlp;
-    MlCtx c;
-    ml_ctx(c, d);
-    const int gl = d.ngemm - 1;
-    MlMeta mc = ml_meta(d, gl), mn = ml_meta(d, gl - 1);
-    MlStage st;
-    st.src = ml_rsrc(d.w + mc.w_off); st.toff = 16u * c.tid;
-    st.dst = reinterpret_cast<ml_f32x4*>(ml_lds) + c.tid;
-    st.npieces = mlw_unit_floats(mc.out_f, mc.in_f) / ML_PIECE;
-    for (int p = 0; p < st.npieces; ++p) { ml_f32x4 v[4]; st.issue(v, p); st.commit(v, p); }
-    ml_f32x4 h[16], gacc[16], acc[16];
-    ml_load_rows(d.x, d.x_ld, d.out_f[gl], c, gacc);
-    __syncthreads();
-    const bool silu = d.act == SDA_ACT_SILU;
-    int rb = 0, buf = 0;
-    for (int g = 0; g < d.ngemm; ++g) rb += d.kind[g] == 2;
-    for (int g = gl; g >= 0; --g) {
-        const MlMeta mm = ml_meta(d, g - 2);
-        const bool last = g == 0;
-        if (mc.kind == 2) --rb;
-        const int cw = mc.in_f, nm = mlw_mf(cw);
-        const int64_t srow = c.rowok ? c.row : 0;
-        if (mc.kind != 1) {
-#pragma unroll
-            for (int m = 0; m < 16; ++m) h[m] = gacc[m];
-        }
-        mlw_gemm(ml_lds, buf, d.w + mc.w_off, mc.out_f, mc.in_f, d.w + (last ? 0 : mn.w_off),
-                 last ? 0 : mlw_unit_floats(mn.out_f, mn.in_f) / ML_PIECE, h, acc, st, c);
-        if (mc.kind != 1) mt_store_cot(t, g, mc.out_f, c, gacc);       // the cotangent this GEMM's output received
-        const int64_t soff = (int64_t)rb * d.save_stride + srow * d.save_ld + 4 * c.kq;
-        if (mc.kind == 0) {
-#pragma unroll
-            for (int m = 0; m < 16; ++m) gacc[m] = acc[m];
-        } else if (mc.kind == 2) {
-            const float* sp = d.z_save + soff;
-            auto dact = [&](auto SILU_) {
-                ml_f32x4 zb[2][4];
-                auto fetch = [&](int grp) {
-#pragma unroll
-                    for (int i = 0; i < 4; ++i)
-                        zb[grp & 1][i] = 4 * grp + i < nm ? *reinterpret_cast<const ml_f32x4*>(sp + 16 * (4 * grp + i)) : ml_f32x4{0.f, 0.f, 0.f, 0.f};
-                };
-                fetch(0);
-#pragma unroll
-                for (int grp = 0; grp < 4; ++grp) {
-                    if (grp < 3) fetch(grp + 1);
-#pragma unroll
-                    for (int i = 0; i < 4; ++i)
-#pragma unroll
-                        for (int r = 0; r < 4; ++r) {
-                            const float z = zb[grp & 1][i][r];
-                            h[4 * grp + i][r] = acc[4 * grp + i][r] * (decltype(SILU_)::value ? sda_dact(SDA_ACT_SILU, z) : sda_dact(d.act, z));
-                        }
-                    __builtin_amdgcn_sched_barrier(0);
-                }
-            };
-            if (silu) dact(std::true_type{});
-            else dact(std::false_type{});
-            mt_store_cot(t, g - 1, cw, c, h);              // gz: the cotangent of the block's first GEMM
-        } else {
-            const float* sp = d.a_save + soff;
-            ml_f32x4 sv[16];                               // the block input
-#pragma unroll
-            for (int m = 0; m < 16; ++m) sv[m] = m < nm ? *reinterpret_cast<const ml_f32x4*>(sp + 16 * m) : ml_f32x4{0.f, 0.f, 0.f, 0.f};
-            const float mean = d.mean_save[(int64_t)rb * d.stat_stride + srow], rs = d.rstd_save[(int64_t)rb * d.stat_stride + srow];
-            const float inv_c = 1.f / (float)cw, inv_v = 1.f / (float)(d.unbiased ? cw - 1 : cw);
-            if (cw == 256) ml_ln_bwd<true>(sv, acc, gacc, cw, c, inv_c, inv_v, mean, rs);
-            else ml_ln_bwd<false>(sv, acc, gacc, cw, c, inv_c, inv_v, mean, rs);
-        }
-        mc = mn; mn = mm;
-    }
-    ml_store_rows(d.out, d.out_ld, d.in_f[0], c, gacc);
-}
+// The two VJP kernels are the text of mlp_bwd_kernel / mlp_bwd_kernel_wide (csrc/mlp1d_vjp_kernels.hpp, which csrc/mlp1d.hip includes too),
+// compiled here under names of this unit's own with the descriptor pair as the parameter and the cotangent hook filled in.  Only <false>
+// (rows, not windows) is instantiated: `w` exists so that the discarded window branches parse (not const: the compiler would fold its zeros
+// into that text and warn of a division by w.c).
+#define ML_VJP_ARGS const sda_mlp_train_desc t
+#define ML_VJP_ENTRY const sda_mlp_desc& d = t.mlp; sda_mlp_win w = {};
+#define ML_COT(g, n, v) mt_store_cot(t, (g), (n), c, v)
+#define ML_WF 1
+#define ML_K_BWD mlp_train_vjp_kernel
+#define ML_K_BWD_WIDE mlp_train_vjp_kernel_wide
+#include "mlp1d_vjp_kernels.hpp"
 
 extern "C" int sda_mlp_bwd_train(const sda_mlp_train_desc* t, void* stream) {
     if (!t) return SDA_E_BADARG;
@@ -387,7 +246,7 @@ extern "C" int sda_mlp_bwd_train(const sda_mlp_train_desc* t, void* stream) {
     if (tiles > 0x7fffffffLL) return SDA_E_UNSUPPORTED;
     constexpr int lds = (2 * ML_SLAB + ML_BIAS) * 4;
     static bool raised[2][SDA_MAX_DEVICES];
-    void (*const kern)(sda_mlp_train_desc) = wide ? mlp_train_vjp_kernel_wide : mlp_train_vjp_kernel;
+    void (*const kern)(sda_mlp_train_desc) = wide ? mlp_train_vjp_kernel_wide<false> : mlp_train_vjp_kernel<false>;
     const int rr = sda_raise_dyn_lds(reinterpret_cast<const void*>(kern), lds, raised[wide]);
     if (rr != SDA_OK) return rr;
     hipLaunchKernelGGL(kern, dim3((unsigned)tiles), dim3(256), lds, (hipStream_t)stream, *t);

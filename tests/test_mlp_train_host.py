@@ -273,8 +273,9 @@ def test_wgrad_emulator_planner_and_chain(emu):
 # ------------------------------------------------------------------------------------------------------------ build-time guard
 
 def test_train_kernels_no_spills_no_scratch_lds_budget():
-    """The VJP kernels with cotangent streams keep what tests/test_isa_guard_mlp.py holds for the kernels they copy: no spill, no scratch
-    instruction, 512 registers (one wave per SIMD), LDS within 160 KiB with the launch's dynamic part; the weight-gradient kernels likewise."""
+    """The VJP kernels with cotangent streams keep what tests/test_isa_guard_mlp.py holds for mlp1d.o's VJP kernels, whose text they are
+    (csrc/mlp1d_vjp_kernels.hpp, included by both units): no spill, no scratch instruction, 512 registers (one wave per SIMD), LDS within
+    160 KiB with the launch's dynamic part; the weight-gradient kernels likewise."""
     import isa_guard as G
     sbuild.build()
     obj = os.path.join(ROOT, 'sda_amd', 'lib', 'mlp_train.o')
@@ -292,3 +293,23 @@ def test_train_kernels_no_spills_no_scratch_lds_budget():
         assert k['vgpr_count'] <= 512, (n, k)
     for n in vjp + [x for x in wg if 'reduce' not in x]:
         assert sum(1 for i in dis[n] if 'v_mfma_f32' in i) > 0, n
+
+
+def test_train_vjp_kernels_multiply_as_the_mlp1d_vjp_kernels_do():
+    """One VJP text, two units: the training kernels issue the fp32 MFMAs of mlp_bwd_kernel<false> / mlp_bwd_kernel_wide<false>, both counts
+    read from the built objects (the pinned numbers are tests/test_isa_guard_mlp.py's alone)."""
+    import isa_guard as G
+    sbuild.build()
+    train = G.disassemble(os.path.join(ROOT, 'sda_amd', 'lib', 'mlp_train.o'))
+    mlp1d = G.disassemble(os.path.join(ROOT, 'sda_amd', 'lib', 'mlp1d.o'))
+
+    def mfmas(dis, pick):
+        names = [n for n in dis if pick(n)]
+        assert len(names) == 1, names
+        return sum(1 for i in dis[names[0]] if 'v_mfma_f32_16x16x4' in i)
+
+    narrow = mfmas(train, lambda n: 'mlp_train_vjp_kernel' in n and '_wide' not in n)
+    wide = mfmas(train, lambda n: 'mlp_train_vjp_kernel' in n and '_wide' in n)
+    assert narrow > 0 and wide > 0
+    assert narrow == mfmas(mlp1d, lambda n: 'mlp_bwd_kernelILb0E' in n)
+    assert wide == mfmas(mlp1d, lambda n: 'mlp_bwd_kernel_wideILb0E' in n)
