@@ -621,6 +621,29 @@ int sda_loss_perturb(const float* x, int rows, int64_t per_row, uint64_t seed, i
 int64_t sda_loss_mse_plan(int64_t numel, int* blocks, int* chain);
 int sda_loss_mse(const float* out, const float* eps, int64_t numel, float* loss, float* g, float* work, void* stream);
 
+/* The device-resident trajectory dataset (csrc/dataset.hip; additive, ABI stays v14): what a shuffled DataLoader over the reference's
+ * TrajectoryDataset (sda/utils.py:58-86: one randint, one narrow, one flatten per item, then collation and an upload) feeds a training
+ * step, as one launch.  data [N][L][F] contiguous fp32 (N trajectories, L frames, F values per frame) -> out [rows][W F]: row b holds the
+ * W F contiguous values from ((n_b L) + start_b) F on.
+ * sda_window_batch: the global batch index is s = step_dev[0] (a device int64 scalar the launch only reads: hipGraph-replayable) or, with
+ *   step_dev NULL, `step`.  spe = ceil(N / batch); epoch e = s / spe, batch i = s % spe, position p = i batch + b.  n_b = perm_e(p), a
+ *   permutation of [0, N) keyed on (seed, e): a four-round balanced Feistel network over 2h-bit words (4^h the smallest power of four
+ *   >= N) with cycle walking, round function = word 0 of Philox4x32-10 at counter {v, e_lo, 0x80000000 | e_hi, 'SHU0' + round};
+ *   start_b = (u (L - W + 1)) >> 32 (64-bit product), u = word 0 at counter {b, s_lo, 0x80000000 | s_hi, 'WSTA'}; key = seed in both.
+ *   Neither counter collides with sda_randn_rows' or sda_bpf_resample's (csrc/philox.hpp): the seed of the loss noise may be reused.
+ *   The caller passes the rows of this batch by value (rows <= batch; the epoch's short last batch is a launch with fewer rows) and
+ *   guarantees i batch + rows <= N; with a device counter, rows past the epoch's end are left unwritten.  16-byte copies where
+ *   F % 4 == 0 and data / out are 16-byte aligned, scalar ones otherwise.
+ * sda_window_batch_plan: host only -- the same (n_b, start_b), from the same index functions, for `rows` rows of batch `step` into two
+ *   int64 host arrays.
+ * Both: SDA_E_BADARG for a null pointer, N, L, F, W, batch or rows < 1, W > L, rows > batch, step < 0, or a by-value step with
+ *   i batch + rows > N (sda_window_batch ignores the by-value step's position when step_dev is given); SDA_E_UNSUPPORTED for N, L or
+ *   batch >= 2^31, more than 2^31 - 1 workgroups (rows * ceil(W F / 1024)) or N L F past an int64 offset. */
+int sda_window_batch(const float* data, int64_t N, int64_t L, int64_t F, int64_t W, int64_t batch, int64_t rows, uint64_t seed,
+                     int64_t step, const int64_t* step_dev, float* out, void* stream);
+int sda_window_batch_plan(int64_t N, int64_t L, int64_t W, int64_t batch, uint64_t seed, int64_t step, int64_t rows, int64_t* src_row,
+                          int64_t* start);
+
 /* The same two launches as the halves of a Gaussian-guided evaluation of a LOCAL score network -- MCScoreNet over a ScoreNet kernel
  * (sda/score.py:134-164, 53-63; experiments/lorenz/utils.py:45-59) inside GaussianScore (score.py:375-396) --, the rows being the
  * nw = len - 2k windows of each of rows / nw trajectories x (B, len, c), wc = (2k + 1) c <= 32 (a window's values fill one or two 16-feature

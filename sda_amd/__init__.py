@@ -13,6 +13,7 @@ from . import score
 from . import utils
 from . import observe
 from . import training
+from . import data
 
 __version__ = '0.1.0'
 
@@ -39,7 +40,7 @@ def install_as_sda(native_chains: bool = False) -> None:
     me = sys.modules[__name__]
     sys.modules['sda'] = me
     # every public submodule is imported BEFORE aliasing: a later `import sda.parallel` must find the one copy, not load a second
-    for sub in ('mcs', 'chains', 'nn', 'score', 'utils', 'observe', 'training', 'parallel', 'metrics', 'ops', 'engine', 'mlp', 'fused1d', 'experiments',
+    for sub in ('mcs', 'chains', 'nn', 'score', 'utils', 'observe', 'training', 'data', 'parallel', 'metrics', 'ops', 'engine', 'mlp', 'fused1d', 'experiments',
                 'experiments.kolmogorov', 'experiments.lorenz'):
         importlib.import_module('.' + sub, __name__)
     for full, mod in list(sys.modules.items()):

@@ -337,6 +337,8 @@ SIGNATURES = {
     'sda_loss_perturb': (c_int, [c_fp, c_int, c_int64, c_uint64, c_int64, c_int64, c_fp, c_int, c_float, c_float, c_int, c_fp, c_fp, c_fp, c_void_p]),
     'sda_loss_mse_plan': (c_int64, [c_int64, POINTER(c_int), POINTER(c_int)]),
     'sda_loss_mse': (c_int, [c_fp, c_fp, c_int64, c_fp, c_fp, c_fp, c_void_p]),
+    'sda_window_batch': (c_int, [c_fp, c_int64, c_int64, c_int64, c_int64, c_int64, c_int64, c_uint64, c_int64, c_fp, c_fp, c_void_p]),
+    'sda_window_batch_plan': (c_int, [c_int64, c_int64, c_int64, c_int64, c_uint64, c_int64, c_int64, POINTER(c_int64), POINTER(c_int64)]),
     'sda_mlp_fwd_win': (c_int, [POINTER(MlpDesc), POINTER(MlpWin), c_void_p]),
     'sda_mlp_bwd_win': (c_int, [POINTER(MlpDesc), POINTER(MlpWin), c_void_p]),
     'sda_mc_finish': (c_int, [c_fp, c_fp, c_fp, c_int, c_int, c_int, c_int, c_float, c_float, c_fp, c_int, c_fp, c_fp, c_fp, c_fp, c_void_p]),

@@ -4,7 +4,10 @@
 // Counter layouts in use (key = the 64-bit seed, low word first):
 //   noise    element 4q..4q+3 of row r in draw t :  {q_lo, r_lo, t_lo, t_hi ^ (q_hi << 16) ^ (r_hi << 24)}
 //   resample draw j of observation k             :  {j_lo, k_lo, 0x80000000 | j_hi, 0x52455341 ('RESA')}
-// A noise counter with t < 2^31 has bit 31 of word 2 clear, a resampling counter has it set: the two never collide.
+//   window   start of row b in batch s           :  {b, s_lo, 0x80000000 | s_hi, 0x57535441 ('WSTA')}
+//   shuffle  round r of value v in epoch e       :  {v, e_lo, 0x80000000 | e_hi, 0x53485530 ('SHU0') + r},  r = 0 .. 3
+// A noise counter with t < 2^31 has bit 31 of word 2 clear, the other three have it set, and those differ in word 3 (s, e < 2^63:
+// s_hi, e_hi < 2^31): no two layouts collide, so the dataset of a training run (dataset.hip) may reuse the seed of its loss noise.
 #pragma once
 #include <math.h>
 #include <stdint.h>
@@ -46,4 +49,14 @@ __host__ __device__ __forceinline__ philox4 philox_noise_words(int64_t q, uint64
                          (uint32_t)((uint64_t)draw >> 32) ^ ((uint32_t)((uint64_t)q >> 32) << 16) ^
                              ((uint32_t)(grow >> 32) << 24),
                          k0, k1);
+}
+
+// word 0 behind the window start of row b in global batch s (the `window` counter)
+__host__ __device__ __forceinline__ uint32_t philox_window_word(uint32_t b, int64_t s, uint32_t k0, uint32_t k1) {
+    return philox4x32_10(b, (uint32_t)s, 0x80000000u | (uint32_t)((uint64_t)s >> 32), 0x57535441u, k0, k1).v[0];
+}
+
+// word 0 behind round r of the epoch-e shuffle at half-word v (the `shuffle` counter)
+__host__ __device__ __forceinline__ uint32_t philox_shuffle_word(int r, uint32_t v, int64_t e, uint32_t k0, uint32_t k1) {
+    return philox4x32_10(v, (uint32_t)e, 0x80000000u | (uint32_t)((uint64_t)e >> 32), 0x53485530u + (uint32_t)r, k0, k1).v[0];
 }

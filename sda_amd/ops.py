@@ -914,6 +914,39 @@ def loss_mse(out: Tensor, eps: Tensor, with_g: bool = True):
     return loss, g
 
 
+def window_batch_plan(n: int, length: int, window: int, batch: int, seed: int, step: int, rows: int):
+    """Host only: (src_row, start), two int64 CPU tensors of ``rows`` entries -- the trajectory and first frame of every row of global
+    batch ``step`` of ``window_batch`` (sda_window_batch_plan, csrc/dataset.hip: the kernel's own index functions).  Needs no GPU."""
+    src_row, start = torch.empty(max(rows, 0), dtype=torch.int64), torch.empty(max(rows, 0), dtype=torch.int64)
+    p64 = ctypes.POINTER(ctypes.c_int64)
+    _lib.check(_lib.load().sda_window_batch_plan(n, length, window, batch, seed & 0xffffffffffffffff, step, rows,
+                                                 ctypes.cast(src_row.data_ptr(), p64), ctypes.cast(start.data_ptr(), p64)),
+               'sda_window_batch_plan')
+    return src_row, start
+
+
+def window_batch(data: Tensor, window: int, batch: int, rows: int, seed: int, step: int = 0, step_dev: Optional[Tensor] = None,
+                 out: Optional[Tensor] = None) -> Tensor:
+    """data (N, L, *frame) -> (rows, window, *frame): the rows of global batch s of the shuffled, randomly windowed dataset in one launch
+    (sda_window_batch, csrc/dataset.hip).  Row b is ``data[n_b, start_b:start_b + window]`` with ``(n_b, start_b)`` of
+    ``window_batch_plan``; s = ``step_dev[0]`` (a device int64 scalar the launch only reads: graph replay) or ``step``.  ``rows <= batch``
+    (the epoch's short last batch).  ``out``: a contiguous fp32 device tensor of rows * window * frame elements to fill."""
+    _dev(data, out)
+    if step_dev is not None and (not step_dev.is_cuda or step_dev.dtype != torch.int64 or step_dev.numel() != 1):
+        raise _lib.SdaHipError('step_dev must be a device int64 scalar')
+    if data.dim() < 2 or not data.is_contiguous() or data.numel() == 0:
+        raise _lib.SdaHipError('window_batch: data is a contiguous tensor (N, L, *frame) with at least one element')
+    n, length = data.shape[:2]
+    f = data.numel() // (n * length)
+    if out is None:
+        out = torch.empty((max(rows, 0), max(window, 0)) + tuple(data.shape[2:]), device=data.device, dtype=torch.float32)
+    elif not out.is_contiguous() or out.numel() != rows * window * f or out.device != data.device:
+        raise _lib.SdaHipError('window_batch: out is a contiguous tensor of rows * window * frame elements on the device of data')
+    _lib.check(_lib.load().sda_window_batch(data.data_ptr(), n, length, f, window, batch, rows, seed & 0xffffffffffffffff, step,
+                                            _ptr(step_dev), out.data_ptr(), _stream()), 'sda_window_batch')
+    return out
+
+
 def mlp_wgrad_work_floats(d: '_lib.MlpWgradDesc') -> int:
     """Floats of the ``work`` buffer sda_mlp_wgrad needs for this descriptor (``d.work`` is not read)."""
     floats = _lib.load().sda_mlp_wgrad_work_floats(ctypes.byref(d))

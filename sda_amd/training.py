@@ -429,10 +429,15 @@ class GraphedStep:
     ``load_state_dict()`` or a direct ``optimizer.step()`` observe them, or on request (``sync_state()``).
 
     Parameters, optimizer state and ``c`` keep their storage while a graph is alive (``optimizer.load_state_dict`` drops the graph: the
-    next step captures again).  fp32 multiply only."""
+    next step captures again).  fp32 multiply only.
+
+    ``GraphedStep(..., data=ds, batch_size=B)`` with a ``sda_amd.data.DeviceTrajectories`` feeds itself: ``step()`` takes no batch, the
+    body begins with ``ds.draw(B, out=<the static input>)`` (one gather launch reading the dataset's device cursor, and its increment), so
+    a replay copies nothing in.  An epoch's short last batch, known from the dataset's host mirror, runs the same body uncaptured on
+    ``ds.draw(B)``.  Without ``data=`` nothing changes."""
 
     def __init__(self, sde, optimizer, *, seed: int, c: torch.Tensor = None, rows: int = 1024, mlp: bool = True, wgrad: str = 'general',
-                 net1d: bool = False):
+                 net1d: bool = False, data=None, batch_size: int = None):
         from . import ops
         if not isinstance(optimizer, AdamW):
             raise TypeError(f'GraphedStep drives sda_amd.training.AdamW (got {type(optimizer).__name__})')
@@ -440,9 +445,16 @@ class GraphedStep:
             raise NotImplementedError(f'parameter gradients are formed with the fp32 multiply only (ops.MULTIPLY = {ops.MULTIPLY!r})')
         if rows < 1:
             raise ValueError('GraphedStep: rows >= 1')
+        if data is not None and (batch_size is None or batch_size < 1):
+            raise ValueError('GraphedStep(data=...): batch_size >= 1')
+        if data is None and batch_size is not None:
+            raise ValueError('GraphedStep: batch_size goes with data=')
         self.sde, self.opt, self.c, self.rows = sde, optimizer, c, int(rows)
+        self.data, self.batch_size = data, batch_size
         self._route = dict(mlp=bool(mlp), wgrad=_check_route(wgrad), net1d=bool(net1d))
         self.device = next(sde.parameters()).device
+        if data is not None and data.data.device != self.device:
+            raise ValueError(f'GraphedStep(data=...): the dataset lives on {data.data.device}, the net on {self.device}')
         self._ctr = torch.zeros(2, device=self.device, dtype=torch.int64)          # {training step of the keyed draws, table row}
         self.noise = KeyedLossNoise(seed, counter=self._ctr[0:1])
         self._irow = self._ctr[1:2]
@@ -543,8 +555,11 @@ class GraphedStep:
 
     # ------------------------------------------------------------------ one step
     def _body(self, x, build_table: bool):
-        """loss, backward, the optimizer launches, loss_sum and the counters -> (loss, buckets, plans).  Gradients are None on entry."""
+        """loss, backward, the optimizer launches, loss_sum and the counters -> (loss, buckets, plans).  Gradients are None on entry.
+        With ``data=``: ``x`` is the static input to draw the next batch into, or None (an uncaptured batch of its own storage)."""
         from . import ops
+        if self.data is not None:
+            x = self.data.draw(self.batch_size, out=x)
         had, prev = 'loss_noise' in self.sde.__dict__, self.sde.__dict__.get('loss_noise')
         self.sde.loss_noise = self.noise
         try:
@@ -595,7 +610,7 @@ class GraphedStep:
     def _eager(self, x):
         self.sync_state()                                   # (the buckets are keyed on the step counts)
         self._clear_grads()
-        loss, buckets, plans = self._body(x.contiguous(), build_table=True)
+        loss, buckets, plans = self._body(x if self.data is not None else x.contiguous(), build_table=True)
         self._after(buckets, plans)
         self._clear_grads()
         return loss, buckets
@@ -609,7 +624,10 @@ class GraphedStep:
         torch.cuda.current_stream(dev).wait_stream(side)
         self.sync_state()
         self._table_for(buckets)                            # (a fresh table where the warm-up used its last row: never inside the capture)
-        self._x = x.contiguous().clone()
+        if self.data is not None:
+            self._x = torch.empty(self.data.batch_shape(self.batch_size), device=self.device, dtype=torch.float32)
+        else:
+            self._x = x.contiguous().clone()
         self._stale_packs()
         torch.cuda.synchronize(dev)
         graph = torch.cuda.CUDAGraph()
@@ -619,20 +637,28 @@ class GraphedStep:
         finally:
             # nothing ran: the packings the capture made "current" are not (outside consumers re-pack; the graph re-packs at its head)
             self._stale_packs()
-        self._graph, self._shape, self._loss = graph, tuple(x.shape), static_loss
+        self._graph, self._shape, self._loss = graph, tuple(self._x.shape), static_loss
         # what the graph's launches point at: the buckets (parameters, pool gradients, moments) and the slabs the optimizer launch writes
         self._cap = (cap_buckets, plans, self._baked(cap_buckets), [(plan, plan.wf, plan.wb, plan.bias) for plan in plans.values()])
         return loss
 
-    def step(self, x: torch.Tensor) -> torch.Tensor:
-        """One training step on the batch ``x`` -> the 0-dim loss (the graph's static tensor once captured: valid until the next step)."""
+    def step(self, x: torch.Tensor = None) -> torch.Tensor:
+        """One training step on the batch ``x`` (with ``data=``: on the dataset's next batch, ``x`` is not given) -> the 0-dim loss (the
+        graph's static tensor once captured: valid until the next step)."""
+        if (x is None) != (self.data is not None):
+            raise TypeError('GraphedStep.step: a batch x without data=, no argument with data=')
+        if self.data is not None:
+            shape = self.data.batch_shape(self.data.rows(self.batch_size))
+            full = shape[0] == self.batch_size
+        else:
+            shape, full = tuple(x.shape), True
         if self._graph is not None and self._baked(self._cap[0]) != self._cap[2]:
             self._drop_graph()
-        if self._graph is not None and tuple(x.shape) == self._shape:
+        if self._graph is not None and shape == self._shape:
             self._table_for(self._cap[0])                   # (drops the graph if the table had to move)
-        if self._graph is None:
+        if self._graph is None and full:
             return self._capture(x)
-        if tuple(x.shape) != self._shape:
+        if self._graph is None or shape != self._shape:
             return self._eager(x)[0]
         buckets, plans, _baked, slabs = self._cap
         for plan, wf, wb, bias in slabs:                    # a parameter changed from outside: re-pack INTO the slabs the graph points at
@@ -641,7 +667,10 @@ class GraphedStep:
                 if plan.wf is not wf:
                     wf.copy_(plan.wf); wb.copy_(plan.wb); bias.copy_(plan.bias)
                     plan.wf, plan.wb, plan.bias = wf, wb, bias
-        self._x.copy_(x)
+        if self.data is None:
+            self._x.copy_(x)
         self._graph.replay()
+        if self.data is not None:
+            self.data.replayed()
         self._after(buckets, plans)
         return self._loss

@@ -4,7 +4,9 @@ sda/utils.py:19-25,40-42; the evaluation metrics ``bpf`` / ``emd`` / ``mmd`` of 
 ``experiments/*/train.py`` reach through ``from sda.utils import *`` -- ``random_config`` / ``save_config``, sda/utils.py:28-37 --
 are plain host code and kept).  ``loop`` is the reference's training loop (sda/utils.py:89-165: AdamW, a linear / cosine /
 exponential LambdaLR schedule, ``(loss_train, loss_valid, lr)`` per epoch); it trains with parameter gradients switched on
-(``sda_amd.training``).  The datasets (``TrajectoryDataset``: h5py files) stay out of scope.
+(``sda_amd.training``).  The reference's ``TrajectoryDataset`` (an h5py file behind a host ``DataLoader``) has a device-resident
+counterpart, ``sda_amd.data.DeviceTrajectories`` (re-exported here): ``loop`` draws its batches on the device, and with ``graph=True``
+inside the replayed step; any other dataset object goes through a ``DataLoader`` as in the reference.
 
 ``from sda.utils import *`` in the reference's drivers also hands on that module's own imports (sda/utils.py:3-16:
 ``json``, ``math``, ``torch``, ``Path``, ``Tensor``, the ``typing`` names, everything of ``sda.score`` and, where installed,
@@ -25,6 +27,7 @@ except ImportError:
     pass
 
 from . import training
+from .data import DeviceTrajectories  # (the device-resident counterpart of sda.utils.TrajectoryDataset)
 from .score import *  # noqa: F401,F403  (sda/utils.py:16)
 from .metrics import bpf, emd, mmd  # noqa: F401  (sda.utils.bpf / emd / mmd)
 
@@ -88,9 +91,22 @@ def loop(sde: 'VPSDE', trainset, validset, epochs: int = 256, batch_size: int = 
     up-sampling tails' as well; ``net1d=True`` trains a single-level 1-D U-Net on the whole-net kernels (``sda_amd.training``).
     ``graph=True`` (implies ``fused``) replays every training step as one hipGraph (``sda_amd.training.GraphedStep``): the loss draws its
     noise keyed on ``seed`` and the step index instead of torch's generator, and the epoch's mean loss is read back once; the items'
-    ``kwargs`` must then be empty."""
+    ``kwargs`` must then be empty.  A ``trainset`` / ``validset`` that is a ``sda_amd.data.DeviceTrajectories`` is iterated with its own
+    ``batches(batch_size)`` (keyed shuffle and windows, no host tensor work); with ``graph=True`` the stepper draws from such a
+    ``trainset`` inside the graph (``GraphedStep(data=...)``)."""
     from torch.utils.data import DataLoader
-    loaders = [DataLoader(ds, batch_size=batch_size, shuffle=True) for ds in (trainset, validset)]
+
+    class _Resident:
+        """A ``DeviceTrajectories`` as the loop iterates a loader: one epoch of ``(x, {})`` batches per ``iter``."""
+
+        def __init__(self, ds):
+            self.ds = ds
+
+        def __iter__(self):
+            return self.ds.batches(batch_size)
+    loaders = [_Resident(ds) if isinstance(ds, DeviceTrajectories) else DataLoader(ds, batch_size=batch_size, shuffle=True)
+               for ds in (trainset, validset)]
+    fed = graph and isinstance(trainset, DeviceTrajectories)
     if optimizer != 'AdamW':
         raise ValueError(f'optimizer {optimizer!r} (the loop knows AdamW)')
     if fused or graph:
@@ -100,16 +116,20 @@ def loop(sde: 'VPSDE', trainset, validset, epochs: int = 256, batch_size: int = 
     if scheduler not in _SCHEDULES:
         raise ValueError(f'scheduler {scheduler!r} (expected one of {sorted(_SCHEDULES)})')
     sched = torch.optim.lr_scheduler.LambdaLR(opt, lr_lambda=_SCHEDULES[scheduler](epochs))
-    stepper = training.GraphedStep(sde, opt, seed=seed, mlp=True, wgrad=wgrad, net1d=net1d) if graph else None
+    stepper = None
     if graph:
+        stepper = training.GraphedStep(sde, opt, seed=seed, mlp=True, wgrad=wgrad, net1d=net1d,
+                                       **(dict(data=trainset, batch_size=batch_size) if fed else {}))
         opt._opt_called = True       # (the steps run inside the graph: LambdaLR would warn that optimizer.step() was never called)
     for _ in range(epochs):
         losses_train, losses_valid = [], []
         sde.train()
         if graph:
             stepper.loss_sum.zero_()
-            n = 0
-            for batch in loaders[0]:
+            n = trainset.remaining(batch_size) if fed else 0
+            for _step in range(n):                           # (the stepper draws its own batches: nothing to hand over)
+                stepper.step()
+            for batch in () if fed else loaders[0]:
                 x, kwargs = _to(batch, device=device)
                 if kwargs:
                     raise NotImplementedError(f'loop(graph=True) trains on items without keyword arguments (got {sorted(kwargs)})')
