@@ -3,7 +3,9 @@
 Every function launches a hand-written gfx950 kernel on the CURRENT torch stream.  There is no CPU path:
 tensors must live on a HIP device (`_dev()` raises otherwise).
 """
+import contextlib
 import ctypes
+import gc
 import math
 import os
 from typing import Optional
@@ -64,6 +66,24 @@ def _ptr(t: Optional[Tensor]):
 
 def _stream():
     return torch.cuda.current_stream().cuda_stream
+
+
+@contextlib.contextmanager
+def capture_without_gc():
+    """Around a stream capture: collect cyclic garbage first, and keep the collector off until the capture has ended.
+
+    A generational collection that happens to start inside ``torch.cuda.graph`` runs the destructors of whatever dead device objects it
+    finds -- an earlier sampler's graph with its private pool, streams, tensors held by a reference cycle -- and a runtime call made
+    from there is illegal while a stream is capturing: the process aborts in the middle of the collection.  ``torch.cuda.graph`` itself
+    no longer collects on entry, so when this happens depends on how many objects the process has allocated before."""
+    was_enabled = gc.isenabled()
+    gc.collect()
+    gc.disable()
+    try:
+        yield
+    finally:
+        if was_enabled:
+            gc.enable()
 
 
 def round_up(v: int, m: int) -> int:

@@ -612,7 +612,7 @@ class PCSampler:
         torch.cuda.current_stream(dev).wait_stream(side)
         torch.cuda.synchronize(dev)
         graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(graph):
+        with ops.capture_without_gc(), torch.cuda.graph(graph):
             self._graph_body()
         self.x.copy_(keep_x)
         torch.cuda.set_rng_state(keep_rng, dev)

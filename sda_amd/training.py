@@ -630,9 +630,10 @@ class GraphedStep:
             self._x = x.contiguous().clone()
         self._stale_packs()
         torch.cuda.synchronize(dev)
+        from . import ops
         graph = torch.cuda.CUDAGraph()
         try:
-            with torch.cuda.graph(graph):                   # (gradients are None: backward allocates them from the graph's pool)
+            with ops.capture_without_gc(), torch.cuda.graph(graph):    # (gradients are None: backward allocates them from the graph's pool)
                 static_loss, cap_buckets, plans = self._body(self._x, build_table=False)
         finally:
             # nothing ran: the packings the capture made "current" are not (outside consumers re-pack; the graph re-packs at its head)

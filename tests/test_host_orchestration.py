@@ -304,3 +304,40 @@ def test_denoising_loss_is_a_value_only():
     for p in net.parameters():
         p.requires_grad_(False)
     assert torch.isfinite(sde.loss(x))                   # frozen parameters: allowed with grad mode on
+
+
+def test_capture_without_gc_collects_first_and_restores_the_collector():
+    """ops.capture_without_gc (around every stream capture of the package): a dead reference cycle is gone before the body runs, no
+    generational collection can start inside it, and the collector's state is put back -- also after an exception, also when it was off."""
+    import gc
+    import weakref
+    from sda_amd import ops
+
+    class Node:
+        pass
+
+    def dead_cycle():
+        a, b = Node(), Node()
+        a.other, b.other = b, a
+        return weakref.ref(a)
+
+    assert gc.isenabled()
+    gc.disable()                                             # (nothing may collect the cycle before the manager does)
+    try:
+        ref = dead_cycle()
+        assert ref() is not None
+        with ops.capture_without_gc():
+            assert ref() is None and not gc.isenabled()
+        assert not gc.isenabled()                            # it was off before: it stays off
+    finally:
+        gc.enable()
+    with ops.capture_without_gc():
+        assert not gc.isenabled()
+        inside = dead_cycle()
+        junk = [[i] for i in range(5000)]                    # far past the generation-0 threshold
+        assert inside() is not None and len(junk) == 5000
+    assert gc.isenabled()
+    with pytest.raises(RuntimeError, match='boom'):
+        with ops.capture_without_gc():
+            raise RuntimeError('boom')
+    assert gc.isenabled()
