@@ -110,6 +110,7 @@ class _ConvCache:
         self._fwd = None
         self._bwd = {}
         self._parity = None
+        self._parity4 = None                             # (the parity classes it was built from, their packings back to back)
 
     def _sync(self):
         # (data_ptr, _version) catches optimiser steps, .to(), load_state_dict and in-place ops on the parameter; writes
@@ -118,7 +119,7 @@ class _ConvCache:
         key = (w.data_ptr(), ops.tensor_version(w), str(w.device), None if self.conv.bias is None else ops.tensor_version(self.conv.bias),
                ops.MULTIPLY)                            # (switching the multiply re-packs: the f16 x 2 packing is made with the others)
         if key != self._key:
-            self._key, self._fwd, self._bwd, self._parity = key, None, {}, None
+            self._key, self._fwd, self._bwd, self._parity, self._parity4 = key, None, {}, None, None
 
     def invalidate(self):
         self._key = None
@@ -177,12 +178,31 @@ class _ConvCache:
         classes = self.bwd_parity()
         if not classes or len(classes) != 4 or [(py, px) for py, px, _, _ in classes] != [(0, 0), (0, 1), (1, 0), (1, 1)]:
             return None
-        if getattr(self, '_parity4', None) is None or self._parity4[0] is not classes:
+        if self._parity4 is None or self._parity4[0] is not classes:
             pks = [pk for _, _, pk, _ in classes]
             if any(pk.k_pad != pks[0].k_pad or pk.m_pad != pks[0].m_pad or pk.m_pad != pk.m_real for pk in pks):
                 return None
             self._parity4 = (classes, torch.cat([pk.packed for pk in pks]))
         return self._parity4[1]
+
+
+def conv_desc(pk: Optional[PackedConv], src: dict, out: Optional[Tensor], ho: int, wo: int, *, circular: bool, cc: Optional[_ConvCache] = None,
+              stride=(1, 1), up=(1, 1), zins=(1, 1), bias=None, mod=None, mod_sn: int = 0, ln=None, act_in: int = 0, dact_z=None,
+              act_d: int = 0, res=None, ctx=None, cctx: int = 0, ctx_sn: int = 0, pad=None, out_strides=(0, 0, 0, 0), pool=(1, 1)):
+    """The sda_conv_desc of one launch of ``pk`` writing ``out``; ``pk`` None: the weight-gradient form of the layer ``cc`` -- its
+    forward loader over ``src`` with no weights and no output (csrc/conv_wgrad.hip reads the loader fields only)."""
+    ptr = ops._ptr
+    if pk is None:
+        weights = dict(w_ptr=0, cin_pad=0, cout_pad=0, cout=cc.cout, kh=cc.kh, kw=cc.kw, out_ptr=0, mt=1)
+    else:
+        zp = pk.wino4_zp() if tuple(up) == (2, 2) or tuple(pool) == (2, 2) else None
+        weights = dict(w_ptr=pk.packed.data_ptr(), cin_pad=pk.k_pad, cout_pad=pk.m_pad, cout=pk.m_real, kh=pk.kh, kw=pk.kw,
+                       out_ptr=out.data_ptr(), mt=pk.mt, w_wino4_ptr=ptr(pk.wino4), w_wino4_zp_ptr=ptr(zp))
+    return make_conv_desc(**src, **weights, ho=ho, wo=wo, stride_h=stride[0], stride_w=stride[1], circular=circular,
+                          up_h=up[0], up_w=up[1], zins_h=zins[0], zins_w=zins[1], ctx_ptr=ptr(ctx), cctx=cctx, ctx_sn=ctx_sn,
+                          mod_ptr=ptr(mod), mod_sn=mod_sn, ln_mean_ptr=None if ln is None else ln[0].data_ptr(),
+                          ln_rstd_ptr=None if ln is None else ln[1].data_ptr(), act_in=act_in, bias_ptr=ptr(bias),
+                          dact_z_ptr=ptr(dact_z), act_d=act_d, res_ptr=ptr(res), pad=pad, out_strides=out_strides, pool=pool)
 
 
 def launch_conv(pk: PackedConv, src: dict, out: Tensor, ho: int, wo: int, *, circular: bool, stride=(1, 1), up=(1, 1),
@@ -200,27 +220,16 @@ def launch_conv(pk: PackedConv, src: dict, out: Tensor, ho: int, wo: int, *, cir
         for t in (dact_z, res):
             if t is not None and tuple(t.stride()) != out_strides:
                 raise SdaHipError('conv epilogue operands must share the layout of the output view')
-    zp = pk.wino4_zp() if (tuple(up) == (2, 2) or tuple(pool) == (2, 2)) and hasattr(pk, 'wino4_zp') else None
-    d = make_conv_desc(**src, w_ptr=pk.packed.data_ptr(), cin_pad=pk.k_pad, cout_pad=pk.m_pad, cout=pk.m_real,
-                       kh=pk.kh, kw=pk.kw, out_ptr=out.data_ptr(), ho=ho, wo=wo, mt=pk.mt,
-                       stride_h=stride[0], stride_w=stride[1], circular=circular, up_h=up[0], up_w=up[1],
-                       zins_h=zins[0], zins_w=zins[1],
-                       ctx_ptr=None if ctx is None else ctx.data_ptr(), cctx=cctx, ctx_sn=ctx_sn,
-                       mod_ptr=None if mod is None else mod.data_ptr(), mod_sn=mod_sn,
-                       ln_mean_ptr=None if ln is None else ln[0].data_ptr(),
-                       ln_rstd_ptr=None if ln is None else ln[1].data_ptr(),
-                       act_in=act_in, bias_ptr=None if bias is None else bias.data_ptr(),
-                       dact_z_ptr=None if dact_z is None else dact_z.data_ptr(), act_d=act_d,
-                       res_ptr=None if res is None else res.data_ptr(),
-                       w_wino4_ptr=None if getattr(pk, 'wino4', None) is None else pk.wino4.data_ptr(),
-                       pad=pad, out_strides=out_strides, pool=pool, w_wino4_zp_ptr=None if zp is None else zp.data_ptr())
+    d = conv_desc(pk, src, out, ho, wo, circular=circular, stride=stride, up=up, zins=zins, bias=bias, mod=mod, mod_sn=mod_sn, ln=ln,
+                  act_in=act_in, dact_z=dact_z, act_d=act_d, res=res, ctx=ctx, cctx=cctx, ctx_sn=ctx_sn, pad=pad,
+                  out_strides=out_strides, pool=pool)
     if pool != (1, 1):
-        if tuple(pool) == (2, 2) and ops.H2_POOL and x_amax is not None and getattr(pk, 'h2', None) is not None:
+        if tuple(pool) == (2, 2) and ops.H2_POOL and x_amax is not None and pk.h2 is not None:
             packing = pk.h2_pool()
             if packing is not None and ops.conv_h2(d, pk, x_amax, out_amax, packing=packing):
                 return d
         return d if ops.conv_pooled(d) else None
-    if getattr(pk, 'h2', None) is not None and parity4_w is None:
+    if pk.h2 is not None and parity4_w is None:
         # OPT-IN f16 x 2 multiply (ops.MULTIPLY): behind a LayerNorm the loader's output is bounded by sqrt(channels); otherwise the
         # caller says how large the input is (the producing launch's out_amax, or an ops.absmax pass)
         bound = math.sqrt(src['cx']) if ln is not None else x_amax
@@ -246,6 +255,51 @@ def launch_conv(pk: PackedConv, src: dict, out: Tensor, ho: int, wo: int, *, cir
     return d
 
 
+def input_scale(pk: PackedConv, x: Tensor, reported: Optional[Tensor]) -> Optional[Tensor]:
+    """The input scale of an f16 x 2 launch of ``pk`` over ``x`` (launch_conv's x_amax), a device scalar: what x's producer
+    ``reported`` (an out_amax slot it wrote), else one streaming read of x into pk's scratch scalar.  None -- the fp32 kernels --
+    without the f16 x 2 packing or for a strided x."""
+    if pk.h2 is None or not x.is_contiguous():
+        return None
+    return reported if reported is not None else ops.absmax(x, pk.in_amax)
+
+
+def _reported(d, slot: Optional[Tensor]) -> Optional[Tensor]:
+    """``slot`` if the launch ``d`` (launch_conv's return) ran on conv_h2 and so wrote its out_amax; else None: the fp32 kernels
+    report nothing, the slot is stale."""
+    return slot if d is not None and d.w_h2 else None
+
+
+def _report_slot(owner, device) -> Tensor:
+    """The device scalar ``owner``'s ln_bwd launch reports max |gradient| through (f16 x 2 route), made on first use -- in warm-up,
+    never under capture."""
+    if owner.report is None or owner.report.device != device:
+        owner.report = torch.zeros(1, device=device, dtype=torch.float32)
+    return owner.report
+
+
+# what each layer kind's FORWARD loader reads, as (source fields, loader options): the forward launch and the layer's weight
+# gradient (UNetEngine._wgrad) both build their descriptor from these
+def _head_loader(hd: _ConvCache, lvl: int, a: Optional[Tensor], src: Source, lo: int, n: int):
+    if lvl == 0:                                         # the strided / window view of the input and its context rows
+        sdesc, ctx = _source0(src, lo, n)
+        return sdesc, dict(stride=(hd.sh, hd.sw), ctx=ctx, cctx=src.cctx, ctx_sn=src.ctx_sn)
+    return planar_source(a), dict(stride=(hd.sh, hd.sw))
+
+
+def _conv1_loader(a: Tensor, mod, mod_sn: int, mean: Tensor, rstd: Tensor):
+    return planar_source(a), dict(mod=mod, mod_sn=mod_sn, ln=(mean, rstd))
+
+
+def _conv2_loader(blk: '_Block', z: Tensor):
+    return planar_source(z), dict(act_in=blk.act)
+
+
+def _tail_loader(a: Tensor, ln=None, up=(1, 1)):
+    """Level 0: the plain tensor; deeper: LN(a) through the nearest up-sample."""
+    return planar_source(a), dict(ln=ln, up=up)
+
+
 class _Block:
     def __init__(self, block, width: int, mod_off: int):
         from .nn import LayerNorm, activation_id
@@ -259,10 +313,26 @@ class _Block:
         self.project = block.project[0]
         self.width = width
         self.mod_off = mod_off
+        self.report = None                               # _report_slot: max |gradient w.r.t. the block's input| of its last VJP
 
 
 class _Level:
-    pass
+    """One resolution of the U-Net: its head and tail convolutions and its blocks; ``mod_off``: where its blocks' modulation rows
+    start (``mod_end``: where the next level's do)."""
+
+    def __init__(self, unet, lvl: int, mod_off: int):
+        j = len(unet.hidden_blocks) - 1 - lvl            # tails / ascent are stored deepest first (nn.py:179-182)
+        self.C = unet.hidden_channels[lvl]
+        self.head = _ConvCache(unet.heads[lvl] if lvl == 0 else unet.heads[lvl][0])
+        self.tail_ln = None if lvl == 0 else unet.tails[j][0]
+        self.tail = _ConvCache(unet.tails[j] if lvl == 0 else unet.tails[j][2])
+        self.descent, self.ascent = [], []
+        for blocks, mine in ((unet.descent[lvl], self.descent), (unet.ascent[j], self.ascent)):
+            for blk in blocks:
+                mine.append(_Block(blk, self.C, mod_off))
+                mod_off += self.C
+        self.mod_end = mod_off
+        self.report = None                               # _report_slot: max |gradient w.r.t. the level's deepest input| (its tail's VJP)
 
 
 class UNetEngine:
@@ -273,27 +343,11 @@ class UNetEngine:
         self.unet = unet
         self.unbiased = LN_UNBIASED
         self.depth = len(unet.hidden_blocks)
-        D = self.depth
         self.levels: List[_Level] = []
         off = 0
-        for lvl in range(D):
-            lev = _Level()
-            lev.C = unet.hidden_channels[lvl]
-            j = D - 1 - lvl                                  # tails / ascent are stored deepest first (nn.py:179-182)
-            head = unet.heads[lvl] if lvl == 0 else unet.heads[lvl][0]
-            lev.head = _ConvCache(head)
-            if lvl == 0:
-                lev.tail = _ConvCache(unet.tails[j])
-                lev.tail_ln = None
-            else:
-                lev.tail_ln = unet.tails[j][0]
-                lev.tail = _ConvCache(unet.tails[j][2])
-            lev.descent, lev.ascent = [], []
-            for blk in unet.descent[lvl]:
-                lev.descent.append(_Block(blk, lev.C, off)); off += lev.C
-            for blk in unet.ascent[j]:
-                lev.ascent.append(_Block(blk, lev.C, off)); off += lev.C
-            self.levels.append(lev)
+        for lvl in range(self.depth):
+            self.levels.append(_Level(unet, lvl, off))
+            off = self.levels[-1].mod_end
         self.mod_total = off
         self._proj_key = None
         self._proj = None
@@ -337,12 +391,8 @@ class UNetEngine:
         """Drop every packed-weight cache (forward / backward-data / Winograd / parity packs, the concatenated projection
         matrix).  The caches re-key themselves on parameter pointer and version, which in-place writes through ``.data``
         (``p.data.copy_(ema)``) do not change: call this after such a write."""
-        for lev in self.levels:
-            lev.head.invalidate()
-            lev.tail.invalidate()
-            for blk in lev.descent + lev.ascent:
-                blk.conv1.invalidate()
-                blk.conv2.invalidate()
+        for cc in self.convs():
+            cc.invalidate()
         self._proj_key = None
         self.__dict__.pop('_net1d_cache', None)
 
@@ -680,15 +730,14 @@ class UNetEngine:
         ops.ln_stats(a, mod, mod_sn, blk.ln.eps, self.unbiased, mean, rstd)
         z = torch.empty_like(a)
         pk = c1.fwd()
-        z_amax = getattr(pk, 'out_amax', None)           # (f16 x 2 launches report max |z|: |act(z)| <= max(|z|, 0.28) scales conv2's input)
-        d1 = launch_conv(pk, planar_source(a), z, h, w, circular=c1.circular, bias=pk.bias, mod=mod, mod_sn=mod_sn,
-                         ln=(mean, rstd), out_amax=z_amax)
-        if not (d1 is not None and d1.w_h2):
-            z_amax = None                                # (the fp32 kernels served conv1: nothing was reported, the slot is stale)
+        src1, opts1 = _conv1_loader(a, mod, mod_sn, mean, rstd)
+        # (f16 x 2 launches report max |z|: |act(z)| <= max(|z|, 0.28) scales conv2's input)
+        z_slot = pk.out_amax if pk.h2 is not None else None
+        d1 = launch_conv(pk, src1, z, h, w, circular=c1.circular, bias=pk.bias, out_amax=z_slot, **opts1)
         y = torch.empty_like(a)
-        c2 = blk.conv2
         pk = c2.fwd()
-        launch_conv(pk, planar_source(z), y, h, w, circular=c2.circular, bias=pk.bias, act_in=blk.act, res=a, x_amax=z_amax)
+        src2, opts2 = _conv2_loader(blk, z)
+        launch_conv(pk, src2, y, h, w, circular=c2.circular, bias=pk.bias, res=a, x_amax=_reported(d1, z_slot), **opts2)
         if saved is not None:
             saved.append((a, mean, rstd, z))
         return y
@@ -709,23 +758,17 @@ class UNetEngine:
         for lvl, lev in enumerate(L):
             hd = lev.head
             pk = hd.fwd()
-            if lvl == 0:
-                ho, wo = conv_out_size(h, hd.kh, hd.sh), conv_out_size(w, hd.kw, hd.sw)
-                a = torch.empty(n, lev.C, ho, wo, device=dev, dtype=torch.float32)
-                sdesc, ctx = _source0(src, lo, n)
-                launch_conv(pk, sdesc, a, ho, wo, circular=hd.circular, stride=(hd.sh, hd.sw), bias=pk.bias, ctx=ctx,
-                            cctx=src.cctx, ctx_sn=src.ctx_sn)
-            else:
-                ho, wo = conv_out_size(h, hd.kh, hd.sh), conv_out_size(w, hd.kw, hd.sw)
-                a2 = torch.empty(n, lev.C, ho, wo, device=dev, dtype=torch.float32)
+            ho, wo = conv_out_size(h, hd.kh, hd.sh), conv_out_size(w, hd.kw, hd.sw)
+            a2 = torch.empty(n, lev.C, ho, wo, device=dev, dtype=torch.float32)
+            hsrc, hopts = _head_loader(hd, lvl, a, src, lo, n)
+            xa = None
+            if lvl > 0:
                 if save and train:
                     saved['head_in'][lvl] = a
-                xa = None
-                if ops.MULTIPLY == 'f16x2' and ops.H2_S2 and (hd.sh, hd.sw) == (2, 2) and getattr(pk, 'h2', None) is not None and a.is_contiguous():
-                    xa = ops.absmax(a, pk.in_amax)       # (the f16 x 2 parity-plane form needs its input's scale: one streaming read)
-                launch_conv(pk, planar_source(a), a2, ho, wo, circular=hd.circular, stride=(hd.sh, hd.sw), bias=pk.bias, x_amax=xa)
-                a = a2
-            h, w = ho, wo
+                if ops.H2_S2 and (hd.sh, hd.sw) == (2, 2):
+                    xa = input_scale(pk, a, None)        # (the f16 x 2 parity-plane form needs its input's scale: one streaming read)
+            launch_conv(pk, hsrc, a2, ho, wo, circular=hd.circular, bias=pk.bias, x_amax=xa, **hopts)
+            a, h, w = a2, ho, wo
             dims.append((h, w))
             for bi, blk in enumerate(lev.descent):
                 rec = [] if save else None
@@ -753,15 +796,16 @@ class UNetEngine:
                 rstd = torch.empty_like(mean)
                 ops.ln_stats(a, None, 0, lev.tail_ln.eps, self.unbiased, mean, rstd)
                 t = torch.empty(n, L[lvl - 1].C, hu, wu, device=dev, dtype=torch.float32)
-                launch_conv(pk, planar_source(a), t, hu, wu, circular=tl.circular, up=(uh, uw), bias=pk.bias,
-                            ln=(mean, rstd), res=skips.pop())
+                tsrc, topts = _tail_loader(a, (mean, rstd), (uh, uw))
+                launch_conv(pk, tsrc, t, hu, wu, circular=tl.circular, bias=pk.bias, res=skips.pop(), **topts)
                 if save:
                     saved['tails'][lvl] = (a, mean, rstd)
                 a, h, w = t, hu, wu
             else:
                 if save and train:
                     saved['tail0_in'] = a
-                launch_conv(pk, planar_source(a), out, h, w, circular=tl.circular, bias=pk.bias)
+                tsrc, topts = _tail_loader(a)
+                launch_conv(pk, tsrc, out, h, w, circular=tl.circular, bias=pk.bias, **topts)
         if save:
             saved['dims'] = dims
         return saved
@@ -781,42 +825,90 @@ class UNetEngine:
             return gx, None
         gz = torch.empty_like(a)
         pk2 = c2.bwd()
-        g_amax = gz_amax = None
-        if getattr(pk2, 'h2', None) is not None and g.is_contiguous():
-            # (the producer's own report, else one streaming read of g)
-            g_amax, gz_amax = (g_amax_in if g_amax_in is not None else ops.absmax(g, pk2.in_amax)), pk2.out_amax
-        d2 = launch_conv(pk2, planar_source(g), gz, h, w, circular=c2.circular, dact_z=z, act_d=blk.act, x_amax=g_amax, out_amax=gz_amax)
-        if not (d2 is not None and d2.w_h2):
-            gz_amax = None
+        g_amax = input_scale(pk2, g, g_amax_in)
+        gz_slot = pk2.out_amax if g_amax is not None else None
+        d2 = launch_conv(pk2, planar_source(g), gz, h, w, circular=c2.circular, dact_z=z, act_d=blk.act, x_amax=g_amax, out_amax=gz_slot)
         if pg is not None:                               # conv2 saw act(z) and produced the block's residual branch (cotangent g)
-            self._wgrad(pg, c2, planar_source(z), g, h, w, act_in=blk.act)
-            self._wgrad(pg, c1, planar_source(a), gz, h, w, mod=mod, mod_sn=mod_sn, ln=(mean, rstd))
+            self._wgrad(pg, c2, _conv2_loader(blk, z), g, h, w)
+            self._wgrad(pg, c1, _conv1_loader(a, mod, mod_sn, mean, rstd), gz, h, w)
         gh = torch.empty_like(a)
-        c1 = blk.conv1
-        launch_conv(c1.bwd(), planar_source(gz), gh, h, w, circular=c1.circular, x_amax=gz_amax)
+        launch_conv(c1.bwd(), planar_source(gz), gh, h, w, circular=c1.circular, x_amax=_reported(d2, gz_slot))
         gx = torch.empty_like(a)
-        gx_amax = None
-        if getattr(pk2, 'h2', None) is not None:
-            # f16 x 2 route: the consumer of gx is (mostly) the previous block's conv2^T -- report max |gx| from this launch
-            gx_amax = getattr(blk, '_gx_amax', None)
-            if gx_amax is None or gx_amax.device != a.device:
-                gx_amax = blk._gx_amax = torch.zeros(1, device=a.device, dtype=torch.float32)
+        # f16 x 2 route: the consumer of gx is (mostly) the previous block's conv2^T -- report max |gx| from this launch
+        gx_amax = _report_slot(blk, a.device) if pk2.h2 is not None else None
         ops.ln_bwd(gh, a, h, w, mod, mod_sn, mean, rstd, self.unbiased, (1, 1), g, gx, out_amax=gx_amax)
         if pg is not None and mod is not None:
             pg.modulation(blk, gx, g, lo, self.mod_total)          # (gx - g: the cotangent at LN's input a + mod)
         return gx, gx_amax
 
-    def _wgrad(self, pg: 'ParamGrads', cc: _ConvCache, sdesc: dict, g: Tensor, ho: int, wo: int, *, mod=None, mod_sn=0, ln=None,
-               act_in=0, up=(1, 1), ctx=None, cctx=0, ctx_sn=0):
-        """Weight / bias gradient of ``cc`` for the output cotangent ``g``: its forward descriptor rebuilt, the loader as the
-        forward ran it."""
-        d = make_conv_desc(**sdesc, w_ptr=0, cin_pad=0, cout_pad=0, cout=cc.cout, kh=cc.kh, kw=cc.kw, out_ptr=0, ho=ho, wo=wo,
-                           mt=1, stride_h=cc.sh, stride_w=cc.sw, circular=cc.circular, up_h=up[0], up_w=up[1],
-                           ctx_ptr=None if ctx is None else ctx.data_ptr(), cctx=cctx, ctx_sn=ctx_sn,
-                           mod_ptr=None if mod is None else mod.data_ptr(), mod_sn=mod_sn,
-                           ln_mean_ptr=None if ln is None else ln[0].data_ptr(), ln_rstd_ptr=None if ln is None else ln[1].data_ptr(),
-                           act_in=act_in)
-        pg.conv(cc, d, g)
+    def _wgrad(self, pg: 'ParamGrads', cc: _ConvCache, loader, g: Tensor, ho: int, wo: int):
+        """Weight / bias gradient of ``cc`` for the output cotangent ``g``; ``loader``: the (source fields, options) its forward
+        launch was built from (_head_loader / _conv1_loader / _conv2_loader / _tail_loader)."""
+        sdesc, opts = loader
+        pg.conv(cc, conv_desc(None, sdesc, None, ho, wo, cc=cc, circular=cc.circular, **opts), g)
+
+    def _tail_vjp(self, lev: _Level, g: Tensor, g_amax: Optional[Tensor], rec, fine, coarse):
+        """VJP of a deeper level's tail (LN -> Upsample -> conv) for the cotangent ``g`` at the ``fine`` resolution, ``g_amax`` its
+        max |.| as reported or None -> (gradient at the level's own ``coarse`` resolution, the device scalar holding its max |.| or None).
+
+        The transposed convolution at the fine resolution, summed over the up-sampling cells -- in ONE launch where a kernel can pool
+        in its epilogue (the f16 x 2 parity-plane form; the zero-position Winograd form: 7 of the 16 positions drop out of the 2 x 2 cell
+        sum), else the fine-resolution gradient goes through memory and ln_bwd pools while reading it."""
+        a, mean, rstd = rec
+        (hu, wu), (h, w) = fine, coarse
+        n, dev = g.shape[0], g.device
+        uh, uw = lev.head.sh, lev.head.sw
+        if (uh, uw) not in ((2, 2), (1, 2)):
+            raise NotImplementedError('VJP through Upsample is implemented for scale factor 2')
+        tl, pk = lev.tail, lev.tail.bwd()
+        gh, cells = None, (uh, uw)
+        if ops.POOLED and (uh, uw) == (2, 2) and hu == 2 * h and wu == 2 * w:
+            pooled = torch.empty(n, lev.C, h, w, device=dev, dtype=torch.float32)
+            if launch_conv(pk, planar_source(g), pooled, hu, wu, circular=tl.circular, pool=(2, 2), x_amax=input_scale(pk, g, g_amax)) is not None:
+                gh, cells = pooled, (1, 1)
+        if gh is None:
+            gh = torch.empty(n, lev.C, hu, wu, device=dev, dtype=torch.float32)
+            launch_conv(pk, planar_source(g), gh, hu, wu, circular=tl.circular)
+        gx = torch.empty(n, lev.C, h, w, device=dev, dtype=torch.float32)
+        gx_amax = _report_slot(lev, dev) if ops.MULTIPLY == 'f16x2' else None
+        ops.ln_bwd(gh, a, h, w, None, 0, mean, rstd, self.unbiased, cells, None, gx, out_amax=gx_amax)
+        return gx, gx_amax
+
+    def _head_vjp(self, hd: _ConvCache, g: Tensor, g_amax: Optional[Tensor], skip: Tensor, cout: int, fine):
+        """VJP of a deeper level's stride-2 head for the cotangent ``g`` (``g_amax``: its max |.| as reported, or None), plus the
+        skip gradient ``skip`` -> (gradient at the ``fine`` resolution, None: a convolution of the fp32 families reports no scale).
+        The first rung that serves the shape runs."""
+        hu, wu = fine
+        if hd.circular and ((hd.sh > 1 and hu % hd.sh) or (hd.sw > 1 and wu % hd.sw)):
+            raise NotImplementedError('VJP of a strided circular conv needs sizes divisible by the stride')
+        g2 = torch.empty(g.shape[0], cout, hu, wu, device=g.device, dtype=torch.float32)
+        gsrc = planar_source(g)
+        classes = hd.bwd_parity() if PARITY_SPLIT and hu % hd.sh == 0 and wu % hd.sw == 0 else None
+        if (ops.MULTIPLY == 'f16x2' and ops.H2_S2 and (hd.sh, hd.sw) == (2, 2) and g.is_contiguous() and skip.is_contiguous() and
+                skip.shape == g2.shape and g.shape[2] % 16 == 0 and g.shape[3] % 16 == 0 and hd.bwd().h2_zins() is not None):
+            # f16 x 2 route: the four output parity classes as 1 / 2 / 2 / 4-tap convolutions of g on conv_h2 (PackedConv.h2_zins).
+            # (h2_only: a descriptor the kernel refuses after all launches nothing here and takes the fp32 parity-class forms below)
+            if launch_conv(hd.bwd(), gsrc, g2, hu, wu, circular=hd.circular, zins=(hd.sh, hd.sw), res=skip,
+                           x_amax=input_scale(hd.bwd(), g, g_amax), h2_only=True) is not None:
+                return g2, None
+        if classes is not None and ops.PARITY4:
+            w4 = hd.bwd_parity4()
+            # (the one-launch kernel addresses the skip gradient with the OUTPUT strides: same layout required)
+            if w4 is not None and skip.is_contiguous() and skip.shape == g2.shape:
+                pk0, pad0 = classes[0][2], classes[0][3]
+                view = g2[:, :, 0::2, 0::2]
+                if launch_conv(pk0, gsrc, view, view.shape[2], view.shape[3], circular=hd.circular, pad=pad0,
+                               res=skip[:, :, 0::2, 0::2], parity4_w=w4) is not None:
+                    return g2, None
+        if classes is not None:                          # one small convolution per output parity class
+            for py, px, pk, pad in classes:
+                ys = slice(None) if py is None else slice(py, None, 2)
+                xs = slice(None) if px is None else slice(px, None, 2)
+                view = g2[:, :, ys, xs]
+                launch_conv(pk, gsrc, view, view.shape[2], view.shape[3], circular=hd.circular, pad=pad, res=skip[:, :, ys, xs])
+            return g2, None
+        launch_conv(hd.bwd(), gsrc, g2, hu, wu, circular=hd.circular, zins=(hd.sh, hd.sw), res=skip)      # zero insertion
+        return g2, None
 
     def backward_chunk(self, saved, g_out: Tensor, src: Source, lo: int, mod_all, per_image: bool, g_in: Optional[Tensor],
                        pg: Optional['ParamGrads'] = None):
@@ -830,106 +922,34 @@ class UNetEngine:
             return self._net1d_backward(saved, g_out, src, lo, mod_all, per_image, g_in)
         g_out = g_out.contiguous()
         L, D = self.levels, self.depth
-        dims = saved['dims']
+        dims, blocks = saved['dims'], saved['blocks']
         n = g_out.shape[0]
-        dev = g_out.device
         h, w = dims[0]
         tl = L[0].tail
-        g = torch.empty(n, L[0].C, h, w, device=dev, dtype=torch.float32)
+        g = torch.empty(n, L[0].C, h, w, device=g_out.device, dtype=torch.float32)
         if pg is not None:
-            self._wgrad(pg, tl, planar_source(saved['tail0_in']), g_out, h, w)
+            self._wgrad(pg, tl, _tail_loader(saved['tail0_in']), g_out, h, w)
         launch_conv(tl.bwd(), planar_source(g_out), g, h, w, circular=tl.circular)
         g_amax = None                                    # max |g| as reported by g's producer (ln_bwd launches), f16 x 2 route only
         g_skip = {}
-        for lvl in range(D):
-            lev = L[lvl]
+        for lvl, lev in enumerate(L):
             if lvl > 0:
                 # g: gradient of (tail_lvl(a) + skip_{lvl-1}) at level lvl-1 resolution
                 g_skip[lvl - 1] = g
-                hu, wu = dims[lvl - 1]
-                h, w = dims[lvl]
-                uh, uw = lev.head.sh, lev.head.sw
-                if (uh, uw) not in ((2, 2), (1, 2)):
-                    raise NotImplementedError('VJP through Upsample is implemented for scale factor 2')
-                tl = lev.tail
                 a, mean, rstd = saved['tails'][lvl]
                 if pg is not None:                       # the tail read LN(a) through the nearest up-sample
-                    self._wgrad(pg, tl, planar_source(a), g, hu, wu, ln=(mean, rstd), up=(uh, uw))
-                # the VJP of Upsample -> conv: the transposed convolution at the fine resolution, summed over the up-sampling
-                # cells -- in ONE launch where the kernel can pool in its epilogue (2 x 2: 7 of the 16 Winograd positions drop out
-                # of the cell sum), else the fine-resolution gradient goes through memory and ln_bwd pools while reading it
-                pooled = None
-                if ops.POOLED and (uh, uw) == (2, 2) and hu == 2 * h and wu == 2 * w:
-                    pooled = torch.empty(n, lev.C, h, w, device=dev, dtype=torch.float32)
-                    xa = None
-                    if ops.MULTIPLY == 'f16x2' and getattr(tl.bwd(), 'h2', None) is not None and g.is_contiguous():
-                        xa = g_amax if g_amax is not None else ops.absmax(g, tl.bwd().in_amax)     # (the f16 x 2 parity-plane form needs g's scale)
-                    if launch_conv(tl.bwd(), planar_source(g), pooled, hu, wu, circular=tl.circular, pool=(2, 2), x_amax=xa) is None:
-                        pooled = None
-                if pooled is None:
-                    ghup = torch.empty(n, lev.C, hu, wu, device=dev, dtype=torch.float32)
-                    launch_conv(tl.bwd(), planar_source(g), ghup, hu, wu, circular=tl.circular)
-                g = torch.empty(n, lev.C, h, w, device=dev, dtype=torch.float32)
-                g_amax = None
-                if ops.MULTIPLY == 'f16x2':
-                    g_amax = getattr(lev, '_g_amax', None)
-                    if g_amax is None or g_amax.device != dev:
-                        g_amax = lev._g_amax = torch.zeros(1, device=dev, dtype=torch.float32)
-                if pooled is not None:
-                    ops.ln_bwd(pooled, a, h, w, None, 0, mean, rstd, self.unbiased, (1, 1), None, g, out_amax=g_amax)
-                else:
-                    ops.ln_bwd(ghup, a, h, w, None, 0, mean, rstd, self.unbiased, (uh, uw), None, g, out_amax=g_amax)
+                    self._wgrad(pg, lev.tail, _tail_loader(a, (mean, rstd), (lev.head.sh, lev.head.sw)), g, *dims[lvl - 1])
+                g, g_amax = self._tail_vjp(lev, g, g_amax, saved['tails'][lvl], dims[lvl - 1], dims[lvl])
             for bi in reversed(range(len(lev.ascent))):
-                g, g_amax = self._block_bwd(lev.ascent[bi], g, saved['blocks'][('a', lvl, bi)], mod_all, lo, per_image, g_amax, pg)
+                g, g_amax = self._block_bwd(lev.ascent[bi], g, blocks[('a', lvl, bi)], mod_all, lo, per_image, g_amax, pg)
         for lvl in reversed(range(D)):
-            lev = L[lvl]
+            lev, hd = L[lvl], L[lvl].head
             for bi in reversed(range(len(lev.descent))):
-                g, g_amax = self._block_bwd(lev.descent[bi], g, saved['blocks'][('d', lvl, bi)], mod_all, lo, per_image, g_amax, pg)
-            hd = lev.head
+                g, g_amax = self._block_bwd(lev.descent[bi], g, blocks[('d', lvl, bi)], mod_all, lo, per_image, g_amax, pg)
             if pg is not None:                           # (g: the cotangent at this level's head output, dims[lvl])
-                if lvl > 0:
-                    self._wgrad(pg, hd, planar_source(saved['head_in'][lvl]), g, *dims[lvl])
-                else:
-                    sdesc, ctx = _source0(src, lo, n)
-                    self._wgrad(pg, hd, sdesc, g, *dims[lvl], ctx=ctx, cctx=src.cctx, ctx_sn=src.ctx_sn)
+                self._wgrad(pg, hd, _head_loader(hd, lvl, saved['head_in'].get(lvl), src, lo, n), g, *dims[lvl])
             if lvl > 0:
-                hu, wu = dims[lvl - 1]
-                if hd.circular and ((hd.sh > 1 and hu % hd.sh) or (hd.sw > 1 and wu % hd.sw)):
-                    raise NotImplementedError('VJP of a strided circular conv needs sizes divisible by the stride')
-                g2 = torch.empty(n, L[lvl - 1].C, hu, wu, device=dev, dtype=torch.float32)
-                skip = g_skip.pop(lvl - 1)
-                classes = hd.bwd_parity() if PARITY_SPLIT and hu % hd.sh == 0 and wu % hd.sw == 0 else None
-                done = False
-                if (ops.MULTIPLY == 'f16x2' and ops.H2_S2 and (hd.sh, hd.sw) == (2, 2) and g.is_contiguous() and skip.is_contiguous() and
-                        skip.shape == g2.shape and g.shape[2] % 16 == 0 and g.shape[3] % 16 == 0 and hd.bwd().h2_zins() is not None):
-                    # f16 x 2 route: the four output parity classes as 1 / 2 / 2 / 4-tap convolutions of g on conv_h2 (PackedConv.h2_zins).
-                    # (h2_only: a descriptor the kernel refuses after all launches nothing here and takes the fp32 parity-class forms below)
-                    xa = g_amax if g_amax is not None else ops.absmax(g, hd.bwd().in_amax)
-                    done = launch_conv(hd.bwd(), planar_source(g), g2, hu, wu, circular=hd.circular, zins=(hd.sh, hd.sw), res=skip,
-                                       x_amax=xa, h2_only=True) is not None
-                if not done and classes is not None and ops.PARITY4:
-                    w4 = hd.bwd_parity4()
-                    # (the one-launch kernel addresses the skip gradient with the OUTPUT strides: same layout required)
-                    if w4 is not None and skip.is_contiguous() and skip.shape == g2.shape:
-                        pk0, pad0 = classes[0][2], classes[0][3]
-                        view = g2[:, :, 0::2, 0::2]
-                        done = launch_conv(pk0, planar_source(g), view, view.shape[2], view.shape[3], circular=hd.circular, pad=pad0,
-                                           res=skip[:, :, 0::2, 0::2], parity4_w=w4) is not None
-                if done:
-                    pass
-                elif classes is not None:
-                    gsrc = planar_source(g)
-                    for py, px, pk, pad in classes:
-                        ys = slice(None) if py is None else slice(py, None, 2)
-                        xs = slice(None) if px is None else slice(px, None, 2)
-                        view = g2[:, :, ys, xs]
-                        launch_conv(pk, gsrc, view, view.shape[2], view.shape[3], circular=hd.circular, pad=pad,
-                                    res=skip[:, :, ys, xs])
-                else:
-                    launch_conv(hd.bwd(), planar_source(g), g2, hu, wu, circular=hd.circular, zins=(hd.sh, hd.sw),
-                                res=skip)
-                g = g2
-                g_amax = None                            # (produced by a convolution of the fp32 families: no report)
+                g, g_amax = self._head_vjp(hd, g, g_amax, g_skip.pop(lvl - 1), L[lvl - 1].C, dims[lvl - 1])
             elif g_in is not None:
                 launch_conv(hd.bwd(cin_keep=src.cx), planar_source(g), g_in, src.hs, src.ws, circular=hd.circular,
                             zins=(hd.sh, hd.sw))

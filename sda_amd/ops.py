@@ -164,12 +164,36 @@ class ConvProfile:
         rd += out * ((1 if d.res else 0) + (1 if d.dact_z else 0))
         return rd, out
 
-    def bracket_mem(self, kernel: str, nbytes: float, launch):
+    def conv_record(self, d: ConvDesc, family: str):
+        """(family, flops, (bytes read, written)) of a served convolution launch."""
+        # (a zero-insertion launch multiplies a quarter of what its fine-resolution output size says: 9 taps per SOURCE pixel)
+        return family, self.flops(d) / float(max(1, d.zins_h) * max(1, d.zins_w)), self.alg_bytes(d)
+
+    def bracket(self, family, flops: Optional[float], launch, nbytes=None):
+        """The one place a launch is timed: ``launch()`` between two HIP events on the launch stream, then its record.  A launch
+        that returns False was not served and ran nothing: no record.  ``flops`` None: an HBM-bound kernel with ``nbytes``
+        algorithmic bytes (mem_records); else a compute family, ``nbytes`` = (read, written) adding to family_bytes.  ``family`` may
+        be a callable -> (family, flops, nbytes), read once the launch is issued (a convolution's family is a planning call)."""
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
-        launch()
+        served = launch()
+        if served is False:
+            return False
         e1.record()
-        self.mem_records.append((e0, e1, nbytes, kernel))
+        if callable(family):
+            family, flops, nbytes = family()
+        if flops is None:
+            self.mem_records.append((e0, e1, nbytes, family))
+            return served
+        self.records.append((e0, e1, flops, family))
+        if nbytes is not None:
+            b = self.family_bytes.setdefault(family, [0.0, 0.0])
+            b[0] += nbytes[0]
+            b[1] += nbytes[1]
+        return served
+
+    def bracket_mem(self, kernel: str, nbytes: float, launch):
+        self.bracket(kernel, None, launch, nbytes)
 
     def mem_summary(self):
         torch.cuda.synchronize()
@@ -198,23 +222,17 @@ class ConvProfile:
 conv_profile: Optional[ConvProfile] = None
 
 
+def _bracketed(launch, record):
+    """``launch()`` -- through the installed profile's bracket if there is one (bench.py's roofline leg); ``record()`` ->
+    (family, flops, nbytes) as ConvProfile.bracket takes them is evaluated only then."""
+    prof = conv_profile
+    return launch() if prof is None else prof.bracket(record, None, launch)
+
+
 def conv_igemm(desc: ConvDesc):
     lib = _lib.load()
-    prof = conv_profile
-    if prof is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        _lib.check(lib.sda_conv_igemm(ctypes.byref(desc), _stream()), 'sda_conv_igemm')
-        e1.record()
-        fam = CONV_FAMILIES[max(0, conv_path(desc))]
-        # (a zero-insertion launch multiplies a quarter of what its fine-resolution output size says: 9 taps per SOURCE pixel)
-        prof.records.append((e0, e1, prof.flops(desc) / float(max(1, desc.zins_h) * max(1, desc.zins_w)), fam))
-        rd, wr = prof.alg_bytes(desc)
-        b = prof.family_bytes.setdefault(fam, [0.0, 0.0])
-        b[0] += rd
-        b[1] += wr
-        return
-    _lib.check(lib.sda_conv_igemm(ctypes.byref(desc), _stream()), 'sda_conv_igemm')
+    _bracketed(lambda: _lib.check(lib.sda_conv_igemm(ctypes.byref(desc), _stream()), 'sda_conv_igemm'),
+               lambda: conv_profile.conv_record(desc, CONV_FAMILIES[max(0, conv_path(desc))]))
 
 
 def absmax(x: Tensor, out: Tensor) -> Tensor:
@@ -230,7 +248,7 @@ def conv_h2(desc: ConvDesc, pk: 'PackedConv', x_amax, out_amax: Optional[Tensor]
     """Run the launch on the f16 x 2 kernel (csrc/conv_h2.hip) when `pk` carries that packing and the kernel serves the shape.
     x_amax: device scalar (Tensor) or a host bound (float) on the magnitude of what the loader feeds the multiply.  False: not
     served -- the caller runs the fp32 kernels."""
-    if getattr(pk, 'h2', None) is None or x_amax is None:
+    if pk.h2 is None or x_amax is None:
         return False
     lib = _lib.load()
     if packing is None:
@@ -245,23 +263,14 @@ def conv_h2(desc: ConvDesc, pk: 'PackedConv', x_amax, out_amax: Optional[Tensor]
     if not lib.sda_conv_h2_supported(ctypes.byref(desc)):
         desc.w_h2 = None
         return False
-    prof = conv_profile
-    if prof is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-    if out_amax is not None:
-        out_amax.zero_()
-    _lib.check(lib.sda_conv_h2(ctypes.byref(desc), _stream()), 'sda_conv_h2')
-    if prof is not None:
-        e1.record()
-        # (the up-sampled / pooled forms issue 4 of the 9 taps; the stride-2 forms all 9, at a quarter of the fine-resolution pixels)
-        fam = 'h2up' if (desc.up_h == 2 or desc.pool_h == 2) else 'h2s2' if (desc.zins_h == 2 or desc.stride_h == 2) else 'h2'
-        # (a zero-insertion launch multiplies a quarter of what its fine-resolution output size says: 9 taps per SOURCE pixel)
-        prof.records.append((e0, e1, prof.flops(desc) / float(max(1, desc.zins_h) * max(1, desc.zins_w)), fam))
-        rd, wr = prof.alg_bytes(desc)
-        b = prof.family_bytes.setdefault(fam, [0.0, 0.0])
-        b[0] += rd
-        b[1] += wr
+
+    def launch():                                         # (the report slot is cleared inside the timed region)
+        if out_amax is not None:
+            out_amax.zero_()
+        _lib.check(lib.sda_conv_h2(ctypes.byref(desc), _stream()), 'sda_conv_h2')
+    # (the up-sampled / pooled forms issue 4 of the 9 taps; the stride-2 forms all 9, at a quarter of the fine-resolution pixels)
+    _bracketed(launch, lambda: conv_profile.conv_record(
+        desc, 'h2up' if (desc.up_h == 2 or desc.pool_h == 2) else 'h2s2' if (desc.zins_h == 2 or desc.stride_h == 2) else 'h2'))
     return True
 
 
@@ -273,21 +282,19 @@ def conv_parity4(desc: ConvDesc) -> bool:
     """The four parity classes of a stride-2 3 x 3 convolution's backward-data in one launch (csrc/conv_par4.hip).  False: the
     shape is outside the kernel's range (the caller runs the four class launches)."""
     lib = _lib.load()
-    prof = conv_profile
-    if prof is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-    rc = lib.sda_conv_parity4(ctypes.byref(desc), _stream())
-    if rc == -2:                                         # SDA_E_UNSUPPORTED
-        return False
-    _lib.check(rc, 'sda_conv_parity4')
-    if prof is not None:
-        e1.record()
-        prof.records.append((e0, e1, 2.0 * desc.n * desc.ho * desc.wo * desc.cout * desc.cx * 9, 'par4'))
-        b = prof.family_bytes.setdefault('par4', [0.0, 0.0])
-        b[0] += 4.0 * desc.n * desc.cx * desc.hs * desc.ws + 4.0 * 9 * desc.cx * desc.cout + (16.0 * desc.n * desc.cout * desc.ho * desc.wo if desc.res else 0.0)
-        b[1] += 16.0 * desc.n * desc.cout * desc.ho * desc.wo
-    return True
+
+    def launch():
+        rc = lib.sda_conv_parity4(ctypes.byref(desc), _stream())
+        if rc == -2:                                     # SDA_E_UNSUPPORTED
+            return False
+        _lib.check(rc, 'sda_conv_parity4')
+        return True
+
+    def record():
+        out = 16.0 * desc.n * desc.cout * desc.ho * desc.wo      # (desc: the class-(0, 0) quarter of the output)
+        return ('par4', 2.0 * desc.n * desc.ho * desc.wo * desc.cout * desc.cx * 9,
+                (4.0 * desc.n * desc.cx * desc.hs * desc.ws + 4.0 * 9 * desc.cx * desc.cout + (out if desc.res else 0.0), out))
+    return _bracketed(launch, record)
 
 
 POOLED = os.environ.get('SDA_CONV_POOLED', '1') != '0'
@@ -365,15 +372,7 @@ def conv_wgrad(conv: ConvDesc, g: Tensor, dw: Tensor, db: Optional[Tensor], accu
     _lib.check(int(min(floats, 0)), name + '_work_floats')
     work = torch.empty(int(floats), device=g.device, dtype=torch.float32)
     d.work = work.data_ptr()
-    prof = conv_profile
-    if prof is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        _lib.check(launch(ctypes.byref(d), _stream()), name)
-        e1.record()
-        prof.records.append((e0, e1, wgrad_flops(conv), family))
-        return
-    _lib.check(launch(ctypes.byref(d), _stream()), name)
+    _bracketed(lambda: _lib.check(launch(ctypes.byref(d), _stream()), name), lambda: (family, wgrad_flops(conv), None))
 
 
 def plane_sum(x: Tensor, y: Optional[Tensor], out: Tensor, out_sn: int, sum_images: bool, accumulate: bool):
@@ -387,10 +386,7 @@ def plane_sum(x: Tensor, y: Optional[Tensor], out: Tensor, out_sn: int, sum_imag
     def launch():
         _lib.check(_lib.load().sda_plane_sum(x.data_ptr(), _ptr(y), n, c, hw, out.data_ptr(), out_sn, int(bool(sum_images)),
                                              int(bool(accumulate)), _stream()), 'sda_plane_sum')
-    if conv_profile is not None:
-        conv_profile.bracket_mem('plane_sum', 4.0 * n * c * hw * (2 if y is not None else 1), launch)
-    else:
-        launch()
+    _bracketed(launch, lambda: ('plane_sum', None, 4.0 * n * c * hw * (2 if y is not None else 1)))
 
 class PackedConv:
     """A conv layer's weights repacked for sda_conv_igemm (forward or backward-data form)."""
@@ -578,14 +574,7 @@ def block1d_eligible(c: int, h: int, pk1: 'PackedConv', pk2: 'PackedConv') -> bo
 
 def _bracket_block1d(family: str, d, launch):
     """bench.py's roofline leg: a fused 1-D residual block is two k = 3 convolutions c -> c over n x len positions."""
-    prof = conv_profile
-    if prof is None:
-        return launch()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    launch()
-    e1.record()
-    prof.records.append((e0, e1, 2 * (2.0 * d.n * d.len * d.c * d.c * 3), family))
+    _bracketed(launch, lambda: (family, 2 * (2.0 * d.n * d.len * d.c * d.c * 3), None))
 
 
 def _block1d_desc(a, mod, mod_sn, pk1, pk2, circular, act, eps, unbiased):
@@ -639,46 +628,24 @@ def net1d_launch(d: '_lib.Net1dDesc', backward: bool):
     (engine.net1d_plan mirrors the kernel's eligibility checks, so SDA_E_UNSUPPORTED here is a planning bug and raises.)"""
     lib = _lib.load()
     fn, name = (lib.sda_net1d_bwd, 'sda_net1d_bwd') if backward else (lib.sda_net1d_fwd, 'sda_net1d_fwd')
-    prof = conv_profile
-    if prof is None:
-        _lib.check(fn(ctypes.byref(d), _stream()), name)
-        return
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    _lib.check(fn(ctypes.byref(d), _stream()), name)
-    e1.record()
-    flops = 2.0 * d.n * d.len * 3 * (d.cin * d.c + 2 * d.nblocks * d.c * d.c + d.c * d.cout)
-    prof.records.append((e0, e1, flops, 'net1d_bwd' if backward else 'net1d_fwd'))
+    _net1d_bracket('net1d_bwd' if backward else 'net1d_fwd', d, lambda: _lib.check(fn(ctypes.byref(d), _stream()), name))
 
 
-def _net1d_bracket(tag: str, flops: float, launch):
-    prof = conv_profile
-    if prof is None:
-        launch()
-        return
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    launch()
-    e1.record()
-    prof.records.append((e0, e1, flops, tag))
-
-
-def _net1d_flops(d: '_lib.Net1dDesc') -> float:
-    return 2.0 * d.n * d.len * 3 * (d.cin * d.c + 2 * d.nblocks * d.c * d.c + d.c * d.cout)
+def _net1d_bracket(tag: str, d: '_lib.Net1dDesc', launch):
+    """The whole net's convolutions: head, two per block, tail, k = 3 each."""
+    _bracketed(launch, lambda: (tag, 2.0 * d.n * d.len * 3 * (d.cin * d.c + 2 * d.nblocks * d.c * d.c + d.c * d.cout), None))
 
 
 def net1d_fwd_train(t: '_lib.Net1dTrainDesc'):
     """sda_net1d_fwd with the saves of a training step (csrc/net1d_train.hip): also writes the tail convolution's input."""
     lib = _lib.load()
-    _net1d_bracket('net1d_fwd', _net1d_flops(t.net),
-                   lambda: _lib.check(lib.sda_net1d_fwd_train(ctypes.byref(t), _stream()), 'sda_net1d_fwd_train'))
+    _net1d_bracket('net1d_fwd', t.net, lambda: _lib.check(lib.sda_net1d_fwd_train(ctypes.byref(t), _stream()), 'sda_net1d_fwd_train'))
 
 
 def net1d_bwd_train(t: '_lib.Net1dTrainDesc'):
     """sda_net1d_bwd that also stores every convolution's output cotangent and the per-tile modulation-gradient sums."""
     lib = _lib.load()
-    _net1d_bracket('net1d_bwd', _net1d_flops(t.net),
-                   lambda: _lib.check(lib.sda_net1d_bwd_train(ctypes.byref(t), _stream()), 'sda_net1d_bwd_train'))
+    _net1d_bracket('net1d_bwd', t.net, lambda: _lib.check(lib.sda_net1d_bwd_train(ctypes.byref(t), _stream()), 'sda_net1d_bwd_train'))
 
 
 def net1d_tiles(d: '_lib.Net1dDesc') -> int:
@@ -699,9 +666,7 @@ def net1d_wgrad(d: '_lib.Net1dWgradDesc', device) -> Tensor:
         _lib.check(floats, 'sda_net1d_wgrad_work_floats')
     work = torch.empty(floats, device=device, dtype=torch.float32)
     d.work = work.data_ptr()
-    t = d.net
-    flops = 2.0 * t.n * t.len * 3 * (t.cin * t.c + 2 * t.nblocks * t.c * t.c + t.c * t.cout)
-    _net1d_bracket('net1d_wgrad', flops, lambda: _lib.check(lib.sda_net1d_wgrad(ctypes.byref(d), _stream()), 'sda_net1d_wgrad'))
+    _net1d_bracket('net1d_wgrad', d.net, lambda: _lib.check(lib.sda_net1d_wgrad(ctypes.byref(d), _stream()), 'sda_net1d_wgrad'))
     return work
 
 
@@ -714,16 +679,7 @@ def net1d_launch_fused(d: '_lib.Net1dDesc', f: '_lib.Net1dFuse', backward: bool)
     """One half of a fused guided evaluation (sda_net1d_fwd_fused / sda_net1d_bwd_fused; sda_amd/fused1d.py)."""
     lib = _lib.load()
     fn, name = (lib.sda_net1d_bwd_fused, 'sda_net1d_bwd_fused') if backward else (lib.sda_net1d_fwd_fused, 'sda_net1d_fwd_fused')
-    prof = conv_profile
-    if prof is None:
-        _lib.check(fn(ctypes.byref(d), ctypes.byref(f), _stream()), name)
-        return
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    _lib.check(fn(ctypes.byref(d), ctypes.byref(f), _stream()), name)
-    e1.record()
-    flops = 2.0 * d.n * d.len * 3 * (d.cin * d.c + 2 * d.nblocks * d.c * d.c + d.c * d.cout)
-    prof.records.append((e0, e1, flops, 'net1d_bwd' if backward else 'net1d_fwd'))
+    _net1d_bracket('net1d_bwd' if backward else 'net1d_fwd', d, lambda: _lib.check(fn(ctypes.byref(d), ctypes.byref(f), _stream()), name))
 
 
 # ------------------------------------------------------------------------------------------ LayerNorm pieces
@@ -737,10 +693,7 @@ def ln_stats(x: Tensor, mod: Optional[Tensor], mod_sn: int, eps: float, unbiased
     def launch():
         _lib.check(_lib.load().sda_ln_stats(x.data_ptr(), n, c, hw, _ptr(mod), mod_sn, eps, int(unbiased),
                                             mean.data_ptr(), rstd.data_ptr(), _stream()), 'sda_ln_stats')
-    if conv_profile is not None:
-        conv_profile.bracket_mem('ln_stats', 4.0 * n * hw * (c + 2), launch)       # read x once, write mean + rstd
-    else:
-        launch()
+    _bracketed(launch, lambda: ('ln_stats', None, 4.0 * n * hw * (c + 2)))         # read x once, write mean + rstd
 
 
 def ln_apply(x: Tensor, mod: Optional[Tensor], mod_sn: int, mean: Tensor, rstd: Tensor, y: Tensor):
@@ -767,12 +720,8 @@ def ln_bwd(gh: Tensor, x: Tensor, h: int, w: int, mod: Optional[Tensor], mod_sn:
             _lib.check(_lib.load().sda_ln_bwd_amax(gh.data_ptr(), x.data_ptr(), n, c, h, w, _ptr(mod), mod_sn, mean.data_ptr(),
                                                    rstd.data_ptr(), int(unbiased), pool[0], pool[1], _ptr(res), gx.data_ptr(),
                                                    out_amax.data_ptr(), _stream()), 'sda_ln_bwd_amax')
-    if conv_profile is not None:
-        # read gh (at the pooled resolution), x, res; write gx; + the statistics
-        nb = 4.0 * n * h * w * (c * (pool[0] * pool[1] + 2 + (1 if res is not None else 0)) + 2)
-        conv_profile.bracket_mem('ln_bwd', nb, launch)
-    else:
-        launch()
+    # read gh (at the pooled resolution), x, res; write gx; + the statistics
+    _bracketed(launch, lambda: ('ln_bwd', None, 4.0 * n * h * w * (c * (pool[0] * pool[1] + 2 + (1 if res is not None else 0)) + 2)))
 
 
 # ------------------------------------------------------------------------------------------ time embedding
@@ -832,47 +781,25 @@ def mlp_launch(d: '_lib.MlpDesc', backward: bool):
     """A whole ResMLP in one launch (csrc/mlp1d.hip), forward or input VJP; see include/sda_hip.h."""
     lib = _lib.load()
     fn, name = (lib.sda_mlp_bwd, 'sda_mlp_bwd') if backward else (lib.sda_mlp_fwd, 'sda_mlp_fwd')
-    prof = conv_profile
-    if prof is None:
-        _lib.check(fn(ctypes.byref(d), _stream()), name)
-        return
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    _lib.check(fn(ctypes.byref(d), _stream()), name)
-    e1.record()
-    flops = 2.0 * d.rows * sum(d.in_f[g] * d.out_f[g] for g in range(d.ngemm))
-    prof.records.append((e0, e1, flops, 'mlp_bwd' if backward else 'mlp_fwd'))
+    _mlp_bracket('mlp_bwd' if backward else 'mlp_fwd', d, lambda: _lib.check(fn(ctypes.byref(d), _stream()), name))
+
+
+def _mlp_bracket(tag: str, d: '_lib.MlpDesc', launch):
+    """Every GEMM of the ResMLP once over all rows."""
+    _bracketed(launch, lambda: (tag, 2.0 * d.rows * sum(d.in_f[g] * d.out_f[g] for g in range(d.ngemm)), None))
 
 
 def mlp_launch_win(d: '_lib.MlpDesc', w: '_lib.MlpWin', backward: bool):
     """One half of a fused guided evaluation of a local score network (sda_mlp_fwd_win / sda_mlp_bwd_win; sda_amd/fused1d.py)."""
     lib = _lib.load()
     fn, name = (lib.sda_mlp_bwd_win, 'sda_mlp_bwd_win') if backward else (lib.sda_mlp_fwd_win, 'sda_mlp_fwd_win')
-    prof = conv_profile
-    if prof is None:
-        _lib.check(fn(ctypes.byref(d), ctypes.byref(w), _stream()), name)
-        return
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    _lib.check(fn(ctypes.byref(d), ctypes.byref(w), _stream()), name)
-    e1.record()
-    flops = 2.0 * d.rows * sum(d.in_f[g] * d.out_f[g] for g in range(d.ngemm))
-    prof.records.append((e0, e1, flops, 'mlp_bwd' if backward else 'mlp_fwd'))
+    _mlp_bracket('mlp_bwd' if backward else 'mlp_fwd', d, lambda: _lib.check(fn(ctypes.byref(d), ctypes.byref(w), _stream()), name))
 
 
 def mlp_bwd_train(d: '_lib.MlpTrainDesc'):
     """The input VJP of a whole ResMLP that also stores the cotangent at every GEMM's output (sda_mlp_bwd_train, csrc/mlp_train.hip)."""
     lib = _lib.load()
-    prof = conv_profile
-    if prof is None:
-        _lib.check(lib.sda_mlp_bwd_train(ctypes.byref(d), _stream()), 'sda_mlp_bwd_train')
-        return
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    _lib.check(lib.sda_mlp_bwd_train(ctypes.byref(d), _stream()), 'sda_mlp_bwd_train')
-    e1.record()
-    m = d.mlp
-    prof.records.append((e0, e1, 2.0 * m.rows * sum(m.in_f[g] * m.out_f[g] for g in range(m.ngemm)), 'mlp_bwd'))
+    _mlp_bracket('mlp_bwd', d.mlp, lambda: _lib.check(lib.sda_mlp_bwd_train(ctypes.byref(d), _stream()), 'sda_mlp_bwd_train'))
 
 
 def adamw_step(d: '_lib.AdamWDesc') -> None:
@@ -978,15 +905,8 @@ def mlp_wgrad(d: '_lib.MlpWgradDesc') -> None:
     """dw[g] / db[g] (+)= the weight and bias gradients of every GEMM of a ResMLP: one launch + one slab reduction (sda_mlp_wgrad,
     csrc/mlp_train.hip).  ``d.work`` holds mlp_wgrad_work_floats(d) floats."""
     lib = _lib.load()
-    prof = conv_profile
-    if prof is None:
-        _lib.check(lib.sda_mlp_wgrad(ctypes.byref(d), _stream()), 'sda_mlp_wgrad')
-        return
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    _lib.check(lib.sda_mlp_wgrad(ctypes.byref(d), _stream()), 'sda_mlp_wgrad')
-    e1.record()
-    prof.records.append((e0, e1, 2.0 * d.rows * sum((d.in_f[g] + 1) * d.out_f[g] for g in range(d.ngemm)), 'wgrad'))
+    _bracketed(lambda: _lib.check(lib.sda_mlp_wgrad(ctypes.byref(d), _stream()), 'sda_mlp_wgrad'),
+               lambda: ('wgrad', 2.0 * d.rows * sum((d.in_f[g] + 1) * d.out_f[g] for g in range(d.ngemm)), None))
 
 
 def mc_finish(eps: Tensor, ghat: Tensor, gwin: Tensor, b: int, nw: int, k: int, c: int, cx0: float, cx1: float, coef_ptr: int, mode: int,
