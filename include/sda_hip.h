@@ -780,6 +780,26 @@ int sda_assignment_cost(const float* cost, int n, double* total, int* col_of_row
  *       unequal sample counts): *total = min_P <P, cost>, an integral min-cost flow after scaling by m n.  cost: m x n row-major,
  *       finite and >= 0. */
 int sda_transport_cost(const float* cost, int m, int n, double* total);
+/*   sda_assignment_auction : DEVICE pointers.  The assignment problem of sda_assignment_cost -- the arithmetic of ot.emd2 in
+ *       sda/utils.py:203-219 for uniform weights and equally many samples -- solved where the cost matrix already is: a forward
+ *       auction with epsilon-scaling, one workgroup per problem, `batch` problems per launch (cost: [batch][n][n] fp32 row-major,
+ *       4-byte aligned; 16-byte loads when n % 4 == 0 and the matrix is 16-byte aligned).  Phases run eps = R / 4, / 4, ... down
+ *       to eps_final = eps_rel R, R = max cost - min cost; prices and bids are float64.  Per problem b:
+ *         col_of_row[b][n]  the permutation (-1 for a row left unassigned when not converged)
+ *         total[b]          sum_i cost[i][col_of_row[i]]                                    (float64, fixed summation order)
+ *         gap[b]            total - (sum_i min_j (cost_ij + p_j) - sum_j p_j) >= total - optimum: a certificate that holds for any
+ *                           prices p; the auction guarantees gap <= n eps_final
+ *         eps_final[b], bids[b] (row scans done; <= bid_budget)
+ *         status[b]         SDA_AUCTION_CONVERGED, SDA_AUCTION_NOT_CONVERGED (bid_budget would have been exceeded: total and gap are
+ *                           NaN) or SDA_E_BADARG (a NaN / inf cost, as sda_assignment_cost answers; nothing else is meaningful)
+ *       Results do not depend on scheduling: ties go to the lowest column (rows) and the lowest row (columns).
+ *       Returns SDA_E_UNSUPPORTED for n > SDA_AUCTION_MAX_N (the state lives in LDS; nothing is launched), SDA_E_BADARG for null
+ *       pointers, n, batch or bid_budget < 1, eps_rel outside [1e-12, 1]. */
+#define SDA_AUCTION_MAX_N 4096
+#define SDA_AUCTION_CONVERGED 0
+#define SDA_AUCTION_NOT_CONVERGED 1
+int sda_assignment_auction(const float* cost, int n, int batch, double eps_rel, int64_t bid_budget, double* total, double* gap,
+                           double* eps_final, int64_t* bids, int32_t* status, int32_t* col_of_row, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * 3-D convolutions: `UNet(spatial=3)` (sda/nn.py:114-118 picks nn.Conv3d; heads / residual blocks / tails as nn.py:148-206).

@@ -25,7 +25,7 @@ def __getattr__(name):
     raise AttributeError(f'module {__name__!r} has no attribute {name!r}')
 
 
-def install_as_sda(native_chains: bool = False) -> None:
+def install_as_sda(native_chains: bool = False, native_emd: bool = False) -> None:
     """Make ``import sda`` / ``from sda.{mcs,nn,score,utils} import *`` resolve to this package, so that the reference's driver
     files (experiments/lorenz/utils.py:8-10, experiments/kolmogorov/utils.py:11-13, lorenz/eval.py:9-11) run unchanged:
 
@@ -36,7 +36,10 @@ def install_as_sda(native_chains: bool = False) -> None:
     the import system load second copies of the submodules (distinct classes) on ``import sda.<name>``.
 
     ``native_chains=True`` also rebinds the chain classes of ``sda.mcs`` (placeholders by default, or the user's own sda/mcs.py)
-    to the device implementations of ``sda_amd.chains``, so that ``make_chain()`` / ``posterior()`` of a driver run here."""
+    to the device implementations of ``sda_amd.chains``, so that ``make_chain()`` / ``posterior()`` of a driver run here.
+
+    ``native_emd=True`` sets ``metrics.EMD_SOLVER = 'device'``: ``sda.utils.emd`` of an unmodified eval.py then solves its
+    equal-count transport problems with the on-device auction (certified to 1e-7 of the cost range) instead of the host solver."""
     me = sys.modules[__name__]
     sys.modules['sda'] = me
     # every public submodule is imported BEFORE aliasing: a later `import sda.parallel` must find the one copy, not load a second
@@ -48,3 +51,5 @@ def install_as_sda(native_chains: bool = False) -> None:
             sys.modules['sda.' + full[len(__name__) + 1:]] = mod
     if native_chains:
         sys.modules[__name__ + '.chains'].install()
+    if native_emd:
+        sys.modules[__name__ + '.metrics'].EMD_SOLVER = 'device'

@@ -383,6 +383,7 @@ SIGNATURES = {
     'sda_mmd_kernel_sums': (c_int, [c_fp, c_int64, c_void_p, c_int, c_void_p]),
     'sda_assignment_cost': (c_int, [c_void_p, c_int, c_void_p, c_void_p]),
     'sda_transport_cost': (c_int, [c_void_p, c_int, c_int, c_void_p]),
+    'sda_assignment_auction': (c_int, [c_fp, c_int, c_int, ctypes.c_double, c_int64, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_void_p]),
     'sda_conv3d': (c_int, [POINTER(Conv3dDesc), c_void_p]),
     'sda_conv3d_packed_floats': (c_int64, [c_int, c_int, c_int, c_int, c_int, c_int]),
     'sda_pack_conv3d_weight': (c_int, [c_fp, c_int, c_int, c_int, c_int, c_int, c_int, c_fp, c_void_p]),

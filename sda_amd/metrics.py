@@ -6,14 +6,15 @@ r"""Evaluation metrics of the sampling experiments: the reference's ``sda.utils.
   reference does not vendor).  With empty weight vectors POT uses uniform weights, and for equally many samples on both
   sides -- how experiments/lorenz/eval.py:61-63,89 call it (1024 vs 1024) -- an optimal plan is a permutation, so the LP
   is a linear assignment problem (``sda_assignment_cost``, exact, O(n^3)).  Unequal sample counts go through an integral
-  min-cost flow on the host (``sda_transport_cost``), exact as well.
+  min-cost flow on the host (``sda_transport_cost``), exact as well.  Opt-in (``solver='device'``): the equal-count problem is
+  solved on the device by an epsilon-scaling auction with a duality-gap certificate (``sda_assignment_auction``).
 * ``mmd`` -- squared distances from the same kernel (differences are squared directly instead of expanding
   |x|^2 + |y|^2 - 2 x.y, which removes the reference's fp32 cancellation noise on the small bandwidths), then one fused
   pass per Gram block accumulates the seven Gaussian kernels in float64.
 * ``bpf`` -- bootstrap particle filter around user callables (``transition``, ``likelihood``); the trajectory buffer is
   allocated once and ancestors are resampled by index instead of re-concatenating the history at every step.
 """
-from typing import Callable
+from typing import Callable, Optional
 
 import torch
 from torch import Tensor
@@ -22,18 +23,55 @@ from . import ops
 from ._lib import SdaHipError
 
 
-def emd(x: Tensor, y: Tensor) -> Tensor:
+#: how ``emd`` solves the equal-count transport problem when called without ``solver``: 'host' (the exact O(n^3) host solver,
+#: the default) or 'device' (OPT-IN: the certified auction of csrc/assign.hip; ``sda_amd.install_as_sda(native_emd=True)`` sets it)
+EMD_SOLVER = 'host'
+#: relative accuracy of the device route: total - optimum <= n eps_rel (max cost - min cost), i.e. emd is off by at most
+#: eps_rel x the cost range -- below the fp32 resolution of the returned tensor
+EMD_EPS_REL = 1e-7
+#: bid budget of the device route (None: ops.auction_default_budget(n))
+EMD_BID_BUDGET = None
+#: route of the last ``emd`` call: 'host', 'device', or 'host_fallback' (device asked for, but n is not served or the bid budget
+#: ran out: the host solver ran on the same cost matrix)
+LAST_EMD_ROUTE = None
+
+
+def emd(x: Tensor, y: Tensor, solver: Optional[str] = None) -> Tensor:
     r"""Earth mover's distance between two equally weighted sample sets ``x`` (M, \*) and ``y`` (N, \*)
     (sda/utils.py:203-219: ``ot.emd2`` with empty weight vectors = uniform marginals).  The cost matrix is formed on the
     device; the transport LP is solved on the host (as POT does): a linear assignment for M == N, an integral min-cost flow
     otherwise.
+
+    ``solver='device'`` (or ``EMD_SOLVER = 'device'``; M == N only) keeps the solve on the device: an epsilon-scaling auction
+    (``ops.assignment_auction``) whose result comes with a duality-gap certificate, value - exact <= EMD_EPS_REL x the cost range;
+    one small record is read back.  When the auction does not serve n or runs out of its bid budget the host solver runs on the
+    same cost matrix (``LAST_EMD_ROUTE == 'host_fallback'``).
 
     Size note: the M == N solve is O(N^3) shortest augmenting paths (1024 vs 1024 trajectories: ~0.1 s).  The M != N solve is
     successive shortest paths with DENSE Dijkstra over the complete bipartite graph -- O((M + N)^2) per augmentation, at
     least M + N augmentations, and an M x N int64 flow matrix: fine for the sample counts of the reference's evaluation
     (hundreds to a couple of thousand), minutes beyond ~2000 x 1000 on one host thread (POT's network simplex takes
     seconds there).  Past that size prefer equal sample counts."""
+    global LAST_EMD_ROUTE
+    solver = EMD_SOLVER if solver is None else solver
+    if solver not in ('host', 'device'):
+        raise ValueError(f"emd solver {solver!r} (expected 'host' or 'device')")
     xf, yf = x.flatten(1).float(), y.flatten(1).float()
+    n = xf.shape[0]
+    if solver == 'device' and n == yf.shape[0]:
+        cost = ops.pairwise_dist(xf, yf, squared=False)
+        if n <= ops.AUCTION_MAX_N:
+            res = ops.assignment_auction(cost, eps_rel=EMD_EPS_REL, bid_budget=EMD_BID_BUDGET)
+            total, _, _, _, status = ops.auction_record(res.record.cpu(), 1)
+            if int(status) == ops.AUCTION_CONVERGED:
+                LAST_EMD_ROUTE = 'device'
+                return x.new_tensor(float(total) / n)
+            if int(status) != ops.AUCTION_NOT_CONVERGED:
+                raise SdaHipError('sda_assignment_auction: bad argument (NaN / inf costs)')
+        LAST_EMD_ROUTE = 'host_fallback'
+        total, _ = ops.assignment_cost(cost.cpu())
+        return x.new_tensor(total / n)
+    LAST_EMD_ROUTE = 'host'
     cost = ops.pairwise_dist(xf, yf, squared=False).cpu()
     if xf.shape[0] == yf.shape[0]:
         total, _ = ops.assignment_cost(cost)

@@ -3,6 +3,7 @@
 Every function launches a hand-written gfx950 kernel on the CURRENT torch stream.  There is no CPU path:
 tensors must live on a HIP device (`_dev()` raises otherwise).
 """
+import collections
 import contextlib
 import ctypes
 import gc
@@ -1117,6 +1118,59 @@ def assignment_cost(cost: Tensor):
     _lib.check(_lib.load().sda_assignment_cost(cost.data_ptr(), n, ctypes.addressof(total), cols.data_ptr()),
                'sda_assignment_cost')
     return total.value, cols
+
+
+#: largest n sda_assignment_auction serves (SDA_AUCTION_MAX_N: its state lives in LDS)
+AUCTION_MAX_N = 4096
+#: per-problem status words of sda_assignment_auction (include/sda_hip.h)
+AUCTION_CONVERGED, AUCTION_NOT_CONVERGED, AUCTION_BADARG = 0, 1, -1
+#: default bid budget = min(AUCTION_BIDS_PER_ROW * n, AUCTION_BID_CAP): 8 x the largest bids / n the host replay showed, capped
+#: where a launch that spends the whole budget would pass about a second at n = 4096
+AUCTION_BIDS_PER_ROW = 8 * 161
+AUCTION_BID_CAP = 160 * 4096
+
+
+def auction_default_budget(n: int) -> int:
+    return min(AUCTION_BIDS_PER_ROW * n, AUCTION_BID_CAP)
+
+AuctionResult = collections.namedtuple('AuctionResult', 'total gap eps_final bids status col_of_row record')
+
+
+def auction_record(record: Tensor, batch: int):
+    """Views of the five per-problem words in an AuctionResult.record (device or host copy): total, gap, eps_final (float64),
+    bids (int64), status (int32)."""
+    w = 8 * batch
+    return (record[0:w].view(torch.float64), record[w:2 * w].view(torch.float64), record[2 * w:3 * w].view(torch.float64),
+            record[3 * w:4 * w].view(torch.int64), record[4 * w:4 * w + 4 * batch].view(torch.int32))
+
+
+def assignment_auction(cost: Tensor, eps_rel: float = 1e-7, bid_budget=None) -> AuctionResult:
+    """Device linear-assignment solve (epsilon-scaling auction, ``sda_assignment_auction``) of an fp32 device tensor (n, n) or
+    (b, n, n), n <= AUCTION_MAX_N.  Returns device tensors: total, gap, eps_final (float64), bids (int64), status (int32) -- 0-dim
+    for an (n, n) input, (b,) otherwise -- and col_of_row (int32, (n,) or (b, n)); ``record`` is the one byte buffer the five
+    words live in (one copy brings them all to the host).  total - optimum <= gap <= n eps_final where status is
+    AUCTION_CONVERGED; AUCTION_NOT_CONVERGED: ``bid_budget`` (default ``auction_default_budget(n)``) ran out; AUCTION_BADARG: NaN /
+    inf costs.  Nothing synchronises."""
+    _dev(cost)
+    if cost.dtype != torch.float32 or cost.dim() not in (2, 3) or cost.shape[-1] != cost.shape[-2] or cost.shape[-1] < 1:
+        raise _lib.SdaHipError('assignment_auction expects a square fp32 device matrix (n, n) or a batch (b, n, n)')
+    single = cost.dim() == 2
+    cost = cost.contiguous()
+    n = cost.shape[-1]
+    batch = 1 if single else cost.shape[0]
+    if batch < 1:
+        raise _lib.SdaHipError('assignment_auction: empty batch')
+    if bid_budget is None:
+        bid_budget = auction_default_budget(n)
+    record = torch.empty(8 * 4 * batch + 8 * ((batch + 1) // 2), device=cost.device, dtype=torch.uint8)
+    total, gap, eps_final, bids, status = auction_record(record, batch)
+    cols = torch.empty(batch, n, device=cost.device, dtype=torch.int32)
+    _lib.check(_lib.load().sda_assignment_auction(cost.data_ptr(), n, batch, float(eps_rel), int(bid_budget), total.data_ptr(),
+                                                  gap.data_ptr(), eps_final.data_ptr(), bids.data_ptr(), status.data_ptr(),
+                                                  cols.data_ptr(), _stream()), 'sda_assignment_auction')
+    if single:
+        total, gap, eps_final, bids, status, cols = total[0], gap[0], eps_final[0], bids[0], status[0], cols[0]
+    return AuctionResult(total, gap, eps_final, bids, status, cols, record)
 
 
 def clock_probe(device, ms: float = 2.0, blocks: int = 1024) -> dict:
