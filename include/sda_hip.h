@@ -943,6 +943,38 @@ int sda_bpf_resample(const double* cdf, int m, uint64_t seed, int64_t obs_index,
 int sda_bpf_traceback(const float* S, int64_t s_st, int64_t s_sp, const int32_t* anc, int m, int n_obs, int step, int d, float* out,
                       void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Kolmogorov flow (csrc/kflow.hip; additive, ABI stays v14): the simulator behind sda/mcs.py:244-338.  The reference only CALLS
+ * jax-cfd, so the scheme (tests/kflow_ref.py) is this project's restatement of semi_implicit_navier_stokes
+ * with its defaults: faithful, not pinned to a reference output.
+ *
+ * State: fields [2][n][n] fp32 (u, v staggered; axis 0 of a plane is x), field stride in floats given per call, planes and rows
+ * contiguous.  n % 16 == 0, 16 <= n <= 512 (sda_kflow_serves), at most 65535 fields per call.
+ * sda_kflow_explicit: out[b] = (u*, v*) = x[b] + delta (-adv + nu lap + f), out contiguous [nb][2][n][n].
+ * sda_kflow_hartley: nb planes [n][n]; side 0: out = Hm x; side 1: out = (x Hm) o scale (scale [n][n] or NULL); out contiguous, out != x.
+ * sda_kflow_project: out[b] = x[b] - grad(lap^-1 div x[b]) (the mean mode of the potential is 0); work: 2 nb n n floats; out may be x.
+ * sda_kflow_advance: `transitions` transitions of model.steps sub-steps each, all queued, nothing read back.  every = 0: out[b] (field
+ *   stride 2 n n) = the last state; every = 1: out[t * out_st + b * 2 n n] = the state after transition t.  work:
+ *   sda_kflow_work_floats(n, nb) floats.  x is only read.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct {
+    int32_t n, steps;
+    float delta;            /* dt / steps, rounded to fp32 */
+    float nu;               /* 1 / reynolds */
+    const float* hm;        /* device [n][n]: (cos(2 pi a b / n) + sin(2 pi a b / n)) / sqrt(n) */
+    const float* inv;       /* device [n][n]: 1 / (lam_a + lam_b), lam_k = (2 cos(2 pi k / n) - 2) / h^2; 0 at [0][0] */
+    const float* forcing;   /* device [n]: sin(4 (j + 1/2) h) */
+} sda_kflow_model;
+int sda_kflow_serves(int n);
+int64_t sda_kflow_work_floats(int n, int nb);
+int sda_kflow_explicit(const sda_kflow_model* m, const float* x, int64_t x_sb, int nb, float* out, void* stream);
+int sda_kflow_hartley(const float* hm, int n, const float* x, int64_t x_sb, int nb, int side, const float* scale, float* out,
+                      void* stream);
+int sda_kflow_project(const sda_kflow_model* m, const float* x, int64_t x_sb, int nb, float* out, int64_t out_sb, float* work,
+                      void* stream);
+int sda_kflow_advance(const sda_kflow_model* m, const float* x, int64_t x_sb, int nb, int transitions, int every, float* out,
+                      int64_t out_st, float* work, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -277,6 +277,11 @@ class ChainAdv(Structure):
     ]
 
 
+class KflowModel(Structure):
+    """Mirror of `struct sda_kflow_model` (include/sda_hip.h)."""
+    _fields_ = [('n', c_int32), ('steps', c_int32), ('delta', c_float), ('nu', c_float), ('hm', c_fp), ('inv', c_fp), ('forcing', c_fp)]
+
+
 SIGNATURES = {
     'sda_abi_version': (c_int, []),
     'sda_conv_igemm': (c_int, [POINTER(ConvDesc), c_void_p]),
@@ -395,6 +400,12 @@ SIGNATURES = {
     'sda_bpf_resample': (c_int, [c_fp, c_int, c_uint64, c_int64, c_fp, c_void_p]),
     'sda_bpf_traceback': (c_int, [c_fp, c_int64, c_int64, c_fp, c_int, c_int, c_int, c_int, c_fp, c_void_p]),
     'sda_pool3d_sum': (c_int, [c_fp, c_int64, c_int, c_int, c_int, c_int, c_int, c_int, c_fp, c_void_p]),
+    'sda_kflow_serves': (c_int, [c_int]),
+    'sda_kflow_work_floats': (c_int64, [c_int, c_int]),
+    'sda_kflow_explicit': (c_int, [POINTER(KflowModel), c_fp, c_int64, c_int, c_fp, c_void_p]),
+    'sda_kflow_hartley': (c_int, [c_fp, c_int, c_fp, c_int64, c_int, c_int, c_fp, c_fp, c_void_p]),
+    'sda_kflow_project': (c_int, [POINTER(KflowModel), c_fp, c_int64, c_int, c_fp, c_int64, c_fp, c_void_p]),
+    'sda_kflow_advance': (c_int, [POINTER(KflowModel), c_fp, c_int64, c_int, c_int, c_int, c_fp, c_int64, c_fp, c_void_p]),
 }
 
 _lib = None

@@ -3,8 +3,9 @@ r"""Markov chains of the reference (sda/mcs.py:22-241) on the device, and the fu
 ``MarkovChain``, ``DiscreteODE``, ``Lorenz63``, ``NoisyLorenz63``, ``Lorenz96`` and ``LotkaVolterra`` keep the reference's
 constructor arguments and methods.  ``transition`` and ``trajectory`` of the three built-in systems are ONE launch of
 ``sda_chain_advance`` (csrc/chain.hip) whatever the length; a user subclass of ``DiscreteODE`` with its own ``f`` -- and any input
-that requires grad -- runs the reference's torch-ops ``rk4`` instead (correct, not fused).  ``DampedSpring`` and
-``KolmogorovFlow`` are not rebuilt.
+that requires grad -- runs the reference's torch-ops ``rk4`` instead (correct, not fused).  ``KolmogorovFlow`` is the
+incompressible-flow simulator the reference obtains from jax-cfd, here as five launches per sub-step (csrc/kflow.hip: one stencil
+kernel and four products with the Hartley matrix on the fp32 matrix cores); see the class.  ``DampedSpring`` is not rebuilt.
 
 Noise.  The noisy chain draws one 63-bit seed per call from torch's default CPU generator (``torch.manual_seed`` reproduces a
 run) unless ``seed=`` is given, and advances a draw counter by the number of transitions, so successive calls never reuse
@@ -14,6 +15,7 @@ noise.  The normal added to particle ``r`` at draw ``t`` is row ``r`` of ``ops.r
 rebinds the chain names inside that module to the classes of this one.
 """
 import abc
+import math
 from typing import Callable, Optional, Tuple
 
 import torch
@@ -23,7 +25,7 @@ from torch.distributions import MultivariateNormal, Normal
 from . import ops
 from ._lib import CHAIN_MAXOBS, SdaHipError
 
-__all__ = ['MarkovChain', 'DiscreteODE', 'Lorenz63', 'NoisyLorenz63', 'Lorenz96', 'LotkaVolterra', 'AffineObservation',
+__all__ = ['MarkovChain', 'DiscreteODE', 'Lorenz63', 'NoisyLorenz63', 'Lorenz96', 'LotkaVolterra', 'KolmogorovFlow', 'AffineObservation',
            'probe_affine', 'bpf_fused', 'install']
 
 
@@ -251,6 +253,183 @@ class LotkaVolterra(DiscreteODE):
 LotkaVolterra._KERNEL = ('lotka_volterra', LotkaVolterra.f)
 
 
+# ---------------------------------------------------------------- Kolmogorov flow
+def _kflow_flux(a: Tensor, cm: Tensor, c0: Tensor, cp: Tensor, cpp: Tensor, dh: float) -> Tensor:
+    """Van-Leer-limited Lax-Wendroff flux through the face between c0 and cp, advecting velocity a, dh = delta / h."""
+    C = a * dh
+    d = cp - c0
+    pos = a > 0
+    low = torch.where(pos, c0, cp)
+    high = torch.where(pos, c0 + 0.5 * (1 - C) * d, cp - 0.5 * (1 + C) * d)
+    num = torch.where(pos, c0 - cm, cpp - cp)
+    nz = d != 0
+    r = torch.where(nz, num / torch.where(nz, d, torch.ones_like(d)), torch.zeros_like(d))
+    ar = r.abs()
+    phi = (r + ar) / (1 + ar)
+    return (low + phi * (high - low)) * a
+
+
+def _shift(a: Tensor, di: int, dj: int) -> Tensor:
+    """a[i + di, j + dj] on the periodic grid."""
+    return torch.roll(a, (-di, -dj), (-2, -1))
+
+
+class KolmogorovFlow(MarkovChain):
+    r"""2-D incompressible flow with Kolmogorov forcing (sda/mcs.py:244-338) on the device.
+
+    The reference only calls jax-cfd, so the scheme here is this project's restatement of ``semi_implicit_navier_stokes`` with its
+    defaults (tests/kflow_ref.py): faithful, not pinned to a reference output, and the random stream of
+    ``prior`` is this package's Philox (``ops.randn_rows`` keyed on (seed, row)), not jax's.
+
+    State ``(..., 2, size, size)`` fp32: u, v on a staggered periodic grid, axis -2 is x.  A transition is ``steps`` sub-steps;
+    ``transition`` and ``trajectory`` queue every launch (five per sub-step, csrc/kflow.hip) and read nothing back, and
+    ``trajectory`` writes each kept frame straight into its slab.  The kernels serve ``size % 16 == 0, 16 <= size <= 512``; other
+    sizes and inputs that require grad take the same scheme in torch ops (``_torch_substep``: ``torch.roll`` and ``torch.fft``,
+    differentiable).  A CPU tensor at a served size raises, as the Lorenz chains do."""
+
+    def __init__(self, size: int = 256, dt: float = 0.01, reynolds: int = 1e3):
+        super().__init__()
+        self.size, self.dt, self.reynolds = int(size), dt, reynolds
+        h = 2 * math.pi / self.size
+        nu = 1 / reynolds
+        dt_min = min(0.5 * h / 5.0, h * h / (4 * nu))
+        self.steps = 1 if dt_min > dt else math.ceil(dt / dt_min)
+        # the fp32 values the kernels are handed; every route and precision uses the same two numbers
+        self.delta = torch.tensor(dt / self.steps, dtype=torch.float32).item()
+        self.nu = torch.tensor(nu, dtype=torch.float32).item()
+        self._kernel_size = self.size % 16 == 0 and 16 <= self.size <= 512
+        self._models, self._filters = {}, {}
+
+    # ---- routes
+    def _fused(self, x: Tensor) -> bool:
+        return self._kernel_size and not (torch.is_grad_enabled() and x.requires_grad)
+
+    def model(self, device):
+        key = ops.kflow_device_key(device)
+        m = self._models.get(key)
+        if m is None:
+            m = self._models[key] = ops.kflow_model(self.size, self.steps, self.delta, self.nu, torch.device(*key))
+        return m
+
+    def _check(self, x: Tensor) -> None:
+        if tuple(x.shape[-3:]) != (2, self.size, self.size):
+            raise SdaHipError(f'KolmogorovFlow: states of shape {tuple(x.shape)}, expected (..., 2, {self.size}, {self.size})')
+
+    # ---- the scheme in torch ops
+    def _torch_project(self, x: Tensor) -> Tensor:
+        n = self.size
+        h = 2 * math.pi / n
+        u, v = x[..., 0, :, :], x[..., 1, :, :]
+        div = ((u - _shift(u, -1, 0)) + (v - _shift(v, 0, -1))) / h
+        inv = ops.kflow_solve_tables(n, x.device, x.dtype)[0]
+        q = torch.fft.ifft2(torch.fft.fft2(div) * inv).real
+        return torch.stack((u - (_shift(q, 1, 0) - q) / h, v - (_shift(q, 0, 1) - q) / h), dim=-3)
+
+    def _torch_explicit(self, x: Tensor) -> Tensor:
+        n = self.size
+        h = 2 * math.pi / n
+        delta, nu, dh = self.delta, self.nu, self.delta / h
+        u, v = x[..., 0, :, :], x[..., 1, :, :]
+
+        def adv(c, ax, ay):
+            fx = _kflow_flux(ax, _shift(c, -1, 0), c, _shift(c, 1, 0), _shift(c, 2, 0), dh)
+            fy = _kflow_flux(ay, _shift(c, 0, -1), c, _shift(c, 0, 1), _shift(c, 0, 2), dh)
+            return ((fx - _shift(fx, -1, 0)) + (fy - _shift(fy, 0, -1))) / h
+
+        def lap(c):
+            return ((((_shift(c, 1, 0) + _shift(c, -1, 0)) + _shift(c, 0, 1)) + _shift(c, 0, -1)) - 4 * c) / (h * h)
+
+        forcing = ops.kflow_solve_tables(n, x.device, x.dtype)[1]
+        au = adv(u, 0.5 * (u + _shift(u, 1, 0)), 0.5 * (v + _shift(v, 1, 0)))
+        av = adv(v, 0.5 * (u + _shift(u, 0, 1)), 0.5 * (v + _shift(v, 0, 1)))
+        us = u + delta * ((nu * lap(u) - au) + (forcing - 0.1 * u))
+        vs = v + delta * ((nu * lap(v) - av) + (-0.1 * v))
+        return torch.stack((us, vs), dim=-3)
+
+    def _torch_substep(self, x: Tensor) -> Tensor:
+        """One sub-step in torch ops: the fallback of the kernels, differentiable, and the timing baseline."""
+        return self._torch_project(self._torch_explicit(x))
+
+    def _torch_transition(self, x: Tensor) -> Tensor:
+        for _ in range(self.steps):
+            x = self._torch_substep(x)
+        return x
+
+    # ---- MarkovChain
+    def _filter(self, device) -> Tensor:
+        """g(|k|) of jax-cfd's filtered_velocity_field (peak wavenumber 4): a log-normal in |k|, 0 at k = 0; (size, size)."""
+        key = ops.kflow_device_key(device)
+        device = torch.device(*key)
+        g = self._filters.get(key)
+        if g is None:
+            n = self.size
+            k = torch.arange(n, dtype=torch.float64)
+            k = torch.where(k > n // 2, k - n, k)
+            kk = (k[:, None] ** 2 + k[None, :] ** 2).sqrt()
+            kk[0, 0] = 1.0
+            lk = kk.log()
+            g = torch.exp(-(math.log(4.0) + 0.25 - lk) ** 2 / (2 * 0.25) - lk) / math.sqrt(2 * math.pi * 0.25)
+            g[0, 0] = 0.0
+            g = self._filters[key] = g.float().to(device)
+        return g
+
+    def prior(self, shape: Size = (), *, device=None, seed: Optional[int] = None) -> Tensor:
+        r"""Filtered unit normal noise, then three rounds of {project; scale the largest speed to 3}.  The noise of field ``r`` is
+        row ``r`` of ``ops.randn_rows(.., seed, 0)``; ``seed`` defaults to one draw from torch's CPU generator.  ``device`` defaults
+        to the current HIP device (the generator has no CPU form).  The filter and the projection run on the kernels at a served
+        size; the rescaling is three small torch reductions."""
+        shape = Size(shape)
+        device = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
+        seed = _draw_seed() if seed is None else int(seed)
+        n = self.size
+        if shape.numel() == 0:
+            return torch.empty(*shape, 2, n, n, device=device, dtype=torch.float32)
+        z = torch.empty(shape.numel(), 2, n, n, device=device, dtype=torch.float32)
+        ops.randn_rows(z, seed, 0)
+        g = self._filter(device)
+        if self._kernel_size:
+            x = ops.kflow_hartley(ops.kflow_hartley(z, g))
+        else:
+            x = torch.fft.ifft2(torch.fft.fft2(z) * g).real
+        for _ in range(3):
+            x = ops.kflow_project(self.model(device), x) if self._kernel_size else self._torch_project(x)
+            speed = (x[:, 0] ** 2 + x[:, 1] ** 2).amax(dim=(-2, -1)).sqrt()
+            # a field that is zero everywhere has no direction to scale: it stays zero
+            x = x * torch.where(speed > 0, 3.0 / speed, torch.zeros_like(speed))[:, None, None, None]
+        return x.reshape(*shape, 2, n, n)
+
+    def transition(self, x: Tensor) -> Tensor:
+        self._check(x)
+        if self._fused(x):
+            return ops.kflow_advance(self.model(x.device), x, 1) if x.is_cuda else ops._dev(x)
+        return self._torch_transition(x)
+
+    def trajectory(self, x: Tensor, length: int, last: bool = False) -> Tensor:
+        self._check(x)
+        if self._fused(x) and length >= 1:
+            return ops.kflow_advance(self.model(x.device), x, length, every=not last) if x.is_cuda else ops._dev(x)
+        return super().trajectory(x, length, last)
+
+    @staticmethod
+    def coarsen(x: Tensor, r: int = 2) -> Tensor:
+        return _mcs()._coarsen(x, r)
+
+    @staticmethod
+    def upsample(x: Tensor, r: int = 2, mode: str = 'bilinear') -> Tensor:
+        return _mcs()._upsample(x, r, mode)
+
+    @staticmethod
+    def vorticity(x: Tensor) -> Tensor:
+        return _mcs()._vorticity(x)
+
+
+def _mcs():
+    """``sda_amd.mcs``, loaded on first use (it probes for a user's own sda/mcs.py): its torch-only static helpers are the ones
+    ``KolmogorovFlow`` hands out."""
+    import importlib
+    return importlib.import_module(__package__ + '.mcs')
+
+
 # ---------------------------------------------------------------- observation operators the fused filter understands
 class AffineObservation:
     r"""A(x) = (x[..., index] - shift) / scale: each output is an affine function of ONE state component."""
@@ -347,6 +526,6 @@ def install() -> None:
     call it before a driver's ``from sda.mcs import *``."""
     import importlib
     mcs = importlib.import_module(__package__ + '.mcs')
-    for name in ('MarkovChain', 'DiscreteODE', 'Lorenz63', 'NoisyLorenz63', 'Lorenz96', 'LotkaVolterra'):
+    for name in ('MarkovChain', 'DiscreteODE', 'Lorenz63', 'NoisyLorenz63', 'Lorenz96', 'LotkaVolterra', 'KolmogorovFlow'):
         setattr(mcs, name, globals()[name])
     mcs.SOURCE = __name__

@@ -1,4 +1,4 @@
-r"""Kolmogorov score-network factories (experiments/kolmogorov/utils.py:29-81 of the reference)."""
+r"""Kolmogorov chain and score-network factories (experiments/kolmogorov/utils.py:25-81 of the reference)."""
 
 from pathlib import Path
 from typing import Sequence
@@ -7,8 +7,14 @@ import torch
 import torch.nn as nn
 from torch import Tensor
 
+from ..chains import KolmogorovFlow, MarkovChain
 from ..score import MCScoreNet, ScoreUNet
 from ..utils import ACTIVATIONS, load_config
+
+
+def make_chain() -> MarkovChain:
+    r"""The flow the reference's data comes from (kolmogorov/utils.py:25-26): 256 x 256, dt = 0.2 (82 sub-steps)."""
+    return KolmogorovFlow(size=256, dt=0.2)
 
 
 class LocalScoreUNet(ScoreUNet):

@@ -2,7 +2,9 @@ r"""``sda.mcs`` for drivers that run on this package -- a passthrough, not an im
 
 The reference's experiment helpers start with ``from sda.mcs import *`` (experiments/lorenz/utils.py:8,
 experiments/kolmogorov/utils.py:11).  The simulators of ``sda/mcs.py`` are data generation, outside the sampling hot path
-(SURVEY.md section 2), so nothing of them is rebuilt here.  This module
+(SURVEY.md section 2); the device implementations (the Lorenz chains, Lotka-Volterra and ``KolmogorovFlow``) live in
+``sda_amd.chains`` and are bound into this module only on request (``sda_amd.install_as_sda(native_chains=True)``).  By default
+this module
 
 * re-exports the user's own ``sda/mcs.py`` when one is installed next to this package (first ``sda`` package on ``sys.path``
   that is not this one, or the file named by ``$SDA_MCS_FILE``) and its imports (jax, optionally jax_cfd) succeed;
@@ -73,6 +75,29 @@ def _passthrough():
     return {k: v for k, v in vars(mod).items() if not k.startswith('_')}
 
 
+# the torch-only static helpers of KolmogorovFlow: the placeholder below and sda_amd.chains.KolmogorovFlow both hand these out
+def _coarsen(x: Tensor, r: int = 2) -> Tensor:
+    """Mean over r x r cells of the last two axes (sda/mcs.py:340-347)."""
+    h, w = x.shape[-2:]
+    return x.unflatten(-1, (w // r, r)).unflatten(-3, (h // r, r)).mean(dim=(-3, -1))
+
+
+def _upsample(x: Tensor, r: int = 2, mode: str = 'bilinear') -> Tensor:
+    """Periodic interpolation by a factor r (sda/mcs.py:349-359): one wrapped cell on each side, interpolate, crop."""
+    h, w = x.shape[-2:]
+    y = torch.nn.functional.pad(x.reshape(-1, 1, h, w), (1, 1, 1, 1), mode='circular')
+    y = torch.nn.functional.interpolate(y, scale_factor=(r, r), mode=mode)
+    return y[..., r:-r, r:-r].reshape(*x.shape[:-2], r * h, r * w)
+
+
+def _vorticity(x: Tensor) -> Tensor:
+    """d u / d x - d v / d y by periodic central differences of a (..., 2, H, W) velocity field (sda/mcs.py:361-375)."""
+    u, v = x[..., 0, :, :], x[..., 1, :, :]
+    du = (torch.roll(u, -1, -1) - torch.roll(u, 1, -1)) / 2
+    dv = (torch.roll(v, -1, -2) - torch.roll(v, 1, -2)) / 2
+    return du - dv
+
+
 globals().update(_passthrough())
 
 if SOURCE is None:
@@ -86,25 +111,6 @@ if SOURCE is None:
 
     def _placeholder(name: str, **statics):
         return type(name, (MarkovChain,), {'__doc__': f'Placeholder for sda.mcs.{name}.', '__module__': __name__, **statics})
-
-    def _coarsen(x: Tensor, r: int = 2) -> Tensor:
-        """Mean over r x r cells of the last two axes (sda/mcs.py:340-347)."""
-        h, w = x.shape[-2:]
-        return x.unflatten(-1, (w // r, r)).unflatten(-3, (h // r, r)).mean(dim=(-3, -1))
-
-    def _upsample(x: Tensor, r: int = 2, mode: str = 'bilinear') -> Tensor:
-        """Periodic interpolation by a factor r (sda/mcs.py:349-359): one wrapped cell on each side, interpolate, crop."""
-        h, w = x.shape[-2:]
-        y = torch.nn.functional.pad(x.reshape(-1, 1, h, w), (1, 1, 1, 1), mode='circular')
-        y = torch.nn.functional.interpolate(y, scale_factor=(r, r), mode=mode)
-        return y[..., r:-r, r:-r].reshape(*x.shape[:-2], r * h, r * w)
-
-    def _vorticity(x: Tensor) -> Tensor:
-        """d u / d x - d v / d y by periodic central differences of a (..., 2, H, W) velocity field (sda/mcs.py:361-375)."""
-        u, v = x[..., 0, :, :], x[..., 1, :, :]
-        du = (torch.roll(u, -1, -1) - torch.roll(u, 1, -1)) / 2
-        dv = (torch.roll(v, -1, -2) - torch.roll(v, 1, -2)) / 2
-        return du - dv
 
     DampedSpring = _placeholder('DampedSpring')
     DiscreteODE = _placeholder('DiscreteODE')

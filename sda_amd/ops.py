@@ -1336,3 +1336,152 @@ def bpf_traceback(S: Tensor, anc: Tensor, step: int) -> Tensor:
     _lib.check(_lib.load().sda_bpf_traceback(S.data_ptr(), m * d, d, _i32(anc, anc.numel(), 'bpf_traceback: anc'), m, anc.shape[0], step, d,
                                              out.data_ptr(), _stream()), 'sda_bpf_traceback')
     return out
+
+
+# ---------------------------------------------------------------- Kolmogorov flow (csrc/kflow.hip)
+_KFLOW_CONST = {}
+_KFLOW_SOLVE = {}
+
+
+def kflow_serves(n: int) -> bool:
+    """The sizes the kernels take: n % 16 == 0, 16 <= n <= 512."""
+    return bool(_lib.load().sda_kflow_serves(int(n)))
+
+
+def kflow_device_key(device):
+    """(type, index) of `device` with an unnamed HIP index resolved to the current device: what the per-device caches are keyed
+    on, so a cached table never outlives a change of the current device."""
+    device = torch.device(device)
+    if device.type == 'cuda' and device.index is None:
+        return device.type, torch.cuda.current_device()
+    return device.type, device.index
+
+
+def _kflow_solve_tables(n: int):
+    """Host float64: 1 / (lam_a + lam_b) with 0 for the mean mode (n, n), and the forcing profile sin(4 (j + 1/2) h) (n,)."""
+    k = torch.arange(n, dtype=torch.float64)
+    h = 2 * math.pi / n
+    lam = (2 * (2 * math.pi * k / n).cos() - 2) / (h * h)
+    s = lam[:, None] + lam[None, :]
+    s[0, 0] = 1.0
+    inv = 1 / s
+    inv[0, 0] = 0.0
+    forcing = (4 * (k + 0.5) * h).sin()
+    return inv, forcing
+
+
+def kflow_tables(n: int):
+    """Host float64 tables of size n: the Hartley matrix Hm (n, n), 1 / (lam_a + lam_b) with 0 for the mean mode (n, n), and the
+    forcing profile sin(4 (j + 1/2) h) (n,)."""
+    k = torch.arange(n, dtype=torch.int64)
+    ang = 2 * math.pi * ((k[:, None] * k[None, :]) % n).double() / n
+    hm = (ang.cos() + ang.sin()) / math.sqrt(n)
+    inv, forcing = _kflow_solve_tables(n)
+    return hm, inv, forcing
+
+
+def kflow_solve_tables(n: int, device, dtype):
+    """(inv, forcing) of `kflow_tables` on `device` in `dtype`, built once per (n, device, dtype): what the torch-ops route reads
+    every sub-step.  Hm is not built for it."""
+    device = torch.device(device)
+    key = (n, *kflow_device_key(device), dtype)
+    c = _KFLOW_SOLVE.get(key)
+    if c is None:
+        c = _KFLOW_SOLVE[key] = tuple(t.to(device=device, dtype=dtype) for t in _kflow_solve_tables(n))
+    return c
+
+
+def kflow_constants(n: int, device) -> Tensor:
+    """[Hm | inv | forcing] of size n on `device`, built once in float64 on the host and rounded."""
+    device = torch.device(device)
+    key = (n, *kflow_device_key(device))
+    c = _KFLOW_CONST.get(key)
+    if c is None:
+        hm, inv, forcing = kflow_tables(n)
+        c = _KFLOW_CONST[key] = torch.cat([hm.flatten(), inv.flatten(), forcing]).float().to(device)
+    return c
+
+
+def kflow_model(n: int, steps: int, delta: float, nu: float, device) -> '_lib.KflowModel':
+    """`sda_kflow_model`: delta = dt / steps and nu rounded to fp32 once."""
+    if not kflow_serves(n):
+        raise _lib.SdaHipError(f'kflow: size {n} is not served by the kernels (n % 16 == 0, 16 <= n <= 512)')
+    c = kflow_constants(n, device)
+    m = _lib.KflowModel()
+    m.n, m.steps, m.delta, m.nu = int(n), int(steps), float(delta), float(nu)
+    m.hm, m.inv, m.forcing = c.data_ptr(), c.data_ptr() + 4 * n * n, c.data_ptr() + 8 * n * n
+    m._keep = c
+    return m
+
+
+def _kflow_fields(x: Tensor, n: int, planes: int, what: str):
+    """x (..., planes, n, n) -> (nb, planes, n, n) whose fields are dense and 16-byte aligned (the batch stride is free)."""
+    _dev(x)
+    if x.dim() < 3 or tuple(x.shape[-3:]) != (planes, n, n) or x.numel() == 0:
+        raise _lib.SdaHipError(f'{what}: fields of shape {tuple(x.shape)}, expected (..., {planes}, {n}, {n})')
+    f = x.reshape(-1, planes, n, n)
+    sb = f.stride(0) if f.shape[0] > 1 else planes * n * n
+    dense = f.stride()[2:] == (n, 1) and (planes == 1 or f.stride(1) == n * n)
+    if not dense or sb < planes * n * n or sb % 4 or f.data_ptr() % 16:
+        f = f.contiguous()
+        sb = planes * n * n
+    if f.shape[0] > 65535:
+        raise _lib.SdaHipError(f'{what}: {f.shape[0]} fields in one call (at most 65535)')
+    return f, sb
+
+
+def kflow_explicit(model, x: Tensor) -> Tensor:
+    """x (..., 2, n, n) -> (u*, v*) = x + delta (-adv + nu lap + f), one launch."""
+    f, sb = _kflow_fields(x, model.n, 2, 'kflow_explicit')
+    out = torch.empty(f.shape, device=x.device, dtype=torch.float32)
+    _lib.check(_lib.load().sda_kflow_explicit(ctypes.byref(model), f.data_ptr(), sb, f.shape[0], out.data_ptr(), _stream()),
+               'sda_kflow_explicit')
+    return out.reshape(x.shape)
+
+
+def kflow_hartley(x: Tensor, scale: Optional[Tensor] = None) -> Tensor:
+    """x (..., n, n) -> (Hm x Hm) o scale on the fp32 matrix cores (two launches); scale (n, n) or None.  Hm is its own inverse."""
+    n = x.shape[-1]
+    if not kflow_serves(n):
+        raise _lib.SdaHipError(f'kflow_hartley: size {n} is not served (n % 16 == 0, 16 <= n <= 512)')
+    f, sb = _kflow_fields(x.unsqueeze(-3), n, 1, 'kflow_hartley')
+    if scale is not None:
+        _dev(scale)
+        if tuple(scale.shape) != (n, n) or not scale.is_contiguous():
+            raise _lib.SdaHipError(f'kflow_hartley: scale {tuple(scale.shape)}, expected a contiguous ({n}, {n})')
+    hm = kflow_constants(n, x.device)
+    tmp = torch.empty(f.shape, device=x.device, dtype=torch.float32)
+    out = torch.empty(f.shape, device=x.device, dtype=torch.float32)
+    lib = _lib.load()
+    _lib.check(lib.sda_kflow_hartley(hm.data_ptr(), n, f.data_ptr(), sb, f.shape[0], 0, None, tmp.data_ptr(), _stream()), 'sda_kflow_hartley')
+    _lib.check(lib.sda_kflow_hartley(hm.data_ptr(), n, tmp.data_ptr(), n * n, f.shape[0], 1, _ptr(scale), out.data_ptr(), _stream()),
+               'sda_kflow_hartley')
+    return out.reshape(x.shape)
+
+
+def kflow_project(model, x: Tensor) -> Tensor:
+    """x (..., 2, n, n) -> x - grad(lap^-1 div x): the divergence-free part (four launches)."""
+    n = model.n
+    f, sb = _kflow_fields(x, n, 2, 'kflow_project')
+    nb = f.shape[0]
+    out = torch.empty(f.shape, device=x.device, dtype=torch.float32)
+    work = torch.empty(2 * nb * n * n, device=x.device, dtype=torch.float32)
+    _lib.check(_lib.load().sda_kflow_project(ctypes.byref(model), f.data_ptr(), sb, nb, out.data_ptr(), 2 * n * n, work.data_ptr(),
+                                             _stream()), 'sda_kflow_project')
+    return out.reshape(x.shape)
+
+
+def kflow_advance(model, x: Tensor, transitions: int, every: bool = False) -> Tensor:
+    """x (nb..., 2, n, n) -> the state after `transitions` transitions (every=False), or (transitions, nb..., 2, n, n) with every
+    kept frame written straight into its slab.  All transitions x steps sub-steps are queued; nothing is read back."""
+    n = model.n
+    f, sb = _kflow_fields(x, n, 2, 'kflow_advance')
+    nb = f.shape[0]
+    if transitions < 1:
+        raise _lib.SdaHipError(f'kflow_advance: {transitions} transitions')
+    lib = _lib.load()
+    out = torch.empty((transitions, *x.shape) if every else tuple(x.shape), device=x.device, dtype=torch.float32)
+    work = torch.empty(lib.sda_kflow_work_floats(n, nb), device=x.device, dtype=torch.float32)
+    _lib.check(lib.sda_kflow_advance(ctypes.byref(model), f.data_ptr(), sb, nb, transitions, int(every), out.data_ptr(), nb * 2 * n * n,
+                                     work.data_ptr(), _stream()), 'sda_kflow_advance')
+    return out
