@@ -975,6 +975,23 @@ int sda_kflow_project(const sda_kflow_model* m, const float* x, int64_t x_sb, in
 int sda_kflow_advance(const sda_kflow_model* m, const float* x, int64_t x_sb, int nb, int transitions, int every, float* out,
                       int64_t out_st, float* work, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Adjoint of the Kolmogorov-flow sub-step (csrc/kflow.hip; additive, ABI stays v14).  The projection is its own transpose
+ * (G = -D^T, L and Hm symmetric), so sda_kflow_project is also its adjoint; what is added is the vector-Jacobian product of
+ * sda_kflow_explicit and the schedule that walks one transition backwards.  Derivative conventions at the limiter's kinks are
+ * those of torch autograd on the torch-ops route.  Gather form, no atomics: bitwise reproducible.
+ * sda_kfvjp_explicit: out[b] = (d explicit / dx at x[b])^T g[b]; x, g strided fields, out contiguous [nb][2][n][n], out != x, g.
+ * sda_kfvjp_transition: out[b] = (d transition / dx0 at x0[b])^T g[b].  Recomputes the model.steps - 1 inner sub-step states from
+ *   x0 with the forward launches (bitwise the forward pass's), then per sub-step, last to first, g <- P g (four launches) and
+ *   g <- E'(x_s)^T g (one).  All queued, nothing read back.  g_sb % 4 == 0, g 16-byte aligned; out contiguous, out != x0 (out may
+ *   be g).  work: sda_kfvjp_work_floats(n, nb, steps) = (steps + 2) 2 nb n n floats (0: not served).
+ * ------------------------------------------------------------------------------------------ */
+int64_t sda_kfvjp_work_floats(int n, int nb, int steps);
+int sda_kfvjp_explicit(const sda_kflow_model* m, const float* x, int64_t x_sb, const float* g, int64_t g_sb, int nb, float* out,
+                       void* stream);
+int sda_kfvjp_transition(const sda_kflow_model* m, const float* x0, int64_t x0_sb, const float* g, int64_t g_sb, int nb, float* out,
+                         float* work, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -406,6 +406,10 @@ SIGNATURES = {
     'sda_kflow_hartley': (c_int, [c_fp, c_int, c_fp, c_int64, c_int, c_int, c_fp, c_fp, c_void_p]),
     'sda_kflow_project': (c_int, [POINTER(KflowModel), c_fp, c_int64, c_int, c_fp, c_int64, c_fp, c_void_p]),
     'sda_kflow_advance': (c_int, [POINTER(KflowModel), c_fp, c_int64, c_int, c_int, c_int, c_fp, c_int64, c_fp, c_void_p]),
+    # the adjoint of the flow; its own prefix: tests/test_kflow_host.py pins the list of sda_kflow_* entries
+    'sda_kfvjp_work_floats': (c_int64, [c_int, c_int, c_int]),
+    'sda_kfvjp_explicit': (c_int, [POINTER(KflowModel), c_fp, c_int64, c_fp, c_int64, c_int, c_fp, c_void_p]),
+    'sda_kfvjp_transition': (c_int, [POINTER(KflowModel), c_fp, c_int64, c_fp, c_int64, c_int, c_fp, c_fp, c_void_p]),
 }
 
 _lib = None

@@ -254,6 +254,11 @@ LotkaVolterra._KERNEL = ('lotka_volterra', LotkaVolterra.f)
 
 
 # ---------------------------------------------------------------- Kolmogorov flow
+#: gradient route of the last ``KolmogorovFlow.transition`` / ``trajectory`` call: 'device' (the kernels and their adjoint), 'torch'
+#: (torch autograd through the torch-ops route), or None when the call's input did not require grad
+LAST_KFLOW_GRAD_ROUTE = None
+
+
 def _kflow_flux(a: Tensor, cm: Tensor, c0: Tensor, cp: Tensor, cpp: Tensor, dh: float) -> Tensor:
     """Van-Leer-limited Lax-Wendroff flux through the face between c0 and cp, advecting velocity a, dh = delta / h."""
     C = a * dh
@@ -274,6 +279,35 @@ def _shift(a: Tensor, di: int, dj: int) -> Tensor:
     return torch.roll(a, (-di, -dj), (-2, -1))
 
 
+class _KflowAdvance(torch.autograd.Function):
+    """``ops.kflow_advance`` with its adjoint.  Forward keeps every frame (the caller's own result when it asked for them, the
+    checkpoints otherwise); backward walks the transitions last to first, one ``ops.kflow_transition_vjp`` each, and adds the
+    cotangent of a kept frame as it passes it.  Memory: the frames plus one transition's slab of sub-step states."""
+
+    @staticmethod
+    def forward(ctx, x, model, length, last):
+        frames = ops.kflow_advance(model, x, length, every=length > 1 or not last)
+        ctx.model, ctx.length, ctx.last = model, length, last
+        ctx.save_for_backward(*((x, frames) if length > 1 else (x,)))      # one transition needs its input alone
+        if not last:
+            return frames
+        return frames[-1] if length > 1 else frames
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gout):
+        x, *frames = ctx.saved_tensors
+        frames = frames[0] if frames else None
+        length, last = ctx.length, ctx.last
+        gout = gout.to(torch.float32)
+        g = gout if last else gout[length - 1]
+        for t in range(length - 1, -1, -1):
+            g = ops.kflow_transition_vjp(ctx.model, frames[t - 1] if t else x, g)
+            if t and not last:
+                g = g + gout[t - 1]
+        return g, None, None, None
+
+
 class KolmogorovFlow(MarkovChain):
     r"""2-D incompressible flow with Kolmogorov forcing (sda/mcs.py:244-338) on the device.
 
@@ -285,10 +319,18 @@ class KolmogorovFlow(MarkovChain):
     ``transition`` and ``trajectory`` queue every launch (five per sub-step, csrc/kflow.hip) and read nothing back, and
     ``trajectory`` writes each kept frame straight into its slab.  The kernels serve ``size % 16 == 0, 16 <= size <= 512``; other
     sizes and inputs that require grad take the same scheme in torch ops (``_torch_substep``: ``torch.roll`` and ``torch.fft``,
-    differentiable).  A CPU tensor at a served size raises, as the Lorenz chains do."""
+    differentiable).  A CPU tensor at a served size raises, as the Lorenz chains do.
 
-    def __init__(self, size: int = 256, dt: float = 0.01, reynolds: int = 1e3):
+    ``grad='device'`` (opt-in) sends float32 HIP inputs that require grad at a served size through the kernels as well: forward is
+    ``ops.kflow_advance`` itself (bitwise the no-grad values), backward recomputes one transition's sub-step states at a time and
+    runs them backwards with the projection (its own transpose) and the explicit terms' VJP kernel.  First order only.
+    ``LAST_KFLOW_GRAD_ROUTE`` records the route a call took."""
+
+    def __init__(self, size: int = 256, dt: float = 0.01, reynolds: int = 1e3, *, grad: str = 'torch'):
         super().__init__()
+        if grad not in ('torch', 'device'):
+            raise ValueError(f"KolmogorovFlow: grad={grad!r}, expected 'torch' or 'device'")
+        self.grad = grad
         self.size, self.dt, self.reynolds = int(size), dt, reynolds
         h = 2 * math.pi / self.size
         nu = 1 / reynolds
@@ -398,14 +440,28 @@ class KolmogorovFlow(MarkovChain):
             x = x * torch.where(speed > 0, 3.0 / speed, torch.zeros_like(speed))[:, None, None, None]
         return x.reshape(*shape, 2, n, n)
 
+    def _grad_route(self, x: Tensor) -> Optional[str]:
+        """What carries the gradient of this call, recorded in ``LAST_KFLOW_GRAD_ROUTE``: None if nothing asks for one."""
+        global LAST_KFLOW_GRAD_ROUTE
+        route = None
+        if torch.is_grad_enabled() and x.requires_grad:
+            served = self.grad == 'device' and self._kernel_size and x.is_cuda and x.dtype == torch.float32
+            route = 'device' if served else 'torch'
+        LAST_KFLOW_GRAD_ROUTE = route
+        return route
+
     def transition(self, x: Tensor) -> Tensor:
         self._check(x)
+        if self._grad_route(x) == 'device':
+            return _KflowAdvance.apply(x, self.model(x.device), 1, True)
         if self._fused(x):
             return ops.kflow_advance(self.model(x.device), x, 1) if x.is_cuda else ops._dev(x)
         return self._torch_transition(x)
 
     def trajectory(self, x: Tensor, length: int, last: bool = False) -> Tensor:
         self._check(x)
+        if self._grad_route(x) == 'device' and length >= 1:
+            return _KflowAdvance.apply(x, self.model(x.device), length, last)
         if self._fused(x) and length >= 1:
             return ops.kflow_advance(self.model(x.device), x, length, every=not last) if x.is_cuda else ops._dev(x)
         return super().trajectory(x, length, last)

@@ -17,12 +17,26 @@
 // accumulators per fragment: q, q shifted by one row (the A rows one further) and q shifted by one column (the B columns one
 // further).  All three are the same blocked fma chains a neighbouring tile computes for the same element, so the values that
 // meet at a tile edge are bitwise equal and the projection is as exact at the edges as inside.
+//
+// The adjoint (opt-in, KolmogorovFlow(grad='device')).  D is a backward difference and G a forward one, so G = -D^T; L and Hm are
+// symmetric; hence P = I - G L^-1 D is its own transpose and the four product launches above ARE the adjoint of the projection.
+// The one new kernel is kflow_explicit_vjp_kernel, the vector-Jacobian product of kflow_explicit_kernel at a stored state, in
+// gather form (no atomics: bitwise reproducible, independent of the batch).  A transition runs backwards as: recompute its
+// sub-step states with the forward launches (bitwise the states the forward pass went through), then per sub-step, last to first,
+// g <- P g (four launches) and g <- E'(x_s)^T g (one launch).
 #include "sda_common.hpp"
 
 #define KF_THREADS 256
 #define KF_T 16             // explicit kernel: cells per tile side
 #define KF_HALO 2           // face i - 1 reads c[i - 2]; the `cpp` tap reads c[i + 2]
 #define KF_LT (KF_T + 2 * KF_HALO)
+#define KF_VH 3             // VJP, state halo: cell i is the cpp tap of face i - 2, whose cm tap is c[i - 3]; face i + 1 reads cpp = c[i + 3]
+#define KF_VG 2             // VJP, cotangent halo: the cotangent of face i - 2 reads g[i - 2], that of face i + 1 reads g[i + 2]
+#define KF_VLT (KF_T + 2 * KF_VH)
+#define KF_VGT (KF_T + 2 * KF_VG)
+#define KF_VFL (KF_T + 3)   // VJP, faces along the flux axis: -2 .. KF_T
+#define KF_VFC (KF_T + 1)   // VJP, faces across it: -1 .. KF_T - 1 (line -1 reaches the other field through the advecting velocity)
+#define KF_VFN (KF_VFL * KF_VFC)
 #define KF_TILE 64          // product kernels: output tile side
 #define KF_KC 16            // k-chunk
 #define KF_SK 80            // LDS row stride of a [k][64 + 1] operand image: 80 % 32 == 16 keeps k and k + 1 on disjoint banks
@@ -88,6 +102,113 @@ __global__ __launch_bounds__(KF_THREADS) void kflow_explicit_kernel(const float*
     float* ob = out + (int64_t)blockIdx.z * 2 * plane;
     ob[(int64_t)gi * n + gj] = us;
     ob[plane + (int64_t)gi * n + gj] = vs;
+}
+
+// ---------------------------------------------------------------- explicit terms, vector-Jacobian product
+// w[0 .. 4] = lam x the partials of kf_flux with respect to (cm, c0, cp, cpp, a).  The conventions at the kinks are those of torch
+// autograd on chains._kflow_flux: a > 0 selects the upwind branch (a == 0: the else branch) and a carries no derivative through the
+// selection; d == 0 gives r = 0 with zero derivative; |r| has derivative sign(r), 0 at r == 0 (so phi'(0) = 1).
+__device__ __forceinline__ void kf_flux_vjp(float a, float cm, float c0, float cp, float cpp, float dh, float lam, float* w) {
+    const float C = a * dh;
+    const float d = cp - c0;
+    const bool pos = a > 0.f;
+    const float low = pos ? c0 : cp;
+    const float num = pos ? c0 - cm : cpp - cp;
+    const float dhl = pos ? 0.5f * (1.f - C) : -0.5f * (1.f + C);    // d(high - low) / dd
+    const float hl = dhl * d;                                         // high - low
+    const bool nz = d != 0.f;
+    const float id = nz ? 1.f / d : 0.f;
+    const float r = nz ? num / d : 0.f;
+    const float ar = fabsf(r);
+    const float s = r > 0.f ? 1.f : (r < 0.f ? -1.f : 0.f);
+    const float q1 = 1.f / (1.f + ar);
+    const float phi = (r + ar) * q1;
+    const float dphi = ((1.f + s) - phi * s) * q1;                    // d phi / dr
+    const float gn = (hl * dphi) * id;                                // dQ / dnum, Q = low + phi (high - low)
+    const float gd = phi * dhl - gn * r;                              // dQ / dd
+    const float la = lam * a;
+    w[0] = pos ? -la * gn : 0.f;
+    w[1] = pos ? la * ((1.f + gn) - gd) : -la * gd;
+    w[2] = pos ? la * gd : la * ((1.f + gd) - gn);
+    w[3] = pos ? 0.f : la * gn;
+    w[4] = lam * ((low + phi * hl) - a * (phi * (0.5f * dh * d)));
+}
+
+// gx = (dE/dx)^T g for E = kflow_explicit_kernel, linearised at x.  Phase A: every face the tile's cells touch gets its cotangent
+// lam = -(delta / h) (g[i] - g[i + 1]) and lam x the five partials of its flux, into LDS.  Face kinds: 0 the x-faces of u, 1 the
+// y-faces of u, 2 the x-faces of v, 3 the y-faces of v; x-faces are stored [KF_VFL][KF_VFC] (rows -2 .., columns -1 ..), y-faces
+// [KF_VFC][KF_VFL] (rows -1 .., columns -2 ..).  Phase B: a cell is the cm, c0, cp, cpp tap of four faces along each axis of its own
+// field, and enters the advecting velocity of two faces of each kind that averages its field -- a fixed-order sum per cell.
+__global__ __launch_bounds__(KF_THREADS) void kflow_explicit_vjp_kernel(const float* __restrict__ x, int64_t x_sb,
+                                                                        const float* __restrict__ g, int64_t g_sb, int n, float delta,
+                                                                        float nu, float h, float dh, float* __restrict__ out) {
+    constexpr int XS = KF_VLT + 1, GS = KF_VGT + 1;
+    __shared__ float sx[2][KF_VLT * XS], sg[2][KF_VGT * GS];
+    __shared__ float sw[4][5][KF_VFN];
+    const int i0 = blockIdx.y * KF_T, j0 = blockIdx.x * KF_T;
+    const float* xb = x + (int64_t)blockIdx.z * x_sb;
+    const float* gb = g + (int64_t)blockIdx.z * g_sb;
+    const int64_t plane = (int64_t)n * n;
+    for (int e = threadIdx.x; e < KF_VLT * KF_VLT; e += KF_THREADS) {
+        const int r = e / KF_VLT, c = e - r * KF_VLT;
+        int gi = i0 + r - KF_VH, gj = j0 + c - KF_VH;
+        gi = gi < 0 ? gi + n : (gi >= n ? gi - n : gi);
+        gj = gj < 0 ? gj + n : (gj >= n ? gj - n : gj);
+        sx[0][r * XS + c] = xb[(int64_t)gi * n + gj];
+        sx[1][r * XS + c] = xb[plane + (int64_t)gi * n + gj];
+    }
+    for (int e = threadIdx.x; e < KF_VGT * KF_VGT; e += KF_THREADS) {
+        const int r = e / KF_VGT, c = e - r * KF_VGT;
+        int gi = i0 + r - KF_VG, gj = j0 + c - KF_VG;
+        gi = gi < 0 ? gi + n : (gi >= n ? gi - n : gi);
+        gj = gj < 0 ? gj + n : (gj >= n ? gj - n : gj);
+        sg[0][r * GS + c] = gb[(int64_t)gi * n + gj];
+        sg[1][r * GS + c] = gb[plane + (int64_t)gi * n + gj];
+    }
+    __syncthreads();
+    for (int e = threadIdx.x; e < 4 * KF_VFN; e += KF_THREADS) {
+        const int t = e / KF_VFN, f = e - t * KF_VFN;
+        const bool xdir = !(t & 1);
+        const int q = xdir ? f / KF_VFC : f / KF_VFL;
+        const int r = xdir ? q - 2 : q - 1;
+        const int c = xdir ? f - q * KF_VFC - 1 : f - q * KF_VFL - 2;
+        const float* sc = sx[t >> 1];                     // the advected field
+        const float* sa = sx[t & 1];                      // the field the advecting velocity averages ...
+        const int at = (r + KF_VH) * XS + c + KF_VH;
+        const int st = xdir ? XS : 1;
+        const int ast = (t >> 1) ? 1 : XS;                // ... towards the neighbour in the direction the field is staggered
+        const float* gg = sg[t >> 1];
+        const int gat = (r + KF_VG) * GS + c + KF_VG;
+        const float lam = -dh * (gg[gat] - gg[gat + (xdir ? GS : 1)]);
+        float w[5];
+        kf_flux_vjp(0.5f * (sa[at] + sa[at + ast]), sc[at - st], sc[at], sc[at + st], sc[at + 2 * st], dh, lam, w);
+#pragma unroll
+        for (int k = 0; k < 5; ++k) sw[t][k][f] = w[k];
+    }
+    __syncthreads();
+    const int li = threadIdx.x >> 4, lj = threadIdx.x & 15;
+#define FX(t, k, di, dj) sw[t][k][(li + (di) + 2) * KF_VFC + lj + (dj) + 1]
+#define FY(t, k, di, dj) sw[t][k][(li + (di) + 1) * KF_VFL + lj + (dj) + 2]
+#define G(p, di, dj) sg[p][(li + (di) + KF_VG) * GS + lj + (dj) + KF_VG]
+    const float h2 = h * h;
+    // the diffusion, drag and identity terms are linear and symmetric: their adjoint is the same stencil on g
+    const float lap_u = ((((G(0, 1, 0) + G(0, -1, 0)) + G(0, 0, 1)) + G(0, 0, -1)) - 4.f * G(0, 0, 0)) / h2;
+    const float lap_v = ((((G(1, 1, 0) + G(1, -1, 0)) + G(1, 0, 1)) + G(1, 0, -1)) - 4.f * G(1, 0, 0)) / h2;
+    float gu = G(0, 0, 0) + delta * (nu * lap_u - 0.1f * G(0, 0, 0));
+    float gv = G(1, 0, 0) + delta * (nu * lap_v - 0.1f * G(1, 0, 0));
+    gu += (FX(0, 0, 1, 0) + FX(0, 1, 0, 0)) + (FX(0, 2, -1, 0) + FX(0, 3, -2, 0));
+    gu += (FY(1, 0, 0, 1) + FY(1, 1, 0, 0)) + (FY(1, 2, 0, -1) + FY(1, 3, 0, -2));
+    gu += 0.5f * ((FX(0, 4, 0, 0) + FX(0, 4, -1, 0)) + (FX(2, 4, 0, 0) + FX(2, 4, 0, -1)));
+    gv += (FX(2, 0, 1, 0) + FX(2, 1, 0, 0)) + (FX(2, 2, -1, 0) + FX(2, 3, -2, 0));
+    gv += (FY(3, 0, 0, 1) + FY(3, 1, 0, 0)) + (FY(3, 2, 0, -1) + FY(3, 3, 0, -2));
+    gv += 0.5f * ((FY(1, 4, 0, 0) + FY(1, 4, -1, 0)) + (FY(3, 4, 0, 0) + FY(3, 4, 0, -1)));
+#undef FX
+#undef FY
+#undef G
+    float* ob = out + (int64_t)blockIdx.z * 2 * plane;
+    const int64_t at = (int64_t)(i0 + li) * n + j0 + lj;
+    ob[at] = gu;
+    ob[plane + at] = gv;
 }
 
 // ---------------------------------------------------------------- dense products with Hm
@@ -281,6 +402,14 @@ static void kf_launch_explicit(const sda_kflow_model* m, const float* x, int64_t
                        m->nu, h, dh, m->forcing, out);
 }
 
+static void kf_launch_explicit_vjp(const sda_kflow_model* m, const float* x, int64_t x_sb, const float* g, int64_t g_sb, int nb, float* out,
+                                   hipStream_t st) {
+    const float h = kf_h(m->n);
+    const float dh = (float)((double)m->delta / (6.283185307179586476925286766559 / (double)m->n));
+    hipLaunchKernelGGL(kflow_explicit_vjp_kernel, dim3(m->n / KF_T, m->n / KF_T, nb), dim3(KF_THREADS), 0, st, x, x_sb, g, g_sb, m->n,
+                       m->delta, m->nu, h, dh, out);
+}
+
 // out = uv - grad(lap^-1 div(uv)): four launches; ta, tb: nb planes each
 static void kf_launch_project(const sda_kflow_model* m, const float* uv, int64_t uv_sb, int nb, float* out, int64_t out_sb, float* ta,
                               float* tb, hipStream_t st) {
@@ -355,5 +484,63 @@ extern "C" int sda_kflow_advance(const sda_kflow_model* m, const float* x, int64
             rc = sda_launch_status();
             if (rc != SDA_OK) return rc;
         }
+    return SDA_OK;
+}
+
+// ---------------------------------------------------------------- the adjoint of a transition
+extern "C" int64_t sda_kfvjp_work_floats(int n, int nb, int steps) {
+    if (!sda_kflow_serves(n) || nb < 1 || steps < 1) return 0;
+    // the states sub-steps 1 .. steps - 1 start from | u* of the recompute, then P g | T a, T b | the running cotangent
+    return ((int64_t)steps + 2) * 2 * nb * n * n;
+}
+
+extern "C" int sda_kfvjp_explicit(const sda_kflow_model* m, const float* x, int64_t x_sb, const float* g, int64_t g_sb, int nb, float* out,
+                                  void* stream) {
+    int rc = kf_model_check(m, nb);
+    if (rc != SDA_OK) return rc;
+    const int64_t plane = (int64_t)m->n * m->n;
+    if (!x || !g || !out || x_sb < 2 * plane || g_sb < 2 * plane || out == x || out == g) return SDA_E_BADARG;
+    kf_launch_explicit_vjp(m, x, x_sb, g, g_sb, nb, out, (hipStream_t)stream);
+    return sda_launch_status();
+}
+
+extern "C" int sda_kfvjp_transition(const sda_kflow_model* m, const float* x0, int64_t x0_sb, const float* g, int64_t g_sb, int nb,
+                                    float* out, float* work, void* stream) {
+    int rc = kf_model_check(m, nb);
+    if (rc != SDA_OK) return rc;
+    const int64_t plane = (int64_t)m->n * m->n, field = 2 * plane, slab = field * nb;
+    if (!x0 || !g || !out || !work || x0_sb < field || g_sb < field || g_sb % 4 != 0 || out == x0) return SDA_E_BADARG;
+    hipStream_t st = (hipStream_t)stream;
+    const int steps = m->steps;
+    float* states = work;                                 // states[s - 1]: what sub-step s starts from, s = 1 .. steps - 1
+    float* tmp = work + (int64_t)(steps - 1) * slab;
+    float* ta = tmp + slab;
+    float* tb = ta + nb * plane;
+    float* run = ta + slab;
+    // forward again, with the launches of sda_kflow_advance: bitwise the states the forward pass went through
+    const float* cur = x0;
+    int64_t cur_sb = x0_sb;
+    for (int s = 0; s + 1 < steps; ++s) {
+        float* dst = states + (int64_t)s * slab;
+        kf_launch_explicit(m, cur, cur_sb, nb, tmp, st);
+        kf_launch_project(m, tmp, field, nb, dst, field, ta, tb, st);
+        cur = dst;
+        cur_sb = field;
+        rc = sda_launch_status();
+        if (rc != SDA_OK) return rc;
+    }
+    // backwards: g <- P g (P is its own transpose), then g <- E'(x_s)^T g
+    const float* gc = g;
+    int64_t gc_sb = g_sb;
+    for (int s = steps - 1; s >= 0; --s) {
+        const float* xs = s ? states + (int64_t)(s - 1) * slab : x0;
+        float* dst = s ? run : out;
+        kf_launch_project(m, gc, gc_sb, nb, tmp, field, ta, tb, st);
+        kf_launch_explicit_vjp(m, xs, s ? field : x0_sb, tmp, field, nb, dst, st);
+        gc = dst;
+        gc_sb = field;
+        rc = sda_launch_status();
+        if (rc != SDA_OK) return rc;
+    }
     return SDA_OK;
 }

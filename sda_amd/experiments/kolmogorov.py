@@ -1,7 +1,7 @@
 r"""Kolmogorov chain and score-network factories (experiments/kolmogorov/utils.py:25-81 of the reference)."""
 
 from pathlib import Path
-from typing import Sequence
+from typing import Callable, Optional, Sequence
 
 import torch
 import torch.nn as nn
@@ -12,9 +12,33 @@ from ..score import MCScoreNet, ScoreUNet
 from ..utils import ACTIVATIONS, load_config
 
 
-def make_chain() -> MarkovChain:
-    r"""The flow the reference's data comes from (kolmogorov/utils.py:25-26): 256 x 256, dt = 0.2 (82 sub-steps)."""
-    return KolmogorovFlow(size=256, dt=0.2)
+def make_chain(grad: str = 'torch') -> MarkovChain:
+    r"""The flow the reference's data comes from (kolmogorov/utils.py:25-26): 256 x 256, dt = 0.2 (82 sub-steps).  ``grad='device'``
+    differentiates through the kernels (``KolmogorovFlow``)."""
+    return KolmogorovFlow(size=256, dt=0.2, grad=grad)
+
+
+def strong_4d_var(x_b: Tensor, y: Tensor, A: Callable[[Tensor], Tensor] = lambda x: x, sigma: float = 1.0, step: int = 1,
+                  iterations: int = 16, chain: Optional[MarkovChain] = None) -> Tensor:
+    r"""Strong-constraint 4D-Var by L-BFGS over the initial state of a deterministic chain, the counterpart of
+    ``experiments.lorenz.weak_4d_var``: minimises :math:`|x_0 - x_b|^2 + \sum |y - A(x_{1:L:step})|^2 / \sigma^2` where
+    ``x_{1:L} = chain.trajectory(x0, L)`` and ``L = len(y) * step``.  ``A`` is any differentiable callable on the kept frames
+    (``len(y)``, ..., 2, size, size).  ``chain`` defaults to ``make_chain(grad='device')``."""
+    chain = make_chain(grad='device') if chain is None else chain
+    length = len(y) * step
+    x0 = torch.nn.Parameter(x_b.detach().clone())
+    optimizer = torch.optim.LBFGS((x0,))
+
+    def closure():
+        optimizer.zero_grad()
+        loss = (x0 - x_b).square().sum() + ((y - A(chain.trajectory(x0, length)[::step])).square() / sigma ** 2).sum()
+        loss.backward()
+        return loss
+
+    for _ in range(iterations):
+        optimizer.step(closure)
+
+    return x0.data
 
 
 class LocalScoreUNet(ScoreUNet):

@@ -1485,3 +1485,33 @@ def kflow_advance(model, x: Tensor, transitions: int, every: bool = False) -> Te
     _lib.check(lib.sda_kflow_advance(ctypes.byref(model), f.data_ptr(), sb, nb, transitions, int(every), out.data_ptr(), nb * 2 * n * n,
                                      work.data_ptr(), _stream()), 'sda_kflow_advance')
     return out
+
+
+def _kflow_pair(model, x: Tensor, g: Tensor, what: str):
+    if g.shape != x.shape or g.device != x.device:
+        raise _lib.SdaHipError(f'{what}: cotangent {tuple(g.shape)} on {g.device} for states {tuple(x.shape)} on {x.device}')
+    if x.dtype != torch.float32 or g.dtype != torch.float32:
+        raise _lib.SdaHipError(f'{what}: float32 states and cotangents, got {x.dtype} and {g.dtype}')
+    return _kflow_fields(x, model.n, 2, what), _kflow_fields(g, model.n, 2, what)
+
+
+def kflow_explicit_vjp(model, x: Tensor, g: Tensor) -> Tensor:
+    """(d kflow_explicit / dx at x)^T g, both (..., 2, n, n): one launch, gather form (bitwise reproducible)."""
+    (f, sb), (gf, gsb) = _kflow_pair(model, x, g, 'kflow_explicit_vjp')
+    out = torch.empty(f.shape, device=x.device, dtype=torch.float32)
+    _lib.check(_lib.load().sda_kfvjp_explicit(ctypes.byref(model), f.data_ptr(), sb, gf.data_ptr(), gsb, f.shape[0], out.data_ptr(),
+                                              _stream()), 'sda_kfvjp_explicit')
+    return out.reshape(x.shape)
+
+
+def kflow_transition_vjp(model, x0: Tensor, g: Tensor) -> Tensor:
+    """(d transition / dx0 at x0)^T g, both (..., 2, n, n): the sub-step states are recomputed from x0 into one slab, then the
+    sub-steps run backwards (five launches each, as forward).  All queued; nothing is read back."""
+    (f, sb), (gf, gsb) = _kflow_pair(model, x0, g, 'kflow_transition_vjp')
+    nb = f.shape[0]
+    lib = _lib.load()
+    out = torch.empty(f.shape, device=x0.device, dtype=torch.float32)
+    work = torch.empty(lib.sda_kfvjp_work_floats(model.n, nb, model.steps), device=x0.device, dtype=torch.float32)
+    _lib.check(lib.sda_kfvjp_transition(ctypes.byref(model), f.data_ptr(), sb, gf.data_ptr(), gsb, nb, out.data_ptr(), work.data_ptr(),
+                                        _stream()), 'sda_kfvjp_transition')
+    return out.reshape(x0.shape)
