@@ -2,6 +2,7 @@
 // guidance elementwise pieces.  All are streaming kernels (one read + one write of each operand); the per-sample
 // reduction uses 64-lane wavefront shuffles.
 #include "sda_common.hpp"
+#include "guide.hpp"                 // the guided step's arithmetic, shared with the fused epilogues
 
 extern "C" int sda_abi_version(void) { return SDA_ABI_VERSION; }
 
@@ -188,7 +189,7 @@ __global__ void pc_predict_kernel(float* __restrict__ x, const float* __restrict
                                   const float* __restrict__ coef) {
     if (coef) { r = coef[0]; c1 = coef[1]; }
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < numel; i += (int64_t)gridDim.x * blockDim.x)
-        x[i] = r * x[i] + c1 * eps[i];
+        x[i] = sda_pc_predict_of(x[i], eps[i], r, c1);
 }
 
 extern "C" int sda_pc_predict(float* x, const float* eps, int64_t numel, float r, float c1, const float* coef_dev,
@@ -233,12 +234,12 @@ __global__ __launch_bounds__(256) void pc_correct_kernel(float* __restrict__ x, 
     if (coef) sigma = coef[0];
     float tot = 0.f;
     for (int j = 0; j < nchunk; ++j) tot += partial[(int64_t)b * nchunk + j];
-    const float delta = tau / (tot / (float)per_sample);
-    const float sq = sqrtf(2.0f * delta);
+    float delta, sq;
+    sda_langevin_step(tot, per_sample, tau, delta, sq);
     const int64_t base = (int64_t)b * per_sample;
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < per_sample; i += (int64_t)gridDim.x * 256) {
         const int64_t o = base + i;
-        x[o] = x[o] - (delta * eps[o] + sq * z[o]) * sigma;
+        x[o] = sda_langevin_correct(x[o], eps[o], z[o], delta, sq, sigma);
     }
 }
 
@@ -254,8 +255,9 @@ extern "C" int sda_pc_correct(float* x, const float* eps, const float* z, int b,
 __global__ void denoise_kernel(const float* __restrict__ x, const float* __restrict__ eps, int64_t numel, float mu,
                                float sigma, const float* __restrict__ coef, float* __restrict__ xhat) {
     if (coef) { mu = coef[0]; sigma = coef[1]; }
+    const SdaGuide g = sda_guide(mu, sigma);
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < numel; i += (int64_t)gridDim.x * blockDim.x)
-        xhat[i] = (x[i] - sigma * eps[i]) / mu;
+        xhat[i] = g.xhat(x[i], eps[i]);
 }
 
 extern "C" int sda_denoise(const float* x, const float* eps, int64_t numel, float mu, float sigma,
@@ -271,9 +273,9 @@ __global__ void guided_combine_kernel(const float* __restrict__ eps, const float
                                       const float* __restrict__ vjp, int64_t numel, float mu, float sigma,
                                       const float* __restrict__ coef, float* __restrict__ out) {
     if (coef) { mu = coef[0]; sigma = coef[1]; }
-    const float k = sigma / mu;
+    const SdaGuide g = sda_guide(mu, sigma);
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < numel; i += (int64_t)gridDim.x * blockDim.x)
-        out[i] = eps[i] - k * (ghat[i] - (vjp ? sigma * vjp[i] : 0.f));
+        out[i] = vjp ? g.score(eps[i], ghat[i], vjp[i]) : g.score(eps[i], ghat[i]);
 }
 
 extern "C" int sda_guided_combine(const float* eps, const float* ghat, const float* vjp, int64_t numel, float mu,
@@ -291,11 +293,9 @@ __global__ void gauss_cotangent_kernel(const float* __restrict__ y, int64_t y_nu
                                        float std, float gamma, float mu, float sigma, const float* __restrict__ coef,
                                        float* __restrict__ out) {
     if (coef) { mu = coef[0]; sigma = coef[1]; }
-    // (the reference's operation order, rounded step by step: no fused multiply-add, a division per element)
-    const float r = __fdiv_rn(sigma, mu);
-    const float var = __fadd_rn(__fmul_rn(std, std), __fmul_rn(gamma, __fmul_rn(r, r)));
+    const SdaGuide g = sda_guide(mu, sigma, std, gamma);
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < numel; i += (int64_t)gridDim.x * blockDim.x)
-        out[i] = __fdiv_rn(y[y_numel == numel ? i : i % y_numel] - ax[i], var);
+        out[i] = g.cot(y[y_numel == numel ? i : i % y_numel], ax[i]);
 }
 
 extern "C" int sda_gauss_cotangent(const float* y, int64_t y_numel, const float* ax, int64_t numel, float std, float gamma,

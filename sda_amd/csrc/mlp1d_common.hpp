@@ -3,6 +3,7 @@
 // mode, the wide kernels' unit walk and the descriptor check.  See the header of mlp1d.hip for the design.
 #pragma once
 #include "sda_common.hpp"
+#include "guide.hpp"
 #include <stdlib.h>
 #include <type_traits>
 
@@ -292,16 +293,12 @@ __device__ __forceinline__ void ml_win_load(const sda_mlp_win& w, const MlCtx& c
 // hold the window values of a row.  (WF = 1 is the code of the one-fragment version, value for value.)
 template <int WF, int NF>
 __device__ __forceinline__ void ml_win_fold(const sda_mlp_win& w, const MlCtx& c, const ml_f32x4 (&a)[NF]) {
-    // fold (score.py:155-164) + eps = (cx0 + cx1 sigma) x + cn s + the likelihood cotangent, as sda_net1d_fwd_fused's epilogue
+    // fold (score.py:155-164) + eps = (cx0 + cx1 sigma) x + cn s + the likelihood cotangent: guide.hpp's arithmetic, as sda_net1d_fwd_fused's epilogue
     if (c.rowok) {
         const MlWinRow wr = ml_win_row(w, c);
         const int k = (w.len - w.nw) / 2, wc = (2 * k + 1) * w.c;
-        const float mu = w.coef[0], sg = w.coef[1];
-        const bool bare = w.cx0 == 0.f && w.cx1 == 0.f && w.cn == 1.f;
-        const float cx = w.cx0 + w.cx1 * sg;
-        const float rr = __fdiv_rn(sg, mu);
-        const float var = __fadd_rn(__fmul_rn(w.std, w.std), __fmul_rn(w.gamma, __fmul_rn(rr, rr)));
-        const int n_oc = (w.c_stop - w.c_start + w.c_step - 1) / w.c_step;
+        const SdaGuide g = sda_guide_of(w);
+        const SdaLattice obs = sda_lattice_of(w);
         const float* yb = w.y + (int64_t)wr.b * w.y_sn;
 #pragma unroll
         for (int m = 0; m < WF; ++m)
@@ -314,14 +311,12 @@ __device__ __forceinline__ void ml_win_fold(const sda_mlp_win& w, const MlCtx& c
                 const int ps = wr.i + j;
                 const int64_t o = ((int64_t)wr.b * w.len + ps) * w.c + ch;
                 const float xv = w.x[o];
-                const float ov = a[m][r];
-                const float e = bare ? ov : (xv * cx) + (w.cn * ov);
+                const float e = g.eps_of(xv, a[m][r]);
                 w.eps[o] = e;
-                const int crel = ch - w.c_start, prel = ps - w.p_start;
                 float gv = 0.f;
-                if (crel >= 0 && ch < w.c_stop && crel % w.c_step == 0 && prel >= 0 && ps < w.p_stop && prel % w.p_step == 0) {
-                    const float xh = (xv - sg * e) / mu;
-                    gv = __fdiv_rn(yb[(prel / w.p_step) * n_oc + crel / w.c_step] - xh, var);
+                if (obs.at(ps, ch)) {
+                    const float xh = g.xhat(xv, e);
+                    gv = g.cot(yb[obs.y_index(ps, ch)], xh);
                 }
                 w.ghat[o] = gv;
             }

@@ -3,6 +3,7 @@
 // tiling planner.  See the header comment of net1d.hip for the design.
 #pragma once
 #include "sda_common.hpp"
+#include "guide.hpp"
 #include <type_traits>
 #include <stdlib.h>
 
@@ -446,12 +447,8 @@ __global__ __launch_bounds__(256) void net1d_fwd_kernel(const sda_net1d_desc d, 
         }
     } else {
         const n1_f32x4 bt = *reinterpret_cast<const n1_f32x4*>(sb + (1 + 2 * d.nblocks) * 64 + cbase);
-        const float mu = f.coef[0], sg = f.coef[1];
-        const bool bare = f.cx0 == 0.f && f.cx1 == 0.f && f.cn == 1.f;
-        const float cx = f.cx0 + f.cx1 * sg;
-        const float rr = __fdiv_rn(sg, mu);
-        const float var = __fadd_rn(__fmul_rn(f.std, f.std), __fmul_rn(f.gamma, __fmul_rn(rr, rr)));
-        const int n_oc = (f.c_stop - f.c_start + f.c_step - 1) / f.c_step;
+        const SdaGuide g = sda_guide_of(f);
+        const SdaLattice obs = sda_lattice_of(f);
         const float* xb = d.x + (int64_t)c.n * d.x_sn;
         const float* yb = f.y + (int64_t)c.n * f.y_sn;
         float* eb = d.out + (int64_t)c.n * d.out_sn;
@@ -460,23 +457,19 @@ __global__ __launch_bounds__(256) void net1d_fwd_kernel(const sda_net1d_desc d, 
         for (int r = 0; r < 4; ++r) {
             const int ch = cbase + r;
             const bool cok = ch < d.cout;
-            const int crel = ch - f.c_start;
-            const bool c_obs = crel >= 0 && ch < f.c_stop && crel % f.c_step == 0;
-            const int och = c_obs ? crel / f.c_step : 0;
+            const SdaLatticeChan oc = obs.channel(ch);
 #pragma unroll
             for (int nf = 0; nf < NF; ++nf) {
                 if (!(nf < nfo && own[nf] && cok)) continue;
                 const int ps = (int)((soff[nf] - (unsigned)(cbase * d.len)));          // this column's position
                 const float xv = xb[(unsigned)(ch * (int)d.x_sc + ps * (int)d.x_sx)];
-                const float ov = o[nf][r] + bt[r];
-                const float e = bare ? ov : (xv * cx) + (f.cn * ov);
+                const float e = g.eps_of(xv, o[nf][r] + bt[r]);
                 const unsigned oo = ooff[nf] + (unsigned)(r * (int)d.out_sc);
                 eb[oo] = e;
-                const int prel = ps - f.p_start;
                 float gv = 0.f;
-                if (c_obs && prel >= 0 && ps < f.p_stop && prel % f.p_step == 0) {
-                    const float xh = (xv - sg * e) / mu;
-                    gv = __fdiv_rn(yb[(prel / f.p_step) * n_oc + och] - xh, var);
+                if (obs.at(oc, ps)) {
+                    const float xh = g.xhat(xv, e);
+                    gv = g.cot(yb[obs.y_index(oc, ps)], xh);
                 }
                 gb[oo] = gv;
             }
@@ -492,7 +485,8 @@ __global__ __launch_bounds__(256) void net1d_fwd_kernel(const sda_net1d_desc d, 
 // FUSED (sda_net1d_bwd_fused): x = ghat (the cotangent the fused forward wrote); the tile is scaled by cn on the way in, and the
 // epilogue finishes the guided score on the own columns,
 //   vjp = (cx0 + cx1 sigma) ghat + J_net^T (cn ghat);   out = eps - (sigma / mu) (ghat - sigma vjp)            (sda_guided_combine)
-// and, by f.mode, 0: writes out;  1: applies the predictor update x <- r x + c1 out in place (sda_pc_predict; safe: this launch
+// -- guide.hpp's functions, which the unfused kernels call too -- and, by f.mode (guide.hpp: SdaGuideTail), 0: writes out;  1: applies
+// the predictor update x <- r x + c1 out in place (sda_pc_predict; safe: this launch
 // reads x on its own columns only);  2: writes out and this tile's sum of out^2 into partial[image][tile] (a fixed slot: the
 // Langevin step size of sda/score.py:259 stays deterministic) for sda_pc_correct / sda_pc_correct_keyed.
 template <int NF, bool FUSED, bool TRAIN = false>
@@ -705,12 +699,8 @@ __global__ __launch_bounds__(256) void net1d_bwd_kernel(const sda_net1d_desc d, 
                 if (nf < nfo && own[nf] && cok) obr[ooff[nf]] = o[nf][r];
         }
     } else {
-        const float mu = f.coef[0], sg = f.coef[1];
-        const bool bare = f.cx0 == 0.f && f.cx1 == 0.f && f.cn == 1.f;
-        const float cx = f.cx0 + f.cx1 * sg;
-        const float kk = sg / mu;
-        float pr = 0.f, pc1 = 0.f;
-        if (f.mode == 1) { pr = f.step_coef[0]; pc1 = f.step_coef[1]; }
+        const SdaGuide g = sda_guide_of(f);
+        const SdaGuideTail tail = sda_guide_tail(f.mode, f.step_coef);
         const float* gb = d.x + (int64_t)c.n * d.x_sn;                 // ghat (unscaled), same layout as the outputs
         const float* eb = f.eps + (int64_t)c.n * d.out_sn;
         float* ob = d.out + (int64_t)c.n * d.out_sn;
@@ -724,13 +714,7 @@ __global__ __launch_bounds__(256) void net1d_bwd_kernel(const sda_net1d_desc d, 
                 if (!(nf < nfo && own[nf] && cok)) continue;
                 const unsigned oo = ooff[nf] + (unsigned)(r * (int)d.out_sc);
                 const float gv = gb[(unsigned)((cbase + r) * (int)d.x_sc) + poff[nf] * (unsigned)d.x_sx];
-                const float vj = bare ? o[nf][r] : (gv * cx) + o[nf][r];
-                const float ov = eb[oo] - kk * (gv - sg * vj);
-                if (f.mode == 1) xb[oo] = pr * xb[oo] + pc1 * ov;
-                else {
-                    ob[oo] = ov;
-                    acc += ov * ov;
-                }
+                tail.put(g.score(eb[oo], gv, g.vjp_of(gv, o[nf][r])), ob + oo, xb + oo, acc);
             }
         }
         if (f.mode == 2) {

@@ -5,6 +5,7 @@
 // With an adjoint available, GaussianScore needs no autograd through A: d log p / d x_hat = A^T((y - A x_hat)/var).
 // All kernels are streaming (HBM-bound): one read of the source, one write of the destination.
 #include "sda_common.hpp"
+#include "guide.hpp"                 // the likelihood cotangent's arithmetic, shared with the fused epilogues
 
 static inline unsigned obs_grid(int64_t total) {
     int64_t b = (total + 255) / 256;
@@ -93,8 +94,7 @@ __global__ void subsample_guidance_kernel(const float* __restrict__ x, const flo
                                           int64_t y_numel, Slice5 s, int64_t total_x, float std, float gamma, float mu, float sigma,
                                           const float* __restrict__ coef, float* __restrict__ g) {
     if (coef) { mu = coef[0]; sigma = coef[1]; }
-    const float r = __fdiv_rn(sigma, mu);
-    const float var = __fadd_rn(__fmul_rn(std, std), __fmul_rn(gamma, __fmul_rn(r, r)));
+    const SdaGuide gd = sda_guide(mu, sigma, std, gamma);
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total_x; i += (int64_t)gridDim.x * blockDim.x) {
         int64_t q = i, dst = 0, mul = 1;
         bool hit = true;
@@ -110,8 +110,8 @@ __global__ void subsample_guidance_kernel(const float* __restrict__ x, const flo
         if (hit) {
 #pragma unroll
             for (int d = 4; d >= 0; --d) { dst += (int64_t)o[d] * mul; mul *= s.osize[d]; }
-            const float xh = (x[i] - sigma * eps[i]) / mu;
-            v = __fdiv_rn(y[dst % y_numel] - xh, var);
+            const float xh = gd.xhat(x[i], eps[i]);
+            v = gd.cot(y[dst % y_numel], xh);
         }
         g[i] = v;
     }

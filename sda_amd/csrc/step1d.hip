@@ -6,9 +6,12 @@
 //                               times -- one launch instead of 2 x (2 sda_vp_schedule + sda_time_embed + sda_linear_small)
 //                               + 3 table-bookkeeping launches.
 //   pc_correct_keyed_kernel  -- the Langevin correction (score.py:257-261) with its row-keyed noise generated in the kernel.
-// Both replay the arithmetic of the kernels they replace operation for operation (elementwise.hip, noise.hip), so the fused
-// step is bit-identical to the unfused one wherever the summation order is the same.
+// Both replay the arithmetic of the kernels they replace operation for operation, so the fused step is bit-identical to the unfused
+// one wherever the summation order is the same: the Langevin update and the guided score are guide.hpp's functions and the noise is
+// philox.hpp's, the ones elementwise.hip and noise.hip call.
 #include "sda_common.hpp"
+#include "guide.hpp"
+#include "philox.hpp"
 
 #ifdef SDA_S1_TRACE                    // tooling build: cycle stamps of thread 0 at the phase boundaries -> out_coef[9 .. 15] (as floats)
 #define S1_STAMP(k) do { if (threadIdx.x == 0) out_coef[9 + (k)] = (float)(__builtin_readcyclecounter() - s1_t0); } while (0)
@@ -250,33 +253,7 @@ extern "C" int sda_step1d_prologue(const float* table, int row_len, int64_t* ist
     return sda_launch_status();
 }
 
-// ---- Philox4x32-10 + Box-Muller exactly as noise.hip (the same counters give the same z as sda_randn_rows)
-#define PHILOX_M0 0xD2511F53u
-#define PHILOX_M1 0xCD9E8D57u
-#define PHILOX_W0 0x9E3779B9u
-#define PHILOX_W1 0xBB67AE85u
-
-__device__ __forceinline__ void s1_philox(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1, uint32_t (&o)[4]) {
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const uint64_t p0 = (uint64_t)PHILOX_M0 * c0, p1 = (uint64_t)PHILOX_M1 * c2;
-        const uint32_t hi0 = (uint32_t)(p0 >> 32), lo0 = (uint32_t)p0, hi1 = (uint32_t)(p1 >> 32), lo1 = (uint32_t)p1;
-        const uint32_t n0 = hi1 ^ c1 ^ k0, n2 = hi0 ^ c3 ^ k1;
-        c0 = n0; c1 = lo1; c2 = n2; c3 = lo0;
-        k0 += PHILOX_W0; k1 += PHILOX_W1;
-    }
-    o[0] = c0; o[1] = c1; o[2] = c2; o[3] = c3;
-}
-
-__device__ __forceinline__ void s1_box_muller(uint32_t a, uint32_t b, float& z0, float& z1) {
-    const float u1 = ((float)(a >> 8) + 0.5f) * (1.0f / 16777216.0f);
-    const float u2 = ((float)(b >> 8) + 0.5f) * (1.0f / 16777216.0f);
-    const float r = sqrtf(-2.0f * logf(u1));
-    float s, c;
-    sincosf(6.28318530717958647692f * u2, &s, &c);
-    z0 = r * c; z1 = r * s;
-}
-
+// (row-keyed noise: philox.hpp's counter of sda_randn_rows -- the same counters give the same z)
 // grid = (blocks, b): block row b updates sample b; a thread owns quads (4 consecutive elements) of the sample
 __global__ __launch_bounds__(256) void pc_correct_keyed_kernel(float* __restrict__ x, const float* __restrict__ eps, int64_t per_sample,
                                                                const float* __restrict__ partial, int nchunk, float tau, float sigma,
@@ -287,24 +264,22 @@ __global__ __launch_bounds__(256) void pc_correct_keyed_kernel(float* __restrict
     const int64_t draw = draw_dev[0] * mul + add;
     float tot = 0.f;
     for (int j = 0; j < nchunk; ++j) tot += partial[(int64_t)b * nchunk + j];
-    const float delta = tau / (tot / (float)per_sample);
-    const float sq = sqrtf(2.0f * delta);
+    float delta, sq;
+    sda_langevin_step(tot, per_sample, tau, delta, sq);
     const int64_t base = (int64_t)b * per_sample;
     const int64_t quads = (per_sample + 3) >> 2;
     const uint64_t grow = (uint64_t)(row0 + b);
     for (int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x; q < quads; q += (int64_t)gridDim.x * 256) {
-        uint32_t w[4];
-        s1_philox((uint32_t)q, (uint32_t)grow, (uint32_t)draw,
-                  (uint32_t)((uint64_t)draw >> 32) ^ ((uint32_t)((uint64_t)q >> 32) << 16) ^ ((uint32_t)(grow >> 32) << 24), k0, k1, w);
+        const philox4 w = philox_noise_words(q, grow, draw, k0, k1);
         float z[4];
-        s1_box_muller(w[0], w[1], z[0], z[1]);
-        s1_box_muller(w[2], w[3], z[2], z[3]);
+        box_muller(w.v[0], w.v[1], z[0], z[1]);
+        box_muller(w.v[2], w.v[3], z[2], z[3]);
         const int64_t left = per_sample - 4 * q;
 #pragma unroll
         for (int e = 0; e < 4; ++e)
             if (e < left) {
                 const int64_t o = base + 4 * q + e;
-                x[o] = x[o] - (delta * eps[o] + sq * z[e]) * sigma;
+                x[o] = sda_langevin_correct(x[o], eps[o], z[e], delta, sq, sigma);
             }
     }
 }
@@ -323,7 +298,7 @@ extern "C" int sda_pc_correct_keyed(float* x, const float* eps, int b, int64_t p
 // ---------------------------------------------------------------------------------------------------------------------------
 // The tail of a fused guided evaluation of a LOCAL score network (sda_mlp_fwd_win / sda_mlp_bwd_win): the overlapping-window sum
 // of the input gradient (`unfold`'s adjoint, sda/score.py:146-153 -- the one place overlaps add), the estimator's affine part, the
-// guided score eps - (sigma/mu)(ghat - sigma J^T ghat) (score.py:394-396) and, by mode, what sda_net1d_bwd_fused's epilogue does:
+// guided score eps - (sigma/mu)(ghat - sigma J^T ghat) (score.py:394-396) and, by mode, what sda_net1d_bwd_fused's epilogue does (guide.hpp):
 // 0 write it; 1 x <- r x + c1 . in place; 2 write it and the trajectory's sum of squares into partial[b] (one chunk per sample).
 // One workgroup per trajectory (L x C elements: 195 for the Lorenz job).  A window is at most 32 values; gwin is [rows][16] for windows of at
 // most 16 values and [rows][32] above.
@@ -334,11 +309,8 @@ __global__ __launch_bounds__(256) void mc_finish_kernel(const float* __restrict_
     __shared__ float wsum[4];
     const int b = blockIdx.x, L = nw + 2 * k, per = L * c;
     const int gld = (2 * k + 1) * c <= 16 ? 16 : 32;       // gwin's row stride: as sda_mlp_bwd_win wrote it (one D fragment per row, or two)
-    const float mu = coef[0], sg = coef[1];
-    const float cx = cx0 + cx1 * sg, kk = sg / mu;
-    const bool bare = cx0 == 0.f && cx1 == 0.f;
-    float pr = 0.f, pc1 = 0.f;
-    if (mode == 1) { pr = step_coef[0]; pc1 = step_coef[1]; }
+    const SdaGuide g = sda_guide(coef[0], coef[1], 0.f, 0.f, cx0, cx1, 1.f);      // (cn: sda_mlp_bwd_win has applied it)
+    const SdaGuideTail tail = sda_guide_tail(mode, step_coef);
     float acc = 0.f;
     for (int e = threadIdx.x; e < per; e += 256) {
         const int l = e / c, ch = e - l * c;
@@ -349,10 +321,7 @@ __global__ __launch_bounds__(256) void mc_finish_kernel(const float* __restrict_
         }
         const int64_t o = (int64_t)b * per + e;
         const float gv = ghat[o];
-        const float vj = bare ? gx : (gv * cx) + gx;
-        const float ov = eps[o] - kk * (gv - sg * vj);
-        if (mode == 1) xs[o] = pr * xs[o] + pc1 * ov;
-        else { out[o] = ov; acc += ov * ov; }
+        tail.put(g.score(eps[o], gv, g.vjp_of(gv, gx)), out + o, xs + o, acc);
     }
     if (mode == 2) {
         acc = sda_wave_sum(acc);

@@ -52,33 +52,88 @@ def _slice3(sl: slice, n: int):
     return a, c, min(b, n)
 
 
-class Fused1D:
+class _Fused:
+    """What the two planners share: the buffers of one (GaussianScore, batch shape), the step prologue, the observation fields of a forward
+    descriptor and the one-call evaluation.  A subclass adds its saves, its descriptors and ``forward`` / ``backward``."""
+
+    def __init__(self, gs, inner, affine, x: Tensor, pos, chan, y_sn: int, sched, embedding, mod_width: int):
+        self.gs, self.inner, self.affine = gs, inner, affine
+        self.pos, self.chan, self.y_sn, self.sched = pos, chan, y_sn, sched
+        self.embedding = embedding
+        self.shape = tuple(x.shape)
+        self.dev = dev = x.device
+        self.eps = torch.empty(self.shape, device=dev, dtype=torch.float32)
+        self.ghat = torch.empty_like(self.eps)
+        self.out = torch.empty_like(self.eps)
+        self.coef = torch.zeros(COEF_LEN, device=dev, dtype=torch.float32)
+        self.step_i = torch.zeros(1, device=dev, dtype=torch.int64)
+        self.mod = torch.empty(2, mod_width, device=dev, dtype=torch.float32)       # what the prologue writes for both evaluation times
+
+    def _partials(self, ptiles: int):
+        """The fixed slots of the Langevin sums of squares (backward mode 2): ``ptiles`` per sample."""
+        self.ptiles = ptiles
+        self.partial = torch.empty(self.shape[0], ptiles, device=self.dev, dtype=torch.float32)
+
+    def _projection(self):
+        """The (weight, bias) that turn the time embedding into ``mod``, or (None, None): ``mod`` is the embedding itself."""
+        return None, None
+
+    # ------------------------------------------------------------------ launches
+    def _prologue(self, table: Optional[Tensor], istep: Optional[Tensor], t: Optional[Tensor], nt: int):
+        emb = self.embedding
+        w0, b0, w2, b2 = emb[0].weight.detach(), emb[0].bias.detach(), emb[2].weight.detach(), emb[2].bias.detach()
+        wp, bp = self._projection()
+        ak, eta, kk, sk = self.sched
+        ops._dev(w0, b0, w2, b2, wp, bp, emb.freqs, t)
+        _lib.check(_lib.load().sda_step1d_prologue(
+            ops._ptr(table), 0 if table is None else table.shape[1], ops._ptr(istep), ops._ptr(t), nt, ak, eta, kk, sk,
+            emb.freqs.data_ptr(), emb.freqs.numel(), w0.data_ptr(), b0.data_ptr(), w0.shape[0], w2.data_ptr(), b2.data_ptr(), w2.shape[0],
+            ops._ptr(wp), ops._ptr(bp), 0 if wp is None else wp.shape[0], self.coef.data_ptr(), self.step_i.data_ptr(), self.mod.data_ptr(),
+            ops._stream()), 'sda_step1d_prologue')
+
+    def prologue_step(self, table: Tensor, istep: Tensor):
+        """This step's scalars and both evaluations' modulation vectors from the device schedule table; advances ``istep``."""
+        self._prologue(table, istep, None, 2)
+
+    def prologue_eval(self, t: Tensor):
+        self._prologue(None, None, t.reshape(1), 1)
+
+    def _observe(self, f):
+        """The observation of a forward launch, into either descriptor (sda_net1d_fuse and sda_mlp_win name these fields alike)."""
+        f.y, f.y_sn = self.gs.y.data_ptr(), self.y_sn
+        f.p_start, f.p_step, f.p_stop = self.pos
+        f.c_start, f.c_step, f.c_stop = self.chan
+        f.std, f.gamma = self.gs._scalars
+
+    # ------------------------------------------------------------------ one guided evaluation (GaussianScore.forward)
+    def evaluate(self, x: Tensor, t: Tensor) -> Tensor:
+        out = torch.empty_like(self.eps)
+        self.prologue_eval(t)
+        self.forward(x, 0)
+        self.backward(0, 0, out=out)
+        return out
+
+
+class Fused1D(_Fused):
     """Buffers and descriptors of the fused evaluation for one (GaussianScore, batch shape)."""
 
     def __init__(self, gs, inner, affine, engine, plan1d, x: Tensor, pos, chan, y_sn: int, sched):
-        self.gs, self.inner, self.affine, self.engine, self.plan1d = gs, inner, affine, engine, plan1d
-        self.pos, self.chan, self.y_sn, self.sched = pos, chan, y_sn, sched
-        B, L, C = x.shape
-        self.shape = (B, L, C)
-        dev = x.device
-        self.dev = dev
-        lev, blocks = plan1d['lev'], plan1d['blocks']
-        nb = len(blocks)
-        self.eps = torch.empty(B, L, C, device=dev, dtype=torch.float32)
-        self.ghat = torch.empty_like(self.eps)
-        self.out = torch.empty_like(self.eps)
-        self.a_s = torch.empty(nb, B, lev.C, L, device=dev, dtype=torch.float32)
+        super().__init__(gs, inner, affine, x, pos, chan, y_sn, sched, inner.score.embedding, engine.mod_total)
+        self.engine, self.plan1d = engine, plan1d
+        B, L, C = self.shape
+        lev, nb = plan1d['lev'], len(plan1d['blocks'])
+        self.a_s = torch.empty(nb, B, lev.C, L, device=self.dev, dtype=torch.float32)
         self.z_s = torch.empty_like(self.a_s)
-        self.m_s = torch.empty(nb, B, L, device=dev, dtype=torch.float32)
+        self.m_s = torch.empty(nb, B, L, device=self.dev, dtype=torch.float32)
         self.r_s = torch.empty_like(self.m_s)
-        self.coef = torch.zeros(COEF_LEN, device=dev, dtype=torch.float32)
-        self.step_i = torch.zeros(1, device=dev, dtype=torch.int64)
-        self.mod = torch.empty(2, engine.mod_total, device=dev, dtype=torch.float32)
         d, _ = self._desc(False, 0)
-        self.ptiles = _lib.load().sda_net1d_tiles(ctypes.byref(d))
-        if self.ptiles <= 0:
+        ptiles = _lib.load().sda_net1d_tiles(ctypes.byref(d))
+        if ptiles <= 0:
             raise _lib.SdaHipError('fused1d: the whole-net kernel declined a shape its planner accepted')
-        self.partial = torch.empty(B, self.ptiles, device=dev, dtype=torch.float32)
+        self._partials(ptiles)
+
+    def _projection(self):
+        return self.engine.projection()
 
     # ------------------------------------------------------------------ descriptors
     def _desc(self, backward: bool, k: int):
@@ -98,36 +153,11 @@ class Fused1D:
         f.coef = self.coef.data_ptr() + 8 * k
         return f
 
-    # ------------------------------------------------------------------ launches
-    def _prologue(self, table: Optional[Tensor], istep: Optional[Tensor], t: Optional[Tensor], nt: int):
-        emb = self.inner.score.embedding
-        w0, b0, w2, b2 = emb[0].weight.detach(), emb[0].bias.detach(), emb[2].weight.detach(), emb[2].bias.detach()
-        wp, bp = self.engine.projection()
-        ak, eta, kk, sk = self.sched
-        ops._dev(w0, b0, w2, b2, wp, bp, emb.freqs, t)
-        _lib.check(_lib.load().sda_step1d_prologue(
-            ops._ptr(table), 0 if table is None else table.shape[1], ops._ptr(istep), ops._ptr(t), nt, ak, eta, kk, sk,
-            emb.freqs.data_ptr(), emb.freqs.numel(), w0.data_ptr(), b0.data_ptr(), w0.shape[0], w2.data_ptr(), b2.data_ptr(), w2.shape[0],
-            wp.data_ptr(), bp.data_ptr(), wp.shape[0], self.coef.data_ptr(), self.step_i.data_ptr(), self.mod.data_ptr(), ops._stream()),
-            'sda_step1d_prologue')
-
-    def prologue_step(self, table: Tensor, istep: Tensor):
-        """This step's scalars and both evaluations' modulation vectors from the device schedule table; advances ``istep``."""
-        self._prologue(table, istep, None, 2)
-
-    def prologue_eval(self, t: Tensor):
-        self._prologue(None, None, t.reshape(1), 1)
-
     def forward(self, x: Tensor, k: int):
         d, keep = self._desc(False, k)
         d.x, d.out = x.data_ptr(), self.eps.data_ptr()
         f = self._fuse(k)
-        y = self.gs.y
-        std, gamma = self.gs._scalars
-        f.y, f.y_sn = y.data_ptr(), self.y_sn
-        f.p_start, f.p_step, f.p_stop = self.pos
-        f.c_start, f.c_step, f.c_stop = self.chan
-        f.std, f.gamma = std, gamma
+        self._observe(f)
         f.ghat = self.ghat.data_ptr()
         ops.net1d_launch_fused(d, f, False)
 
@@ -144,66 +174,32 @@ class Fused1D:
             f.partial, f.partial_stride = self.partial.data_ptr(), self.ptiles
         ops.net1d_launch_fused(d, f, True)
 
-    # ------------------------------------------------------------------ one guided evaluation (GaussianScore.forward)
-    def evaluate(self, x: Tensor, t: Tensor) -> Tensor:
-        out = torch.empty_like(self.eps)
-        self.prologue_eval(t)
-        self.forward(x, 0)
-        self.backward(0, 0, out=out)
-        return out
 
-
-class FusedLocal:
+class FusedLocal(_Fused):
     """The same interface as :class:`Fused1D` for a LOCAL score network -- ``MCScoreNet`` over a ``ScoreNet`` kernel (sda/score.py:134-164,
     53-63; experiments/lorenz/utils.py:45-59): per evaluation ``sda_mlp_fwd_win`` (window gather + time embedding in the loader, ``fold`` + eps +
     likelihood cotangent in the epilogue), ``sda_mlp_bwd_win`` (fold's adjoint in the loader) and ``sda_mc_finish`` (overlapping-window sum, guided
     score, predictor update / Langevin sum of squares)."""
 
     def __init__(self, gs, inner, affine, mplan, x: Tensor, pos, chan, y_sn: int, sched):
-        from . import mlp
-        self.gs, self.inner, self.affine, self.mplan = gs, inner, affine, mplan
-        self.pos, self.chan, self.y_sn, self.sched = pos, chan, y_sn, sched
-        B, L, C = x.shape
-        self.shape = (B, L, C)
+        emb = inner.kernel.embedding
+        self.emb_n = emb[2].weight.shape[0]
+        super().__init__(gs, inner, affine, x, pos, chan, y_sn, sched, emb, self.emb_n)      # (mod: the time embedding of both evaluation times)
+        self.mplan = mplan
+        B, L, C = self.shape
         self.k = inner.order
         self.nw = L - 2 * self.k
         self.rows = B * self.nw
-        dev = x.device
-        self.eps = torch.empty(B, L, C, device=dev, dtype=torch.float32)
-        self.ghat = torch.empty_like(self.eps)
-        self.out = torch.empty_like(self.eps)
         # (the row stride sda_mlp_bwd_win and sda_mc_finish derive from the window: one 16-value fragment per row, or two)
-        self.gwin = torch.empty(self.rows, 16 if (2 * self.k + 1) * C <= 16 else 32, device=dev, dtype=torch.float32)
+        self.gwin = torch.empty(self.rows, 16 if (2 * self.k + 1) * C <= 16 else 32, device=self.dev, dtype=torch.float32)
         nres = max(mplan.nres, 1)
-        self.a_s = torch.empty(nres, self.rows, mplan.save_ld, device=dev, dtype=torch.float32)
+        self.a_s = torch.empty(nres, self.rows, mplan.save_ld, device=self.dev, dtype=torch.float32)
         self.z_s = torch.empty_like(self.a_s)
-        self.m_s = torch.empty(nres, self.rows, device=dev, dtype=torch.float32)
+        self.m_s = torch.empty(nres, self.rows, device=self.dev, dtype=torch.float32)
         self.r_s = torch.empty_like(self.m_s)
-        self.coef = torch.zeros(COEF_LEN, device=dev, dtype=torch.float32)
-        self.step_i = torch.zeros(1, device=dev, dtype=torch.int64)
-        self.emb_n = inner.kernel.embedding[2].weight.shape[0]
-        self.mod = torch.empty(2, self.emb_n, device=dev, dtype=torch.float32)        # the time embedding of both evaluation times
-        self.ptiles = 1
-        self.partial = torch.empty(B, 1, device=dev, dtype=torch.float32)
-
-    def _prologue(self, table, istep, t, nt):
-        emb = self.inner.kernel.embedding
-        w0, b0, w2, b2 = emb[0].weight.detach(), emb[0].bias.detach(), emb[2].weight.detach(), emb[2].bias.detach()
-        ak, eta, kk, sk = self.sched
-        ops._dev(w0, b0, w2, b2, emb.freqs, t)
-        _lib.check(_lib.load().sda_step1d_prologue(
-            ops._ptr(table), 0 if table is None else table.shape[1], ops._ptr(istep), ops._ptr(t), nt, ak, eta, kk, sk,
-            emb.freqs.data_ptr(), emb.freqs.numel(), w0.data_ptr(), b0.data_ptr(), w0.shape[0], w2.data_ptr(), b2.data_ptr(), w2.shape[0],
-            None, None, 0, self.coef.data_ptr(), self.step_i.data_ptr(), self.mod.data_ptr(), ops._stream()), 'sda_step1d_prologue')
-
-    def prologue_step(self, table: Tensor, istep: Tensor):
-        self._prologue(table, istep, None, 2)
-
-    def prologue_eval(self, t: Tensor):
-        self._prologue(None, None, t.reshape(1), 1)
+        self._partials(1)
 
     def _desc(self, backward: bool):
-        from . import mlp
         d = self.mplan.desc(self.rows, backward)
         d.a_save, d.z_save, d.save_stride, d.save_ld = self.a_s.data_ptr(), self.z_s.data_ptr(), self.rows * self.mplan.save_ld, self.mplan.save_ld
         d.mean_save, d.rstd_save, d.stat_stride = self.m_s.data_ptr(), self.r_s.data_ptr(), self.rows
@@ -220,12 +216,8 @@ class FusedLocal:
 
     def forward(self, x: Tensor, k: int):
         d, w = self._desc(False), self._win(k)
-        std, gamma = self.gs._scalars
         w.x, w.emb = x.data_ptr(), self.mod.data_ptr() + 4 * self.emb_n * k
-        w.y, w.y_sn = self.gs.y.data_ptr(), self.y_sn
-        w.p_start, w.p_step, w.p_stop = self.pos
-        w.c_start, w.c_step, w.c_stop = self.chan
-        w.std, w.gamma = std, gamma
+        self._observe(w)
         w.eps = self.eps.data_ptr()
         ops.mlp_launch_win(d, w, False)
 
@@ -238,12 +230,20 @@ class FusedLocal:
                       mode, None if mode == 1 else (self.out if out is None else out), x if mode == 1 else None,
                       self.coef.data_ptr() + 16, self.partial if mode == 2 else None)
 
-    def evaluate(self, x: Tensor, t: Tensor) -> Tensor:
-        out = torch.empty_like(self.eps)
-        self.prologue_eval(t)
-        self.forward(x, 0)
-        self.backward(0, 0, out=out)
-        return out
+
+def _embedding_fits(emb) -> bool:
+    """sda_step1d_prologue's limits (csrc/step1d.hip: S1_MAX_FEAT, S1_MAX_HIDDEN, S1_MAX_E)."""
+    return emb.freqs.numel() * 2 <= 128 and emb[0].weight.shape[0] <= 1024 and emb[2].weight.shape[0] <= 256
+
+
+def _cached(gs, key, make):
+    """The planner object ``gs`` keeps for ``key``; ``make()`` builds (and replaces) it when the key changed."""
+    hit = getattr(gs, '_fused1d_cache', None)
+    if hit is not None and hit[0] == key:
+        return hit[1]
+    fz = make()
+    object.__setattr__(gs, '_fused1d_cache', (key, fz))
+    return fz
 
 
 def _plan_local(gs, m, affine, x: Tensor, pos, chan, y_sn: int, sched, key_extra):
@@ -262,15 +262,9 @@ def _plan_local(gs, m, affine, x: Tensor, pos, chan, y_sn: int, sched, key_extra
     emb = kern.embedding
     if mplan is None or mplan.gemms[0][1] != wc + emb[2].weight.shape[0] or mplan.gemms[-1][2] != wc:
         return None
-    if emb.freqs.numel() * 2 > 128 or emb[0].weight.shape[0] > 1024 or emb[2].weight.shape[0] > 256:
+    if not _embedding_fits(emb):
         return None
-    key = key_extra + (id(mplan),)
-    hit = getattr(gs, '_fused1d_cache', None)
-    if hit is not None and hit[0] == key:
-        return hit[1]
-    fz = FusedLocal(gs, m, affine, mplan, x, pos, chan, y_sn, sched)
-    object.__setattr__(gs, '_fused1d_cache', (key, fz))
-    return fz
+    return _cached(gs, key_extra + (id(mplan),), lambda: FusedLocal(gs, m, affine, mplan, x, pos, chan, y_sn, sched))
 
 
 def plan(gs, x: Tensor, t, c):
@@ -332,15 +326,8 @@ def plan(gs, x: Tensor, t, c):
     p1 = engine.net1d_plan(src)
     if p1 is None:
         return None
-    emb = score.embedding
-    if emb.freqs.numel() * 2 > 128 or emb[0].weight.shape[0] > 1024 or emb[2].weight.shape[0] > 256:
+    if not _embedding_fits(score.embedding):
         return None
-    key = key0 + (id(engine), len(p1['blocks']))
-    hit = getattr(gs, '_fused1d_cache', None)
-    if hit is not None and hit[0] == key:
-        fz = hit[1]
-        fz.plan1d = p1
-        return fz
-    fz = Fused1D(gs, m, affine, engine, p1, x, pos, chan, y_sn, sched)
-    object.__setattr__(gs, '_fused1d_cache', (key, fz))
+    fz = _cached(gs, key0 + (id(engine), len(p1['blocks'])), lambda: Fused1D(gs, m, affine, engine, p1, x, pos, chan, y_sn, sched))
+    fz.plan1d = p1                 # (a hit: this call's plan)
     return fz

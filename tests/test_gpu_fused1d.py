@@ -289,3 +289,75 @@ def test_fused_local_pc_steps_equal_general_path_eager_and_graph(dev, B, L, corr
     fg = run(True, True)
     assert_close(fg.cpu(), fe.cpu(), 1e-6, what='fused graph replay vs fused eager (local net)')
     monkeypatch.setattr(fused1d, 'ENABLED', True)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# The epilogue arithmetic itself (csrc/guide.hpp).  The tests above compare the fused and the general path at 1e-6 because the network
+# between them differs; the guidance, the modes of the VJP's tail and the predictor update are the SAME functions on both sides and
+# compare exactly.
+
+def _forward_plan(dev, case, local=False):
+    """A CASES / LOCAL_CASES entry planned and run through ``prologue_eval`` + ``forward``: (fz, gs, x)."""
+    from sda_amd import fused1d, observe as Ob
+    from sda_amd.score import GaussianScore
+    if local:
+        B, L, C, window, sl, per_sample, affine, width = case
+        net, inner = _build_local(dev, C, window, affine, width=width)
+    else:
+        B, L, C, sl, per_sample, affine = case
+        net, inner = _build(dev, C, affine)
+    torch.manual_seed(71)
+    x = torch.randn(B, L, C, device=dev)
+    t = torch.tensor(0.37, device=dev)
+    A = Ob.Subsample(sl)
+    oshape = A._osize(x.shape)
+    y = torch.randn(oshape if per_sample else oshape[1:])
+    gs = GaussianScore(y, A=A, std=0.3, sde=inner, gamma=3e-2).to(dev)
+    fz = fused1d.plan(gs, x, t, None)
+    assert isinstance(fz, fused1d.FusedLocal if local else fused1d.Fused1D)
+    fz.prologue_eval(t)
+    fz.forward(x, 0)
+    return fz, gs, x
+
+
+def assert_forward_epilogue_is_the_guidance_kernel(fz, gs, x):
+    """ghat of the fused forward == sda_obs_subsample_guidance on the eps it wrote, with the same device {mu, sigma}."""
+    std, gamma = gs._scalars
+    ref = gs.A.gaussian_guidance(x, fz.eps, gs.y, std, gamma, fz.coef[0], fz.coef[1])       # (adjacent 0-dim views: travels as coef_dev)
+    assert ref is not None and ref.abs().sum().item() > 0
+    assert torch.equal(fz.ghat, ref)
+
+
+SMALL_LOCAL = LOCAL_CASES[3]                                                  # (1, 5, 3): one window per trajectory -- the smallest entry
+EPILOGUE_CASES = [(CASES[2], False), (CASES[3], False), (CASES[4], False), (CASES[5], False), (SMALL_LOCAL, True)]
+
+
+@pytest.mark.parametrize('case,local', EPILOGUE_CASES)
+def test_fused_forward_epilogue_is_the_unfused_guidance_kernel_bit_for_bit(dev, case, local):
+    assert_forward_epilogue_is_the_guidance_kernel(*_forward_plan(dev, case, local))
+
+
+@pytest.mark.parametrize('case,local', [(CASES[2], False), (CASES[4], False), (SMALL_LOCAL, True)])
+def test_fused_backward_modes_agree_with_each_other_and_with_pc_predict(dev, case, local):
+    """Mode 0 and mode 2 write the same guided score; mode 1 is sda_pc_predict of it; mode 2's fixed-slot sums add up to the sample's sum
+    of squares within the worst case of a positive fp32 sum of n = L C terms, n 2^-24 relative."""
+    from sda_amd import ops
+    fz, gs, x = _forward_plan(dev, case, local)
+    B, L, C = x.shape
+    fz.backward(0, 0)
+    out0 = fz.out.clone()
+    fz.backward(2, 0)
+    assert torch.equal(out0, fz.out)
+    want = out0.double().pow(2).sum((1, 2))
+    got = fz.partial.sum(1).double()
+    rel = ((got - want).abs() / want).max().item()
+    n = L * C
+    print(f'mode 2 sum of squares, n = {n}: relative error {rel:.3e}, bound {n * 2.0 ** -24:.3e}')
+    assert rel <= n * 2.0 ** -24
+    step_coef = fz.coef[4:6]
+    step_coef.copy_(torch.tensor([0.97, 0.013]))
+    x1 = x.clone()
+    fz.backward(1, 0, x=x1)
+    ref = x.clone()
+    ops.pc_predict(ref, out0, 0.0, 0.0, coef_dev=step_coef)
+    assert torch.equal(x1, ref) and not torch.equal(x1, x)

@@ -181,3 +181,23 @@ def test_gwin_row_stride_follows_the_window(dev, window, stride):
     fz = fused1d.plan(gs, x, torch.tensor(0.5, device=dev), None)
     assert isinstance(fz, fused1d.FusedLocal)
     assert fz.gwin.shape == (B * (L - window + 1), stride)
+
+
+def test_fused_forward_epilogue_window32_is_the_unfused_guidance_kernel_bit_for_bit(dev):
+    """The two-fragment windows' epilogue (csrc/guide.hpp through ml_win_fold<2>): ghat == sda_obs_subsample_guidance on the eps it wrote."""
+    from sda_amd import fused1d, observe as Ob
+    from sda_amd.score import GaussianScore
+    B, L, C, window, sl, per_sample, affine, width = CASES[3]                 # two windows, both edge windows; offsets and stops
+    net, inner = _build_local(dev, C, window, affine, width=width)
+    torch.manual_seed(91)
+    x = torch.randn(B, L, C, device=dev)
+    t = torch.tensor(0.41, device=dev)
+    A = Ob.Subsample(sl)
+    gs = GaussianScore(torch.randn(A._osize(x.shape)), A=A, std=0.3, sde=inner, gamma=3e-2).to(dev)
+    fz = fused1d.plan(gs, x, t, None)
+    assert isinstance(fz, fused1d.FusedLocal) and fz.gwin.shape[1] == 32
+    fz.prologue_eval(t)
+    fz.forward(x, 0)
+    ref = A.gaussian_guidance(x, fz.eps, gs.y, 0.3, 3e-2, fz.coef[0], fz.coef[1])       # (adjacent 0-dim views: travels as coef_dev)
+    assert ref is not None and ref.abs().sum().item() > 0
+    assert torch.equal(fz.ghat, ref)
