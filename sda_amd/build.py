@@ -20,7 +20,7 @@ SOURCES = ['conv_igemm.hip', 'conv_wino4.hip', 'conv_small1d.hip', 'conv_few.hip
 HIPCC = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
 # extra compile flags (e.g. SDA_EXTRA_HIPCC_FLAGS=-DSDA_W4_VARIANTS builds the tuning variants tools/wino4_check.py compares)
 EXTRA_FLAGS = os.environ.get('SDA_EXTRA_HIPCC_FLAGS', '').split()
-EMU_SOURCES = ['conv_igemm.hip', 'conv_wgrad.hip', 'conv_wgrad3.hip', 'chain.hip', 'mlp_train.hip', 'net1d_train.hip', 'optim.hip', 'assign.hip']       # host replays of the tile algorithms, the chain arithmetic, the optimizer step and the auction (libsda_emu.so)
+EMU_SOURCES = ['conv_igemm.hip', 'conv_wino4.hip', 'conv_h2.hip', 'conv_wgrad.hip', 'conv_wgrad3.hip', 'chain.hip', 'mlp_train.hip', 'net1d_train.hip', 'optim.hip', 'assign.hip']       # host replays of the tile algorithms, the Winograd / f16x2 kernels' pick functions, the chain arithmetic, the optimizer step and the auction (libsda_emu.so)
 CONV_PARTS = 4                                       # see SDA_CONV_PART in csrc/conv_igemm.hip
 
 

@@ -43,6 +43,7 @@
 // at 1.45 GHz (profiles/r05_h2_pmc_v7_384ch.txt).  Algorithmic bytes: x once per 96-cout tile x 1.27 (halo), out once.
 #include "sda_common.hpp"
 #include <stdlib.h>
+#include <string.h>
 #include <type_traits>
 
 typedef _Float16 h2_h8 __attribute__((ext_vector_type(8)));
@@ -91,6 +92,7 @@ struct h2_args {
     int stagger;                // (tooling) start delay of workgroup slot s: (s & 3) * stagger * 8 128 cycles
 };
 
+#ifndef SDA_HOST_EMU
 // barrier of the 4 + 4 waves.  Not __syncthreads(): that also drains vmcnt, and a consumer's epilogue stores (gfx9 counts stores in
 // vmcnt) would be waited for at the next tile's first stage.  Consumers wait for their LDS reads only; producers also for their
 // loads / LDS-DMA (hipcc does not count LDS-DMA: the wait is ours).
@@ -645,106 +647,137 @@ extern "C" int sda_absmax(const float* x, int64_t numel, float* amax, void* stre
     return sda_launch_status();
 }
 
-// ------------------------------------------------------------------------------------------------------------------- launcher
-static bool h2_ok(const sda_conv_desc* d) {
-    if (!d || !d->x || !d->out || !d->w_h2) return false;
+#endif  // !SDA_HOST_EMU
+
+// ---------------------------------------------------------------- which instantiation serves a launch (host; no device, no environment)
+// The launch's MODE (see the kernel) if a kernel serves it, else -1.  The mode is decoded here, once.
+static int h2_ok(const sda_conv_desc* d) {
+    if (!d || !d->x || !d->out || !d->w_h2) return -1;
     const bool up = d->up_h == 2 && d->up_w == 2;                  // MODE 1 (w_h2 = sda_pack_conv_weight_h2_up's packing)
     const bool pool = d->pool_h == 2 && d->pool_w == 2;            // MODE 2 (sda_pack_conv_weight_h2_rows of the class-major transpose)
     const bool zins = d->zins_h == 2 && d->zins_w == 2;            // MODE 3 (the four classes' sda_pack_conv_weight_h2_rows packings, back to back)
     const bool s2 = d->stride_h == 2 && d->stride_w == 2;          // MODE 4 (the same, forward orientation)
-    if (d->kh != 3 || d->kw != 3 || d->explicit_pad || (int)up + (int)pool + (int)zins + (int)s2 > 1) return false;
+    if (d->kh != 3 || d->kw != 3 || d->explicit_pad || (int)up + (int)pool + (int)zins + (int)s2 > 1) return -1;
     if (!(s2 || (d->stride_h == 1 && d->stride_w == 1)) || !(up || (d->up_h == 1 && d->up_w == 1)) ||
         !(zins || (d->zins_h == 1 && d->zins_w == 1)) || !(pool || (d->pool_h <= 1 && d->pool_w <= 1)))
-        return false;
-    if (d->cctx != 0 || d->n_inner != 1 || d->x_n_off != 0) return false;
+        return -1;
+    if (d->cctx != 0 || d->n_inner != 1 || d->x_n_off != 0) return -1;
     const int ts = (pool || s2) ? 2 * H2_TS : H2_TS;               // source pixels per tile side
     const int mb = d->cout > 0 ? H2_MB_OF(d->cout) : 0;
-    if (d->cx % H2_KQ || !mb || d->hs % ts || d->ws % ts) return false;
-    if (s2 ? (2 * d->ho != d->hs || 2 * d->wo != d->ws) : (d->ho != ((up || zins) ? 2 : 1) * d->hs || d->wo != ((up || zins) ? 2 : 1) * d->ws)) return false;
-    if (up && (d->dact_z || d->act_in != SDA_ACT_NONE)) return false;
-    if (pool && (d->dact_z || d->res || d->bias || d->ln_mean || d->act_in != SDA_ACT_NONE)) return false;
-    if ((zins || s2) && (d->dact_z || d->ln_mean || d->act_in != SDA_ACT_NONE)) return false;
-    if (d->out_sn || d->out_sc || d->out_sy || d->out_sx) return false;
-    if ((d->ln_mean == nullptr) != (d->ln_rstd == nullptr)) return false;
-    if (d->mod && !d->ln_mean) return false;
-    if (d->ln_mean && d->act_in != SDA_ACT_NONE) return false;
-    if (d->act_in != SDA_ACT_NONE && d->act_in != SDA_ACT_SILU) return false;
-    if (d->dact_z && d->act_d != SDA_ACT_SILU) return false;
-    if (d->dact_z && d->res) return false;
+    if (d->cx % H2_KQ || !mb || d->hs % ts || d->ws % ts) return -1;
+    if (s2 ? (2 * d->ho != d->hs || 2 * d->wo != d->ws) : (d->ho != ((up || zins) ? 2 : 1) * d->hs || d->wo != ((up || zins) ? 2 : 1) * d->ws)) return -1;
+    if (up && (d->dact_z || d->act_in != SDA_ACT_NONE)) return -1;
+    if (pool && (d->dact_z || d->res || d->bias || d->ln_mean || d->act_in != SDA_ACT_NONE)) return -1;
+    if ((zins || s2) && (d->dact_z || d->ln_mean || d->act_in != SDA_ACT_NONE)) return -1;
+    if (d->out_sn || d->out_sc || d->out_sy || d->out_sx) return -1;
+    if ((d->ln_mean == nullptr) != (d->ln_rstd == nullptr)) return -1;
+    if (d->mod && !d->ln_mean) return -1;
+    if (d->ln_mean && d->act_in != SDA_ACT_NONE) return -1;
+    if (d->act_in != SDA_ACT_NONE && d->act_in != SDA_ACT_SILU) return -1;
+    if (d->dact_z && d->act_d != SDA_ACT_SILU) return -1;
+    if (d->dact_z && d->res) return -1;
     if (d->x_sc < 0 || d->x_sy < 0 || d->x_sx < 0 ||
         (int64_t)d->cx * d->x_sc + (int64_t)d->hs * d->x_sy + (int64_t)d->ws * d->x_sx >= (1LL << 31))
-        return false;
+        return -1;
     const int64_t tiles = (int64_t)d->n * (d->hs / ts) * (d->ws / ts) * (d->cout / H2_BM_OF(mb)) * ((up || zins) ? 4 : 1);
-    return tiles >= 1 && tiles <= 0x3fffffffLL;
+    if (tiles < 1 || tiles > 0x3fffffffLL) return -1;
+    return up ? 1 : pool ? 2 : zins ? 3 : s2 ? 4 : 0;
 }
 
-extern "C" int sda_conv_h2_supported(const sda_conv_desc* d) { return h2_ok(d) ? 1 : 0; }
+struct H2Pick { int loader, mode, mb; };                           // conv_h2_kernel's template arguments (ABL: tooling builds, sda_conv_h2)
+// The shipped instantiations, each written once: H2(LOADER, MODE, MB), at the 96- and the 64-cout tile.  The block convolutions have all
+// three loaders; the tails LayerNorm or plain; the tails' VJP, the stride-2 heads' VJP and the heads themselves the plain one
+#define H2_ROWS_MB(H2, LOADER, MODE) H2(LOADER, MODE, 3) H2(LOADER, MODE, 2)
+#define H2_ROWS(H2) \
+    H2_ROWS_MB(H2, 0, 0) H2_ROWS_MB(H2, 1, 0) H2_ROWS_MB(H2, 2, 0) H2_ROWS_MB(H2, 0, 1) H2_ROWS_MB(H2, 2, 1) \
+    H2_ROWS_MB(H2, 0, 2) H2_ROWS_MB(H2, 0, 3) H2_ROWS_MB(H2, 0, 4)
+#define H2_PICK_ROW(LOADER, MODE, MB) {LOADER, MODE, MB},
 
-// one (loader, mode) kernel at the launch's cout tile (96 or 64 couts: MB = 3 / 2)
-template <int LOADER, int MODE>
-static int h2_launch(const sda_conv_desc* d, const h2_args& a, unsigned grid, int lds, int mb, hipStream_t stream) {
-    static bool set3[SDA_MAX_DEVICES], set2[SDA_MAX_DEVICES];
-    int rc;
-    if (mb == 3) {
-        if ((rc = sda_raise_dyn_lds(reinterpret_cast<const void*>(conv_h2_kernel<LOADER, MODE, 0, 3>), lds, set3)) != SDA_OK) return rc;
-        hipLaunchKernelGGL((conv_h2_kernel<LOADER, MODE, 0, 3>), dim3(grid), dim3(512), (size_t)lds, stream, *d, a);
-    } else {
-        if ((rc = sda_raise_dyn_lds(reinterpret_cast<const void*>(conv_h2_kernel<LOADER, MODE, 0, 2>), lds, set2)) != SDA_OK) return rc;
-        hipLaunchKernelGGL((conv_h2_kernel<LOADER, MODE, 0, 2>), dim3(grid), dim3(512), (size_t)lds, stream, *d, a);
-    }
+// Plans the launch (the kernel's arguments but the tooling builds' `stagger`, the grid) and names the instantiation that serves it; returns
+// what sda_conv_h2 returns short of the launch's own status.
+static int h2_pick(const sda_conv_desc* d, int cus, h2_args* a, H2Pick* p, unsigned* grid) {
+    const int mode = h2_ok(d);
+    if (mode < 0) return SDA_E_UNSUPPORTED;
+    a->w = d->w_h2;
+    a->w_scale = d->w_h2_scale;
+    a->x_amax = d->x_amax;
+    a->x_amax_static = d->x_amax_static;
+    a->out_amax = d->out_amax;
+    const bool planes = mode == 2 || mode == 4, scatter = mode == 1 || mode == 3;    // (PLANES and SCATTER of the kernel)
+    a->tiles_x = d->ws / (planes ? 2 * H2_TS : H2_TS);             // (tiles of the grid the kernel walks: the source grid, or one of its parity planes)
+    a->tiles_y = d->hs / (planes ? 2 * H2_TS : H2_TS);
+    const int mb = H2_MB_OF(d->cout);
+    a->n_ct = (d->cout / H2_BM_OF(mb)) * (scatter ? 4 : 1);
+    a->c16 = d->cx / H2_CK;
+    a->nchunk = a->c16 * (planes ? 4 : 1);
+    a->stagger = 0;
+    if (!(a->w_scale > 0.f) || (!a->x_amax && !(a->x_amax_static > 0.f))) return SDA_E_BADARG;
+    a->ntiles = (int)((int64_t)d->n * a->tiles_x * a->tiles_y * a->n_ct);
+    // persistent workgroups, one per CU (the stage buffers take the whole LDS); a multiple of 8 keeps the XCD-contiguous tile walk
+    if (cus <= 0) cus = 256;
+    *grid = (unsigned)(a->ntiles < cus ? a->ntiles : cus);
+    if (*grid >= 8) *grid &= ~7u;
+    const int loader = d->ln_mean ? 2 : (d->act_in != SDA_ACT_NONE ? 1 : 0);       // (h2_ok: never both, SiLU the only activation)
+    *p = H2Pick{loader, mode, mb};
+    return SDA_OK;
+}
+
+#ifndef SDA_HOST_EMU
+template <int LOADER, int MODE, int MB, int ABL = 0>
+static int h2_launch(const sda_conv_desc* d, const h2_args& a, unsigned grid, hipStream_t stream) {
+    static bool attr_set[SDA_MAX_DEVICES];
+    const int rc = sda_raise_dyn_lds(reinterpret_cast<const void*>(conv_h2_kernel<LOADER, MODE, ABL, MB>), H2_LDS, attr_set);
+    if (rc != SDA_OK) return rc;
+    hipLaunchKernelGGL((conv_h2_kernel<LOADER, MODE, ABL, MB>), dim3(grid), dim3(512), (size_t)H2_LDS, stream, *d, a);
     return sda_launch_status();
 }
 
+// the variant table: the rows with their launchers
+typedef int (*h2_launch_fn)(const sda_conv_desc*, const h2_args&, unsigned, hipStream_t);
+#define H2_VARIANT(LOADER, MODE, MB) {H2_PICK_ROW(LOADER, MODE, MB) h2_launch<LOADER, MODE, MB>},
+static const struct { H2Pick pick; h2_launch_fn launch; } H2_TABLE[] = {H2_ROWS(H2_VARIANT)};
+#ifdef SDA_H2_ABLATE
+// tooling builds: $SDA_H2_ABL = one of these runs the ablated form (see ABL at the kernel) of the plain 96-cout MODE 0 kernel in place of
+// any plain-loader 96-cout launch
+#define H2_ABL_ROWS(H2A) H2A(1) H2A(2) H2A(3) H2A(4) H2A(7) H2A(8) H2A(11) H2A(15)
+#define H2_ABL_VARIANT(ABL) {ABL, h2_launch<0, 0, 3, ABL>},
+static const struct { int abl; h2_launch_fn launch; } H2_ABL_TABLE[] = {H2_ABL_ROWS(H2_ABL_VARIANT)};
+#endif
+
+extern "C" int sda_conv_h2_supported(const sda_conv_desc* d) { return h2_ok(d) >= 0 ? 1 : 0; }
+
 extern "C" int sda_conv_h2(const sda_conv_desc* d, void* stream) {
-    if (!h2_ok(d)) return SDA_E_UNSUPPORTED;
-    h2_args a;
-    a.w = d->w_h2;
-    a.w_scale = d->w_h2_scale;
-    a.x_amax = d->x_amax;
-    a.x_amax_static = d->x_amax_static;
-    a.out_amax = d->out_amax;
-    const bool up = d->up_h == 2, pool = d->pool_h == 2, zins = d->zins_h == 2, s2 = d->stride_h == 2;
-    const bool planes = pool || s2;
-    a.tiles_x = d->ws / (planes ? 2 * H2_TS : H2_TS);              // (tiles of the grid the kernel walks: the source grid, or one of its parity planes)
-    a.tiles_y = d->hs / (planes ? 2 * H2_TS : H2_TS);
-    const int mb = H2_MB_OF(d->cout);
-    a.n_ct = (d->cout / H2_BM_OF(mb)) * ((up || zins) ? 4 : 1);
-    a.c16 = d->cx / H2_CK;
-    a.nchunk = a.c16 * (planes ? 4 : 1);
-    a.stagger = 0;
+    h2_args a; H2Pick p; unsigned grid;
+    const int rc = h2_pick(d, sda_cu_count(), &a, &p, &grid);
+    if (rc != SDA_OK) return rc;
 #ifdef SDA_H2_ABLATE
-    { static const int stg = getenv("SDA_H2_STAGGER") ? atoi(getenv("SDA_H2_STAGGER")) : 0; a.stagger = stg; }
+    static const int stagger = getenv("SDA_H2_STAGGER") ? atoi(getenv("SDA_H2_STAGGER")) : 0;
+    static const int abl = getenv("SDA_H2_ABL") ? atoi(getenv("SDA_H2_ABL")) : 0;
+    a.stagger = stagger;
+    if (p.loader == 0 && p.mb == 3)
+        for (const auto& v : H2_ABL_TABLE)
+            if (v.abl == abl) return v.launch(d, a, grid, (hipStream_t)stream);
 #endif
-    if (!(a.w_scale > 0.f) || (!a.x_amax && !(a.x_amax_static > 0.f))) return SDA_E_BADARG;
-    const int lds = H2_LDS;
-    a.ntiles = (int)((int64_t)d->n * a.tiles_x * a.tiles_y * a.n_ct);
-    // persistent workgroups, one per CU (the stage buffers take the whole LDS); a multiple of 8 keeps the XCD-contiguous tile walk
-    int cus = sda_cu_count();
-    if (cus <= 0) cus = 256;
-    unsigned grid = (unsigned)(a.ntiles < cus ? a.ntiles : cus);
-    if (grid >= 8) grid &= ~7u;
-    int rc = SDA_OK;
-#ifdef SDA_H2_ABLATE
-    {
-        static const int abl_env = getenv("SDA_H2_ABL") ? atoi(getenv("SDA_H2_ABL")) : 0;
-        const int abl = mb == 3 ? abl_env : 0;               // (the ablation variants exist for the 96-cout tile)
-        static bool seta[16][SDA_MAX_DEVICES];
-        const void* fn = nullptr;
-#define H2_ABL_CASE(v) case v: fn = reinterpret_cast<const void*>(conv_h2_kernel<0, 0, v>); \
-            if (!d->ln_mean && d->act_in == SDA_ACT_NONE) { if ((rc = sda_raise_dyn_lds(fn, lds, seta[v])) != SDA_OK) return rc; \
-                hipLaunchKernelGGL((conv_h2_kernel<0, 0, v>), dim3(grid), dim3(512), (size_t)lds, (hipStream_t)stream, *d, a); return sda_launch_status(); } break;
-        switch (abl) {
-            H2_ABL_CASE(1) H2_ABL_CASE(2) H2_ABL_CASE(3) H2_ABL_CASE(4) H2_ABL_CASE(7) H2_ABL_CASE(8) H2_ABL_CASE(11) H2_ABL_CASE(15)
-            default: break;
-        }
-    }
-#endif
-    // (the stride-2 heads and their VJP, the tails' VJP: plain loader; the tails: LayerNorm or plain; the block convolutions: all three)
-    if (zins) return h2_launch<0, 3>(d, a, grid, lds, mb, (hipStream_t)stream);
-    if (s2) return h2_launch<0, 4>(d, a, grid, lds, mb, (hipStream_t)stream);
-    if (pool) return h2_launch<0, 2>(d, a, grid, lds, mb, (hipStream_t)stream);
-    if (up) return d->ln_mean ? h2_launch<2, 1>(d, a, grid, lds, mb, (hipStream_t)stream) : h2_launch<0, 1>(d, a, grid, lds, mb, (hipStream_t)stream);
-    if (d->ln_mean) return h2_launch<2, 0>(d, a, grid, lds, mb, (hipStream_t)stream);
-    if (d->act_in != SDA_ACT_NONE) return h2_launch<1, 0>(d, a, grid, lds, mb, (hipStream_t)stream);
-    return h2_launch<0, 0>(d, a, grid, lds, mb, (hipStream_t)stream);
+    for (const auto& v : H2_TABLE)
+        if (!memcmp(&v.pick, &p, sizeof(p))) return v.launch(d, a, grid, (hipStream_t)stream);
+    return SDA_E_UNSUPPORTED;                                      // (not reached: h2_pick names table rows only, tests/test_winograd_dispatch_host.py)
 }
+
+#else  // SDA_HOST_EMU
+// h2_pick for tests/test_winograd_dispatch_host.py.  out: the pick's 3 fields, the launch grid, the dynamic-LDS bytes, a.tiles_x, tiles_y, n_ct,
+// c16, nchunk, ntiles
+extern "C" int sda_conv_h2_pick(const sda_conv_desc* d, int cus, int out[11]) {
+    h2_args a; H2Pick p; unsigned grid;
+    const int rc = h2_pick(d, cus, &a, &p, &grid);
+    if (rc != SDA_OK) return rc;
+    const int v[11] = {p.loader, p.mode, p.mb, (int)grid, H2_LDS, a.tiles_x, a.tiles_y, a.n_ct, a.c16, a.nchunk, a.ntiles};
+    memcpy(out, v, sizeof(v));
+    return SDA_OK;
+}
+// the variant table: copies its rows (the 3 pick fields each) if `cap` rows fit and returns their number
+extern "C" int sda_conv_h2_variants(int* out, int cap) {
+    static const H2Pick rows[] = {H2_ROWS(H2_PICK_ROW)};
+    if (cap >= (int)(sizeof(rows) / sizeof(rows[0]))) memcpy(out, rows, sizeof(rows));
+    return (int)(sizeof(rows) / sizeof(rows[0]));
+}
+#endif  // SDA_HOST_EMU

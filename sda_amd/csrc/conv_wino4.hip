@@ -35,6 +35,7 @@
 // Roofline: fp32 matrix pipe, 157.3 TFLOP/s; issued flops = algorithmic (direct-convolution) flops / 2.25.
 #include "sda_common.hpp"
 #include <stdlib.h>
+#include <string.h>
 #include <type_traits>
 
 // (The U slab goes L2 -> registers -> ds_write_b128; the LDS-DMA form was built, measured 2-11 % slower and removed: profiles/r05_w4_udma_ab.txt.)
@@ -86,10 +87,17 @@ __device__ __forceinline__ void w4_static_for(F&& f) {
     }
 }
 
-static int wino4_config(const sda_conv_desc* d);
+// the four loader configurations of the reference U-Net have a kernel: plain (backward-data convolutions), modulation +
+// LayerNorm (first block convolution), SiLU (second block convolution), LayerNorm (upsampling tails); other combinations
+// are served by the direct kernel
+static int wino4_config(const sda_conv_desc* d) {
+    const bool mod = d->mod != nullptr, ln = d->ln_mean != nullptr, silu = d->act_in == SDA_ACT_SILU;
+    const int key = (mod ? 4 : 0) | (ln ? 2 : 0) | (silu ? 1 : 0);
+    return (key == 0 || key == 1 || key == 2 || key == 6) ? key : -1;
+}
 
 // eligibility + geometry.  SDA_E_UNSUPPORTED -> the caller falls back to the direct kernel.
-int sda_wino4_plan(const sda_conv_desc* d, Wino4Geom* g) {
+static int sda_wino4_plan(const sda_conv_desc* d, Wino4Geom* g) {
     if (!d || !d->x || !d->w_wino4 || !d->out) return SDA_E_UNSUPPORTED;
     if (d->kh != 3 || d->kw != 3 || d->stride_h != 1 || d->stride_w != 1 || d->zins_h != 1 || d->zins_w != 1)
         return SDA_E_UNSUPPORTED;
@@ -139,10 +147,11 @@ int sda_wino4_plan(const sda_conv_desc* d, Wino4Geom* g) {
     { static const int dbg = sda_debug_env(); g->debug = dbg; }            // (0 in the product build)
 #endif
     g->trace = nullptr;
-    g->walk = 1; g->sc = 1; g->sx = 0; g->sy = 0; g->sn = 0;   // (set per launch: sda_wino4_launch)
+    g->walk = 1; g->sc = 1; g->sx = 0; g->sy = 0; g->sn = 0;   // (set per launch: wino4_pick)
     return SDA_OK;
 }
 
+#ifndef SDA_HOST_EMU
 // (tile id of the flat XCD-ordered list) -> cout tile, image, block row / column
 struct W4Tile { int ct, n, by, bx; };
 __device__ __forceinline__ W4Tile w4_decode(const Wino4Geom& g, int tile) {
@@ -246,7 +255,7 @@ __host__ __device__ constexpr bool w4_dead(int p) { return ZP != 0 && ((p >> 2) 
 // MF:  cout fragments (16 couts each) per consumer wave: the workgroup tile is 32 MF couts x 32 Winograd tiles (W4_BM_OF above).  MF = 2
 //      keeps everything of the MF = 3 design -- same helpers, same V side, same two barriers per stage -- with 8 instead of 12 MFMAs and 4
 //      instead of 5 LDS reads per consumer step, a 32-KiB U slab (8 loads per helper) and the epilogue operand through consumer-side
-//      loads (EPM 2; see wino4_epm for the measured-and-removed helper-fed form).
+//      loads (EPM 2; see wino4_pick for the measured-and-removed helper-fed form).
 template <bool MOD, bool LN, bool SILU, int EPM, int VAR = 0, int ZP = 0, int MF = 3>
 __global__ __launch_bounds__(512, 2) void conv_wino4_kernel(const sda_conv_desc d, const Wino4Geom g) {
     static_assert(MF >= 1 && MF <= 3, "cout tile = 32, 64 or 96");
@@ -1200,159 +1209,145 @@ extern "C" int sda_w4_trace_read(double* out) {
     }
     return SDA_OK;
 }
+// arms the phase trace of a VAR 11 launch: the (zeroed) buffer sda_w4_trace_read reads
+static int w4_trace_arm(Wino4Geom* g, int grid, hipStream_t stream) {
+    if (!w4_trace_buf && hipMalloc(&w4_trace_buf, 256 * 64 * sizeof(long long)) != hipSuccess) return SDA_E_BADARG;
+    (void)hipMemsetAsync(w4_trace_buf, 0, 256 * 64 * sizeof(long long), stream);
+    g->trace = w4_trace_buf; w4_trace_grid = grid;
+    return SDA_OK;
+}
 #endif
 
-template <bool MOD, bool LN, bool SILU, int EPI, int VAR, int ZP, int MF>
+template <bool MOD, bool LN, bool SILU, int EPM, int VAR, int ZP, int MF>
 static int wino4_launch_mf(const sda_conv_desc* d, const Wino4Geom& g, int grid, hipStream_t stream) {
     static_assert(W4_LDS_BYTES_OF(MF) <= 160 * 1024, "LDS");
     static bool attr_set[SDA_MAX_DEVICES];
-    const int rc = sda_raise_dyn_lds(reinterpret_cast<const void*>(conv_wino4_kernel<MOD, LN, SILU, EPI, VAR, ZP, MF>), W4_LDS_BYTES_OF(MF), attr_set);
+    const int rc = sda_raise_dyn_lds(reinterpret_cast<const void*>(conv_wino4_kernel<MOD, LN, SILU, EPM, VAR, ZP, MF>), W4_LDS_BYTES_OF(MF), attr_set);
     if (rc != SDA_OK) return rc;
-    hipLaunchKernelGGL((conv_wino4_kernel<MOD, LN, SILU, EPI, VAR, ZP, MF>), dim3(grid), dim3(512), (size_t)W4_LDS_BYTES_OF(MF), stream, *d, g);
+    hipLaunchKernelGGL((conv_wino4_kernel<MOD, LN, SILU, EPM, VAR, ZP, MF>), dim3(grid), dim3(512), (size_t)W4_LDS_BYTES_OF(MF), stream, *d, g);
     return sda_launch_status();
 }
 
-// (the 64-cout tile ships for the product variants only: the tooling variants VAR != 0 study the 96-cout kernel)
-template <bool MOD, bool LN, bool SILU, int EPI, int VAR, int ZP = 0>
-static int wino4_launch_t(const sda_conv_desc* d, const Wino4Geom& g, int grid, hipStream_t stream) {
-    if constexpr ((VAR == 0 || VAR == 11) && EPI != 1) {   // (11: the phase trace of tools/wino4_check.py, tooling builds)
-        if (g.mf == 2) return wino4_launch_mf<MOD, LN, SILU, EPI, VAR, ZP, 2>(d, g, grid, stream);
-        if constexpr (ZP != 1 && VAR == 0) {
-            if (g.mf == 1) return wino4_launch_mf<MOD, LN, SILU, EPI, VAR, ZP, 1>(d, g, grid, stream);
-        }
-    }
-    if (g.mf != 3) return SDA_E_UNSUPPORTED;
-    return wino4_launch_mf<MOD, LN, SILU, EPI, VAR, ZP, 3>(d, g, grid, stream);
-}
+#endif  // !SDA_HOST_EMU
 
-// the four loader configurations of the reference U-Net have a kernel: plain (backward-data convolutions), modulation +
-// LayerNorm (first block convolution), SiLU (second block convolution), LayerNorm (upsampling tails); other combinations
-// are served by the direct kernel
-static int wino4_config(const sda_conv_desc* d) {
-    const bool mod = d->mod != nullptr, ln = d->ln_mean != nullptr, silu = d->act_in == SDA_ACT_SILU;
-    const int key = (mod ? 4 : 0) | (ln ? 2 : 0) | (silu ? 1 : 0);
-    return (key == 0 || key == 1 || key == 2 || key == 6) ? key : -1;
-}
+// ---------------------------------------------------------------- which instantiation serves a launch (host; no device; of the environment
+// only what sda_wino4_plan reads: the ablation bits of tooling builds, g->debug)
+struct W4Pick { int mod, ln, silu, epm, var, zp, mf; };                // conv_wino4_kernel's template arguments
+// $SDA_CONV_WINO=0: no Winograd form at all; $SDA_CONV_WINO4=0: not this kernel.  One kernel today, so either clears `enabled` and sends the
+// launch to the direct kernel (sda_amd/ops.py reads the same two switches for the packing).  A/B runs: $SDA_W4_EPI=0 (no operand through
+// the helpers), $SDA_W4_ZP=0 (the up-sampled launch on the full kernels), $SDA_W4_WALK=0 (contiguous tile sub-ranges).  var: $SDA_W4_VAR, the
+// ablation variant tools/wino4_check.py asks a tooling build for (0 in the product build)
+struct W4Switches { bool enabled, epi, zp, walk; int var; };
 
-static int wino4_epm(const sda_conv_desc* d, const Wino4Geom& g) {
-    // the epilogue operand through the helpers (EPI, mode 1): one operand, tiles of at least twelve stages (the six-stage load
-    // window of a tile must open after the previous tile's operand has left the registers: not before stage 5), SiLU' if it is an
-    // act' launch.  The 64-cout tile loads its 16 pairs in a two-stage window: tiles of at least eight stages (64 input channels).
-    static const bool epi_on = !(getenv("SDA_W4_EPI") && atoi(getenv("SDA_W4_EPI")) == 0);
+// The shipped instantiations, each written once: W4(MOD, LN, SILU, EPM, VAR, ZP, MF).  A loader configuration of the full kernels has no
+// operand (EPM 0) and consumer-side loads (EPM 2) at every cout tile, the helper-fed operand (EPM 1) at the 96-cout tile only
+#define W4_ROWS_MF123(W4, MOD, LN, SILU, EPM, ZP) W4(MOD, LN, SILU, EPM, 0, ZP, 1) W4(MOD, LN, SILU, EPM, 0, ZP, 2) W4(MOD, LN, SILU, EPM, 0, ZP, 3)
+#define W4_ROWS_FULL(W4, MOD, LN, SILU) W4_ROWS_MF123(W4, MOD, LN, SILU, 0, 0) W4_ROWS_MF123(W4, MOD, LN, SILU, 2, 0)
+#define W4_ROWS(W4) \
+    W4_ROWS_FULL(W4, 0, 0, 0) W4(0, 0, 0, 1, 0, 0, 3)                /* plain (backward-data convolutions) */ \
+    W4_ROWS_FULL(W4, 0, 0, 1) W4(0, 0, 1, 1, 0, 0, 3)                /* SiLU (second block convolution) */ \
+    W4_ROWS_FULL(W4, 0, 1, 0) W4(0, 1, 0, 1, 0, 0, 3)                /* LayerNorm (up-sampling tails + skip) */ \
+    W4_ROWS_FULL(W4, 1, 1, 0)                                        /* modulation + LayerNorm (first block convolution) */ \
+    W4_ROWS_MF123(W4, 0, 0, 0, 0, 2)                                 /* zero positions: pooled output */ \
+    W4(0, 1, 0, 1, 0, 1, 3) W4(0, 1, 0, 2, 0, 1, 2)                  /* zero positions: 2 x 2 up-sampled LayerNorm + skip (the tails) */
+// tooling builds: the phase trace (VAR 11: tools/wino4_check.py) of the plain and the zero-position kernels, where the operand does not come
+// through the helpers also at the 64-cout tile; the ablation variants 12-15 study the 96-cout kernel without an operand
+#ifdef SDA_W4_VARIANTS
+#define W4_ROWS_TOOLING(W4) \
+    W4(0, 0, 0, 0, 11, 0, 2) W4(0, 0, 0, 0, 11, 0, 3) W4(0, 0, 0, 2, 11, 0, 2) W4(0, 0, 0, 2, 11, 0, 3) W4(0, 0, 0, 1, 11, 0, 3) \
+    W4(0, 0, 0, 0, 11, 2, 2) W4(0, 0, 0, 0, 11, 2, 3) W4(0, 1, 0, 1, 11, 1, 3) \
+    W4(0, 0, 0, 0, 12, 0, 3) W4(0, 0, 0, 0, 13, 0, 3) W4(0, 0, 0, 0, 14, 0, 3) W4(0, 0, 0, 0, 15, 0, 3)
+#else
+#define W4_ROWS_TOOLING(W4)
+#endif
+#define W4_PICK_ROW(MOD, LN, SILU, EPM, VAR, ZP, MF) {MOD, LN, SILU, EPM, VAR, ZP, MF},
+
+// Plans the launch (`g`, the launch grid) and names the instantiation that serves it; returns what sda_wino4_try returns short of the
+// launch's own status.  SDA_E_UNSUPPORTED -> the caller falls back to the direct kernel.
+static int wino4_pick(const sda_conv_desc* d, const W4Switches& sw, int cus, Wino4Geom* g, W4Pick* p, int* grid) {
+    if (!sw.enabled) return SDA_E_UNSUPPORTED;
+    const int rc = sda_wino4_plan(d, g);
+    if (rc != SDA_OK) return rc;
+    if (!cus) return SDA_E_BADARG;
+    // persistent grid: one workgroup per CU in whole rounds of the 8 XCDs, never more than there are tiles
+    *grid = cus - cus % 8;
+    const int need = (g->grid + 7) / 8 * 8;
+    if (*grid > need) *grid = need;
+    if (*grid < 8) *grid = 8;
+    // the tile walk (see the kernel): interleaved within an XCD by default, else contiguous sub-ranges
+    g->walk = sw.walk ? 1 : 0;
+    int step = sw.walk ? *grid / 8 : 1;                    // tiles between a workgroup's consecutive tiles
+    g->sc = step % g->n_ct; step /= g->n_ct;
+    g->sx = step % g->bx_n; step /= g->bx_n;
+    g->sy = step % g->by_n;
+    g->sn = step / g->by_n;
+    const int cfg = wino4_config(d);                       // (>= 0: the plan)
+    // one epilogue operand, SiLU' if it is the act' one: the launch the helper-fed and the up-sampled kernels are built for
+    const bool one_operand = ((d->res != nullptr) != (d->dact_z != nullptr)) && (!d->dact_z || d->act_d == SDA_ACT_SILU);
+    // the epilogue operand through the helpers (EPM 1): that launch, with tiles of at least twelve stages (the six-stage load window of a
+    // tile must open after the previous tile's operand has left the registers: not before stage 5).
     // 64- / 32-cout tiles: consumer-side loads (EPM 2) only.  The helper-fed route was built for the 64-cout tile (a two-slot window of
     // eight loads: an eight-stage tile leaves no room for more slots) and measured SLOWER than the consumers' own loads -- equal at 64
     // channels, +4 % at 128, +7 % at 256, +10 % on the up-sampled tail (profiles/r06_mf2_epm_ab.txt: 128 accumulators leave the consumers the
     // registers to keep their loads in flight, and the helpers lose the window loads of every stage) -- and removed.
-    const bool epi = epi_on && g.mf == 3 && ((d->res != nullptr) != (d->dact_z != nullptr)) && g.nstage >= 12 &&
-                     (!d->dact_z || d->act_d == SDA_ACT_SILU);
-    return epi ? 1 : ((d->res || d->dact_z) ? 2 : 0);
+    const bool helper_fed = sw.epi && g->mf == 3 && one_operand && g->nstage >= 12;
+    // zero-position kernels (ZP, see the kernel).  2 = pooled output (eligibility, w_wino4_zp included: the plan).  1 = the 2 x 2 up-sampled
+    // source in the reference tails' configuration, LayerNorm loader + one operand: at 96 couts the helper-fed launch; at 64 couts any tile
+    // length, its skip operand through consumer-side loads (EPM 2 below: 2.07 -> 1.87 ms on the 128 -> 64 tail, neutral at 96 couts)
+    int zp = 0;
+    if (d->pool_h > 1 || d->pool_w > 1) zp = 2;
+    else if (sw.zp && d->w_wino4_zp && !(reinterpret_cast<uintptr_t>(d->w_wino4_zp) & 15) && d->up_h == 2 && d->up_w == 2 && cfg == 2 &&
+             (g->mf == 3 ? helper_fed : g->mf == 2 && one_operand))
+        zp = 1;
+    // how the operand travels: 1 where the launch is the helper-fed one -- but modulation + LayerNorm has no such kernel (EPM 2 serves it) --
+    // else 2 for any operand(s), 0 for none
+    const int epm = (helper_fed && cfg != 6) ? 1 : ((d->res || d->dact_z) ? 2 : 0);
+    // tooling variants: the phase trace (11) of the plain and the zero-position kernels, 12-15 of the plain kernel without an operand;
+    // other launches run the product kernel.  Only the trace has a tile narrower than 96 couts: 64, where EPM is not 1
+    int var = 0;
+    if (sw.var == 11 ? (zp || cfg == 0) : (sw.var >= 12 && sw.var <= 15 && !zp && cfg == 0 && epm == 0)) var = sw.var;
+    if (var && g->mf != 3 && !(var == 11 && g->mf == 2 && zp != 1)) return SDA_E_UNSUPPORTED;
+    *p = W4Pick{(cfg >> 2) & 1, (cfg >> 1) & 1, cfg & 1, epm, var, zp, g->mf};
+    return SDA_OK;
 }
 
-// which zero-position kernel (ZP) serves the launch: 2 = pooled output, 1 = 2 x 2 up-sampled source (the reference tails'
-// configuration: LayerNorm loader + skip operand through the helpers), 0 = the full kernels
-static int wino4_zp(const sda_conv_desc* d, const Wino4Geom& g) {
-    static const bool zp_on = !(getenv("SDA_W4_ZP") && atoi(getenv("SDA_W4_ZP")) == 0);
-    if (d->pool_h > 1 || d->pool_w > 1) return 2;                                               // (the plan requires w_wino4_zp)
-    if (!(zp_on && d->w_wino4_zp && !(reinterpret_cast<uintptr_t>(d->w_wino4_zp) & 15) && d->up_h == 2 && d->up_w == 2 && wino4_config(d) == 2))
-        return 0;
-    if (g.mf == 3) return wino4_epm(d, g) == 1 ? 1 : 0;
-    // 64-cout tile: the same launch (one operand; SiLU' if it is the act' one) with consumer-side loads, any tile length
-    return (g.mf == 2 && ((d->res != nullptr) != (d->dact_z != nullptr)) && (!d->dact_z || d->act_d == SDA_ACT_SILU)) ? 1 : 0;
-}
+#ifndef SDA_HOST_EMU
+// the variant table: the rows with their launchers
+typedef int (*w4_launch_fn)(const sda_conv_desc*, const Wino4Geom&, int, hipStream_t);
+#define W4_VARIANT(MOD, LN, SILU, EPM, VAR, ZP, MF) {W4_PICK_ROW(MOD, LN, SILU, EPM, VAR, ZP, MF) wino4_launch_mf<MOD, LN, SILU, EPM, VAR, ZP, MF>},
+static const struct { W4Pick pick; w4_launch_fn launch; } W4_TABLE[] = {W4_ROWS(W4_VARIANT) W4_ROWS_TOOLING(W4_VARIANT)};
 
-int sda_wino4_launch(const sda_conv_desc* d, const Wino4Geom& g_in, hipStream_t stream) {
-    const int cus = sda_cu_count();
-    if (!cus) return SDA_E_BADARG;
-    int grid = cus - cus % 8;
-    const int need = (g_in.grid + 7) / 8 * 8;
-    if (grid > need) grid = need;
-    if (grid < 8) grid = 8;
-    // the tile walk (see the kernel): interleaved within an XCD by default; SDA_W4_WALK=0 = contiguous sub-ranges (A/B runs)
-    static const bool walk_on = !(getenv("SDA_W4_WALK") && atoi(getenv("SDA_W4_WALK")) == 0);
-    Wino4Geom g = g_in;
-    g.walk = walk_on ? 1 : 0;
-    {
-        int step = walk_on ? grid / 8 : 1;                 // tiles between a workgroup's consecutive tiles
-        g.sc = step % g.n_ct; step /= g.n_ct;
-        g.sx = step % g.bx_n; step /= g.bx_n;
-        g.sy = step % g.by_n;
-        g.sn = step / g.by_n;
-    }
-    const int epm = wino4_epm(d, g);
-#define W4_LAUNCH3(MOD, LN, SILU)                                                                                              \
-    (epm == 1 ? wino4_launch_t<MOD, LN, SILU, 1, 0>(d, g, grid, stream)                                                        \
-              : epm == 2 ? wino4_launch_t<MOD, LN, SILU, 2, 0>(d, g, grid, stream)                                             \
-                         : wino4_launch_t<MOD, LN, SILU, 0, 0>(d, g, grid, stream))
-    // zero-position kernels (ZP, see the kernel): the pooled-output launch, and the 2 x 2 up-sampled LayerNorm + skip launch of the
-    // reference tails; SDA_W4_ZP=0 runs the latter on the full kernels (A/B runs)
-    const int zp = wino4_zp(d, g);
+static W4Switches wino4_switches() {
+    static const W4Switches env = [] {                     // the environment is read here, once
+        auto off = [](const char* name) { const char* e = getenv(name); return e && atoi(e) == 0; };
+        return W4Switches{!off("SDA_CONV_WINO") && !off("SDA_CONV_WINO4"), !off("SDA_W4_EPI"), !off("SDA_W4_ZP"), !off("SDA_W4_WALK"), 0};
+    }();
+    W4Switches sw = env;
 #ifdef SDA_W4_VARIANTS
-    if (zp && getenv("SDA_W4_VAR") && atoi(getenv("SDA_W4_VAR")) == 11) {                      // phase tracing of the ZP kernels
-        static long long* tbuf = nullptr;
-        if (!tbuf && hipMalloc(&tbuf, 256 * 64 * sizeof(long long)) != hipSuccess) return SDA_E_BADARG;
-        (void)hipMemsetAsync(tbuf, 0, 256 * 64 * sizeof(long long), stream);
-        Wino4Geom gt = g; gt.trace = tbuf; w4_trace_buf = tbuf; w4_trace_grid = grid;
-        return zp == 2 ? wino4_launch_t<false, false, false, 0, 11, 2>(d, gt, grid, stream)
-                       : wino4_launch_t<false, true, false, 1, 11, 1>(d, gt, grid, stream);
-    }
+    if (const char* e = getenv("SDA_W4_VAR")) sw.var = atoi(e);        // (tooling build: re-read per launch, as g->debug is)
 #endif
-    if (zp == 2) return wino4_launch_t<false, false, false, 0, 0, 2>(d, g, grid, stream);      // (eligibility: the plan)
-    // (64-cout tile: the tail's skip operand through consumer-side loads -- 2.07 -> 1.87 ms on the 128 -> 64 tail, neutral at 96 couts)
-    if (zp == 1) return g.mf == 2 ? wino4_launch_mf<false, true, false, 2, 0, 1, 2>(d, g, grid, stream)
-                                  : wino4_launch_t<false, true, false, 1, 0, 1>(d, g, grid, stream);
-    switch (wino4_config(d)) {
-        case 0: {
-#ifdef SDA_W4_VARIANTS
-            const char* ev = getenv("SDA_W4_VAR");
-            switch (ev ? atoi(ev) : 0) {
-                case 11: {                                                                      // phase tracing
-                    static long long* tbuf = nullptr;
-                    if (!tbuf && hipMalloc(&tbuf, 256 * 64 * sizeof(long long)) != hipSuccess) return SDA_E_BADARG;
-                    (void)hipMemsetAsync(tbuf, 0, 256 * 64 * sizeof(long long), stream);
-                    Wino4Geom gt = g; gt.trace = tbuf; w4_trace_buf = tbuf; w4_trace_grid = grid;
-                    return epm == 1 ? wino4_launch_t<false, false, false, 1, 11>(d, gt, grid, stream)
-                         : epm == 2 ? wino4_launch_t<false, false, false, 2, 11>(d, gt, grid, stream)
-                                    : wino4_launch_t<false, false, false, 0, 11>(d, gt, grid, stream);
-                }
-                case 12: if (epm == 0) return wino4_launch_t<false, false, false, 0, 12>(d, g, grid, stream); break;
-                case 13: if (epm == 0) return wino4_launch_t<false, false, false, 0, 13>(d, g, grid, stream); break;
-                case 14: if (epm == 0) return wino4_launch_t<false, false, false, 0, 14>(d, g, grid, stream); break;
-                case 15: if (epm == 0) return wino4_launch_t<false, false, false, 0, 15>(d, g, grid, stream); break;
-                default: break;
-            }
-#endif
-            return W4_LAUNCH3(false, false, false);
-        }
-        case 1: return W4_LAUNCH3(false, false, true);
-        case 2: return W4_LAUNCH3(false, true, false);                                             // (up-sampling tails + skip)
-        case 6: return epm == 0 ? wino4_launch_t<true, true, false, 0, 0>(d, g, grid, stream)
-                                : wino4_launch_t<true, true, false, 2, 0>(d, g, grid, stream);
-        default: return SDA_E_UNSUPPORTED;
-    }
-#undef W4_LAUNCH3
-}
-
-// SDA_CONV_WINO=0: no Winograd form at all; SDA_CONV_WINO4=0: not this kernel.  One kernel today, so either sends the launch to the
-// direct kernel (sda_amd/ops.py reads the same two switches for the packing).
-static bool wino4_disabled() {
-    static const bool off = (getenv("SDA_CONV_WINO") && atoi(getenv("SDA_CONV_WINO")) == 0) ||
-                            (getenv("SDA_CONV_WINO4") && atoi(getenv("SDA_CONV_WINO4")) == 0);
-    return off;
+    return sw;
 }
 
 // 0 = not served; 1 = the full kernels; 2 = a zero-position kernel (54 of 96 MFMAs per stage)
 int sda_wino4_path(const sda_conv_desc* d) {
-    Wino4Geom g;
-    if (wino4_disabled() || sda_wino4_plan(d, &g) != SDA_OK) return 0;
-    return wino4_zp(d, g) ? 2 : 1;
+    Wino4Geom g; W4Pick p; int grid;
+    W4Switches sw = wino4_switches();
+    sw.var = 0;                                            // (the family of the launch, whichever tooling variant would run it)
+    if (wino4_pick(d, sw, 8, &g, &p, &grid) != SDA_OK) return 0;                   // (any CU count: the row does not depend on it)
+    return p.zp ? 2 : 1;
 }
 
 int sda_wino4_try(const sda_conv_desc* d, hipStream_t stream) {
-    if (wino4_disabled()) return SDA_E_UNSUPPORTED;
-    Wino4Geom g;
-    const int rc = sda_wino4_plan(d, &g);
+    Wino4Geom g; W4Pick p; int grid;
+    const int rc = wino4_pick(d, wino4_switches(), sda_cu_count(), &g, &p, &grid);
     if (rc != SDA_OK) return rc;
-    return sda_wino4_launch(d, g, stream);
+#ifdef SDA_W4_VARIANTS
+    if (p.var == 11 && w4_trace_arm(&g, grid, stream) != SDA_OK) return SDA_E_BADARG;
+#endif
+    for (const auto& v : W4_TABLE)
+        if (!memcmp(&v.pick, &p, sizeof(p))) return v.launch(d, g, grid, stream);
+    return SDA_E_UNSUPPORTED;                              // (not reached: wino4_pick names table rows only, tests/test_winograd_dispatch_host.py)
 }
 
 // ---------------------------------------------------------------- weight transform for this kernel (one-off per layer)
@@ -1453,3 +1448,24 @@ extern "C" int sda_pack_conv_weight_wino4_zp(const float* w_wino4, int k_pad, in
     hipLaunchKernelGGL(pack_wino4_zp_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, w_wino4, dst, k_pad / 8, m_pad / W4_BM_OF(mf), mf);
     return sda_launch_status();
 }
+
+#else  // SDA_HOST_EMU
+// wino4_pick for tests/test_winograd_dispatch_host.py.  out: the pick's 7 fields, the launch grid, the dynamic-LDS bytes, g.bx_n, by_n, n_ct,
+// nstage, mtiles, walk, sc, sx, sy, sn, mf
+extern "C" int sda_wino4_pick(const sda_conv_desc* d, int enabled, int epi, int zp, int walk, int cus, int out[20]) {
+    Wino4Geom g; W4Pick p; int grid;
+    const int rc = wino4_pick(d, W4Switches{enabled != 0, epi != 0, zp != 0, walk != 0, 0}, cus, &g, &p, &grid);
+    if (rc != SDA_OK) return rc;
+    const int rest[13] = {grid, p.mf == 3 ? W4_LDS_BYTES_OF(3) : p.mf == 2 ? W4_LDS_BYTES_OF(2) : W4_LDS_BYTES_OF(1),
+                          g.bx_n, g.by_n, g.n_ct, g.nstage, g.mtiles, g.walk, g.sc, g.sx, g.sy, g.sn, g.mf};
+    memcpy(out, &p, sizeof(p));
+    memcpy(out + 7, rest, sizeof(rest));
+    return SDA_OK;
+}
+// the variant table: copies its rows (the 7 pick fields each) if `cap` rows fit and returns their number
+extern "C" int sda_wino4_variants(int* out, int cap) {
+    static const W4Pick rows[] = {W4_ROWS(W4_PICK_ROW)};
+    if (cap >= (int)(sizeof(rows) / sizeof(rows[0]))) memcpy(out, rows, sizeof(rows));
+    return (int)(sizeof(rows) / sizeof(rows[0]));
+}
+#endif  // SDA_HOST_EMU

@@ -389,3 +389,68 @@ def test_h2_trained_checkpoint_like_operands(dev, cin, cout, hw, n):
         assert served, 'the f16 x 2 kernel did not serve the launch'
         assert whole <= 3e-6 and worst <= 4e-6, (kw, r)
         assert worst <= 2.5 * r['f32'][2] + 1e-6, (kw, r)          # and in the fp32 kernels' class channel by channel
+
+
+# the 16 rows of conv_h2's variant table (csrc/conv_h2.hip: H2_ROWS; tests/test_winograd_dispatch_host.py holds the table to the host pick)
+H2_ROWS = [(ld, md, mb) for ld, md in ((0, 0), (1, 0), (2, 0), (0, 1), (2, 1), (0, 2), (0, 3), (0, 4)) for mb in (3, 2)]
+
+
+@pytest.mark.parametrize('loader,mode,mb', H2_ROWS)
+def test_h2_every_variant(dev, f16x2, loader, mode, mb):
+    """Every instantiation of conv_h2_kernel runs once, at the smallest shape it admits (one 16 x 16 tile of 32 channels, 32 x 32 source
+    pixels where the producers sample parity planes: the pooled and the stride-2 forms; 96 or 64 couts = the row's tile), against float64
+    at the bound of this module's single launches."""
+    from sda_amd import ops
+    from sda_amd.engine import launch_conv, planar_source
+    torch.manual_seed(10 * loader + 3 * mode + mb)
+    k, m = 32, 32 * mb                                   # contraction channels, output channels of the LAUNCH
+    transpose = mode in (2, 3)
+    w = (torch.rand(k, m, 3, 3, device=dev) * 2 - 1) / math.sqrt(m * 9) if transpose else (torch.rand(m, k, 3, 3, device=dev) * 2 - 1) / math.sqrt(k * 9)
+    b = None if transpose else torch.randn(m, device=dev)
+    pk = ops.PackedConv(w, b, transpose=transpose)
+    side = 32 if mode in (2, 4) else 16
+    x = torch.randn(1, k, side, side, device=dev) * 1.3
+    w64, x64 = w.double().cpu(), x.double().cpu()
+    pad = lambda v: F.pad(v, (1, 1, 1, 1), mode='circular')
+    kw, ln = {}, None
+    if loader == 2:
+        var, mean = torch.var_mean(x, dim=1, unbiased=True)
+        ln = kw['ln'] = (mean.reshape(-1).contiguous(), (1 / torch.sqrt(var + 1e-5)).reshape(-1).contiguous())
+    xa = None if ln is not None else ops.absmax(x, pk.in_amax)
+    if mode == 0:
+        res = torch.randn(1, m, side, side, device=dev)
+        out = torch.full_like(res, float('nan'))
+        d = launch_conv(pk, planar_source(x), out, side, side, circular=True, bias=pk.bias, act_in=1 if loader == 1 else 0, res=res, x_amax=xa, **kw)
+        ref = _ref64(x, w, b, True, False, ln is not None, None, loader == 1, None, res)
+        assert (d.up_h, d.pool_h, d.zins_h, d.stride_h) == (1, 1, 1, 1)
+    elif mode == 1:
+        out = torch.full((1, m, 2 * side, 2 * side), float('nan'), device=dev)
+        d = launch_conv(pk, planar_source(x), out, 2 * side, 2 * side, circular=True, bias=pk.bias, up=(2, 2), x_amax=xa, **kw)
+        if ln is not None:
+            v64, m64 = torch.var_mean(x64, dim=1, unbiased=True, keepdim=True)
+            x64 = (x64 - m64) / torch.sqrt(v64 + 1e-5)
+        ref = F.conv2d(pad(x64.repeat_interleave(2, -1).repeat_interleave(2, -2)), w64, b.double().cpu())
+        assert d.up_h == 2
+    elif mode == 2:
+        a64 = torch.zeros(1, m, side // 2, side // 2, dtype=torch.float64, requires_grad=True)
+        ref, = torch.autograd.grad(F.conv2d(pad(a64.repeat_interleave(2, -1).repeat_interleave(2, -2)), w64), a64, x64)
+        out = torch.full((1, m, side // 2, side // 2), float('nan'), device=dev)
+        d = launch_conv(pk, planar_source(x), out, side, side, circular=True, pool=(2, 2), x_amax=xa)
+        assert d is not None and d.pool_h == 2
+    elif mode == 3:
+        skip = torch.randn(1, m, 2 * side, 2 * side, device=dev)
+        a64 = torch.zeros(1, m, 2 * side, 2 * side, dtype=torch.float64, requires_grad=True)
+        ref, = torch.autograd.grad(F.conv2d(pad(a64), w64, stride=2), a64, x64)
+        ref = ref + skip.double().cpu()
+        out = torch.full_like(skip, float('nan'))
+        d = launch_conv(pk, planar_source(x), out, 2 * side, 2 * side, circular=True, zins=(2, 2), res=skip, x_amax=xa)
+        assert d.zins_h == 2
+    else:
+        out = torch.full((1, m, side // 2, side // 2), float('nan'), device=dev)
+        d = launch_conv(pk, planar_source(x), out, side // 2, side // 2, circular=True, stride=(2, 2), bias=pk.bias, x_amax=xa)
+        ref = F.conv2d(pad(x64), w64, b.double().cpu(), stride=2)
+        assert d.stride_h == 2
+    assert d.w_h2, 'the f16 x 2 kernel did not serve the launch'
+    assert (d.cx, d.cout) == (k, m) and bool(d.ln_mean) == (loader == 2) and d.act_in == (1 if loader == 1 else 0)
+    err = ((out.double().cpu() - ref).abs().max() / ref.abs().max()).item()
+    assert err <= 3e-6, f'row {(loader, mode, mb)}: {err:.2e}'

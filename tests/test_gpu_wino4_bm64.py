@@ -275,3 +275,76 @@ def test_unet_default_width_net_32_64_128_forward_and_vjp_vs_oracle(dev):
     with torch.no_grad():
         assert_close(out.detach().cpu(), eps_o(x, t), TOL, what='eps vs the fp32 oracle')
     assert_close(vjp.cpu(), ref, TOL, what='vjp')
+
+
+def _wino4_rows():
+    """The smallest recorded launch of every row of conv_wino4's variant table (tests/golden/wino4_dispatch.json: no switch set, aligned
+    operands, no context channels; tests/test_winograd_dispatch_host.py asserts that these are all the rows and that wino4_pick names them)."""
+    from tests.util import load_pick_dispatch
+    cases, _ = load_pick_dispatch('wino4_dispatch')
+    rows = {}
+    for c in cases:
+        if c['rc'] == 0 and all(c['switches']) and c['cus'] == 256 and c['extra'] == {} and not c['cctx'] and \
+                all(c[k] in (0, 1) for k in c if k.endswith('_ptr')) and \
+                bool(c['w_wino4_zp_ptr']) == (c['up'] == 2 or c['pool'] == 2):           # (the engine passes the packing with exactly these)
+            key = c['out'][:7]
+            size = (c['n'] * c['ho'] * c['wo'], c['cx'], c['cout'])
+            if key not in rows or size < rows[key][0]:
+                rows[key] = (size, c)
+    return [pytest.param(c, id='mod%d-ln%d-silu%d-epm%d-var%d-zp%d-mf%d' % key) for key, (_, c) in sorted(rows.items())]
+
+
+@pytest.mark.parametrize('c', _wino4_rows())
+def test_wino4_every_variant(dev, c):
+    """Every instantiation of conv_wino4_kernel runs once, on the smallest recorded launch that picks it, with the operands the row
+    implies (modulation, LayerNorm statistics, SiLU input, res / act'(z), up-sampled source, pooled output), against float64."""
+    from sda_amd import ops
+    from sda_amd.engine import launch_conv, planar_source
+    row = c['named']
+    torch.manual_seed(sum(c['out'][:7]) + c['cout'])
+    n, cin, cout, hs, ws, ho, wo = c['n'], c['cx'], c['cout'], c['hs'], c['ws'], c['ho'], c['wo']
+    x = torch.randn(n, cin, hs, ws) * 1.3 + 0.1
+    wgt = torch.randn(cout, cin, 3, 3) / (9 * cin) ** 0.5
+    b = None if c['pool'] == 2 else torch.randn(cout)
+    xin, kw = x.double(), {}
+    if c['mod_ptr']:
+        kw['mod'] = torch.randn(1, cin).to(dev)
+        xin = xin + kw['mod'].double().cpu()[:, :, None, None]
+    if c['ln_ptr']:
+        var, mean = torch.var_mean(xin, dim=1, unbiased=True, keepdim=True)
+        rstd = 1 / torch.sqrt(var + 1e-5)
+        kw['ln'] = (mean.float().reshape(n, -1).contiguous().to(dev), rstd.float().reshape(n, -1).contiguous().to(dev))
+        xin = (xin - mean) * rstd
+    if c['act_in']:
+        kw['act_in'] = c['act_in']
+        xin = F.silu(xin)
+    if c['up'] == 2:
+        kw['up'] = (2, 2)
+        xin = xin.repeat_interleave(2, -1).repeat_interleave(2, -2)
+    ref = ref_conv(xin, wgt.double(), None if b is None else b.double(), True)
+    if c['dact_z_ptr']:
+        z = torch.randn(ref.shape)
+        zz = z.double().requires_grad_(True)
+        dz, = torch.autograd.grad((F.silu(zz) if c['act_d'] == 1 else F.relu(zz)).sum(), zz)
+        ref = ref * dz
+        kw['dact_z'], kw['act_d'] = z.to(dev), c['act_d']
+    if c['res_ptr']:
+        r = torch.randn(ref.shape)
+        ref = ref + r.double()
+        kw['res'] = r.to(dev)
+    if c['pool'] == 2:
+        kw['pool'] = (2, 2)
+        ref = 4 * F.avg_pool2d(ref, 2)
+    pk = ops.PackedConv(wgt.to(dev), None if b is None else b.to(dev))
+    out = torch.full(tuple(ref.shape), float('nan'), device=dev)
+    desc = launch_conv(pk, planar_source(x.to(dev)), out, ho, wo, circular=True, bias=pk.bias, **kw)
+    torch.cuda.synchronize()
+    assert desc is not None and ops.conv_path(desc) == (5 if row['zp'] else 2)
+    # the launch is the recorded one in every field the pick reads (bias, which it does not, is added)
+    launched = (desc.n, desc.cx, desc.cctx, desc.hs, desc.ws, desc.ho, desc.wo, desc.up_h, desc.up_w, desc.pool_h, desc.pool_w, desc.cin_pad, desc.cout,
+                desc.cout_pad, desc.act_in, bool(desc.mod), bool(desc.ln_mean), bool(desc.res), bool(desc.dact_z), desc.act_d if desc.dact_z else 0,
+                bool(desc.w_wino4), bool(desc.w_wino4_zp))
+    recorded = (n, cin, 0, hs, ws, ho, wo, c['up'], c['up'], c['pool'], c['pool'], c['cin_pad'], cout, cout, c['act_in'], bool(c['mod_ptr']),
+                bool(c['ln_ptr']), bool(c['res_ptr']), bool(c['dact_z_ptr']), c['act_d'] if c['dact_z_ptr'] else 0, True, bool(c['w_wino4_zp_ptr']))
+    assert launched == recorded, (launched, recorded)
+    assert_close(out.cpu(), ref, TOL, what=str(row))

@@ -77,6 +77,56 @@ def conv_dispatch_desc(c, x_ptr=0x10000, w_ptr=0x20000, out_ptr=0x30000, **ptrs)
                           pad=(c['pad_h'], c['pad_w']) if c['explicit_pad'] else None, **ptrs)
 
 
+def load_pick_dispatch(name):
+    """tests/golden/wino4_dispatch.json / h2_dispatch.json, the dispatch of csrc/conv_wino4.hip / conv_h2.hip recorded from the launch
+    ladders those files had before wino4_pick / h2_pick existed: the list of cases.  A case is a dict of the file's `fields` (the
+    descriptor's varying fields; a `*_ptr` field is 0 for a null pointer, else 1 + the bytes its address is off alignment; `extra` is a dict
+    of further raw descriptor fields, null for a null descriptor), `switches`, `cus`, `rc` and on rc == 0 `out`, named by `out_fields`
+    (the kernel's template arguments, the launch grid, the dynamic-LDS bytes, the planned geometry)."""
+    import json
+    with open(os.path.join(GOLDEN, name + '.json')) as f:
+        data = json.load(f)
+    nf, ns = len(data['fields']), len(data['switch_fields'])
+    cases = []
+    for row in data['cases']:
+        c = dict(zip(data['fields'], row[:nf]))
+        c['switches'], c['cus'], c['rc'] = tuple(row[nf:nf + ns]), row[nf + ns], row[nf + ns + 1]
+        c['out'] = tuple(row[nf + ns + 2:])
+        c['named'] = dict(zip(data['out_fields'], c['out']))
+        cases.append(c)
+    return cases, data['out_fields']
+
+
+_PICK_PTRS = ('out', 'res', 'dact_z', 'bias', 'mod', 'ln', 'w_wino4', 'w_wino4_zp', 'w_h2', 'x_amax')
+
+
+def pick_dispatch_desc(c):
+    """The sda_conv_desc of a load_pick_dispatch() case (None for the null descriptor): a planar 3 x 3 stride-1 launch unless `extra`
+    says otherwise; pointer k of _PICK_PTRS is 0x100000 (k + 2) + its misalignment."""
+    from sda_amd._lib import ConvDesc
+    if c['extra'] is None:
+        return None
+    d = ConvDesc()
+    d.x, d.w = 0x100000, 0x80000
+    d.n, d.cx, d.cctx, d.hs, d.ws, d.ho, d.wo = c['n'], c['cx'], c.get('cctx', 0), c['hs'], c['ws'], c['ho'], c['wo']
+    d.x_sc, d.x_sy, d.x_sx, d.x_sn_outer, d.n_inner = c['hs'] * c['ws'], c['ws'], 1, c['cx'] * c['hs'] * c['ws'], 1
+    d.up_h = d.up_w = c['up']
+    d.pool_h = d.pool_w = c['pool']
+    d.zins_h = d.zins_w = c.get('zins', 1)
+    d.stride_h = d.stride_w = c.get('stride', 1)
+    d.kh = d.kw = 3
+    d.cin_pad, d.cout, d.cout_pad, d.mt = c.get('cin_pad', c['cx']), c['cout'], c['cout'], 1
+    d.act_in, d.act_d = c['act_in'], c['act_d']
+    d.w_h2_scale, d.x_amax_static = c.get('w_h2_scale', 0.0), c.get('x_amax_static', 0.0)
+    for k, name in enumerate(_PICK_PTRS):
+        v = c.get(name + '_ptr', 0)
+        for field in (('ln_mean', 'ln_rstd') if name == 'ln' else (name,)):
+            setattr(d, field, 0x100000 * (k + 2) + v - 1 if v else None)
+    for field, v in c['extra'].items():
+        setattr(d, field, v)
+    return d
+
+
 # ---------------------------------------------------------------------------- model builders shared by GPU tests
 def build_unet1d_tiny():
     import torch.nn as nn
