@@ -992,6 +992,64 @@ int sda_kfvjp_explicit(const sda_kflow_model* m, const float* x, int64_t x_sb, c
 int sda_kfvjp_transition(const sda_kflow_model* m, const float* x0, int64_t x0_sb, const float* g, int64_t g_sb, int nb, float* out,
                          float* work, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Linear-Gaussian state space (csrc/lgss.hip; additive, ABI stays v14): the DampedSpring of sda/mcs.py:60-82 and any chain
+ *   x_0 ~ N(m0, P0),  x_{i+1} = A x_i + b + w_i, w_i ~ N(0, Q),  y = H x + c + v, v ~ N(0, sigma^2 I_k),   1 <= d, k <= 8,
+ * its exact posterior given N observations `step` transitions apart (time index i = 0 .. T = (N - 1) step, observation j at
+ * i = j step, (m0, P0) the law of the state at i = 0) and the exact eps of the VP-noised trajectory.  Matrices travel BY VALUE.
+ *
+ * sda_lgss_advance (fp32): m states [m][d] (stride in_sp), `transitions` >= 1 in ONE launch; every / out_st / out_sp as in
+ *   sda_chain_advance.  x'[i] = b[i] + sum_j A[i][j] x[j] accumulated in index order with fma, then + sum_{j<=i} Lq[i][j] z[j] the
+ *   same way (Lq: lower Cholesky factor of Q).  z of state j at transition t is BY DEFINITION row j of
+ *   sda_randn_rows(out[m][d], seed, row0, draw = draw0 + t).  One state per lane, state in registers.
+ * sda_lgss_tables (HOST only, float64, no device access): table[i] for i = 0 .. T, sda_lgss_table_doubles(d, k, T) doubles in all,
+ *   each slab {K_i[d][k], G_i[d][d], L_i[d][d], Ls_i[k][k], logdet_i}: the Kalman gain (0 where nothing is observed), the backward
+ *   gain G_i = P_i A^T (A P_i A^T + Q)^-1 (0 at i = T), the lower Cholesky factor of P_i - G_i A P_i (of P_T at i = T), the lower
+ *   factor of the innovation covariance H P_i^- H^T + sigma^2 I and its log-determinant (0 where nothing is observed).  Both
+ *   covariance updates use the Joseph form and are symmetrised.  SDA_E_BADARG if Q, P0 or any factor is not positive definite.
+ * sda_lgss_filter: y[B][N][k] fp32 (device) -> mean[B][T+1][d] and logz[B] = log p(y) = sum_j log N(y_j; H m_j^- + c, S_j)
+ *   (2 pi terms included), float64, one sequence per lane; `table` is the device copy of sda_lgss_tables' output.
+ * sda_lgss_sample: out[B][M][T+1][d] fp32, M exact posterior trajectories per sequence: x_T = mean_T + L_T z_T, then downwards
+ *   x_i = mean_i + G_i (x_{i+1} - A mean_i - b) + L_i z_i in float64.  z of sample (b, r) at time i = row b M + r of
+ *   sda_randn_rows(out[B M][d], seed, row0, draw = draw0 + i): it depends on neither the launch geometry nor M' > r, B' > b.
+ *   One sample per lane; a tile of times is staged in LDS and written as contiguous rows.
+ * sda_lgss_score_factor / sda_lgss_score: with Lambda the block-tridiagonal precision of (x_0 .. x_T) (diagonal blocks
+ *   P0^-1 + A^T Q^-1 A, Q^-1 + A^T Q^-1 A, .., Q^-1; off-diagonal -A^T Q^-1) and m its mean, x(t) ~ N(mu m, mu^2 Lambda^-1 +
+ *   sigma^2 I) and eps = sigma Lambda (mu^2 I + sigma^2 Lambda)^-1 (x - mu m).  `prec` (device, float64,
+ *   sda_lgss_score_doubles(d, T, 0) values) = {P0^-1, Q^-1, A^T Q^-1, A^T Q^-1 A, m[T+1][d]}; coef (device, fp32) = {mu, sigma}.
+ *   factor: one wave, block Cholesky (block Thomas order) of mu^2 I + sigma^2 Lambda into work (sda_lgss_score_doubles(d, T, 1)
+ *   doubles).  score: x[n][T+1][d] fp32 -> out likewise, one trajectory per lane, float64 sweeps, ywork: n (T+1) d doubles.
+ *   zero_mean != 0 takes m = 0 and mu out of the right-hand side: Lambda and the solve commute, the Jacobian is symmetric, and
+ *   this is the vector-Jacobian product on a cotangent x.
+ * Bad arguments (null pointers, d or k outside 1..8, T < 0, counts < 1) are refused on the host before any launch.
+ * ------------------------------------------------------------------------------------------ */
+#define SDA_LGSS_MAXD 8
+typedef struct {
+    int32_t d;
+    float A[SDA_LGSS_MAXD][SDA_LGSS_MAXD];
+    float b[SDA_LGSS_MAXD];
+    float Lq[SDA_LGSS_MAXD][SDA_LGSS_MAXD];     /* lower Cholesky factor of Q */
+} sda_lgss_model;
+typedef struct {
+    int32_t d, k;
+    double A[SDA_LGSS_MAXD][SDA_LGSS_MAXD], b[SDA_LGSS_MAXD], Q[SDA_LGSS_MAXD][SDA_LGSS_MAXD];
+    double m0[SDA_LGSS_MAXD], P0[SDA_LGSS_MAXD][SDA_LGSS_MAXD];     /* the law of the state at time index 0 */
+    double H[SDA_LGSS_MAXD][SDA_LGSS_MAXD], c[SDA_LGSS_MAXD];       /* H is k x d */
+    double sigma;
+} sda_lgss_model64;
+int sda_lgss_advance(const sda_lgss_model* model, const float* x_in, int64_t in_sp, int m, int transitions, int every, float* out,
+                     int64_t out_st, int64_t out_sp, uint64_t seed, int64_t row0, int64_t draw0, void* stream);
+int64_t sda_lgss_table_doubles(int d, int k, int T);
+int sda_lgss_tables(const sda_lgss_model64* model, int step, int N, double* table);
+int sda_lgss_filter(const sda_lgss_model64* model, const double* table, int step, int N, const float* y, int B, double* mean,
+                    double* logz, void* stream);
+int sda_lgss_sample(const sda_lgss_model64* model, const double* table, const double* mean, int T, int B, int M, uint64_t seed,
+                    int64_t row0, int64_t draw0, float* out, void* stream);
+int64_t sda_lgss_score_doubles(int d, int T, int which);
+int sda_lgss_score_factor(int d, int T, const double* prec, const float* coef, double* work, void* stream);
+int sda_lgss_score(int d, int T, const double* prec, const float* coef, const double* work, const float* x, int n, int zero_mean,
+                   double* ywork, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -5,7 +5,7 @@ loading raises -- nothing in sda_amd computes on the CPU or through the oracle.
 """
 import ctypes
 import os
-from ctypes import POINTER, Structure, c_float, c_int, c_int32, c_int64, c_uint32, c_uint64, c_void_p
+from ctypes import POINTER, Structure, c_double, c_float, c_int, c_int32, c_int64, c_uint32, c_uint64, c_void_p
 
 import torch  # noqa: F401  -- must be imported first: the library binds to the HIP runtime torch loaded
 
@@ -282,6 +282,23 @@ class KflowModel(Structure):
     _fields_ = [('n', c_int32), ('steps', c_int32), ('delta', c_float), ('nu', c_float), ('hm', c_fp), ('inv', c_fp), ('forcing', c_fp)]
 
 
+LGSS_MAXD = 8
+
+
+class LgssModel(Structure):
+    """Mirror of `struct sda_lgss_model` (include/sda_hip.h)."""
+    _fields_ = [('d', c_int32), ('A', c_float * LGSS_MAXD * LGSS_MAXD), ('b', c_float * LGSS_MAXD), ('Lq', c_float * LGSS_MAXD * LGSS_MAXD)]
+
+
+class LgssModel64(Structure):
+    """Mirror of `struct sda_lgss_model64` (include/sda_hip.h)."""
+    _fields_ = [('d', c_int32), ('k', c_int32),
+                ('A', c_double * LGSS_MAXD * LGSS_MAXD), ('b', c_double * LGSS_MAXD), ('Q', c_double * LGSS_MAXD * LGSS_MAXD),
+                ('m0', c_double * LGSS_MAXD), ('P0', c_double * LGSS_MAXD * LGSS_MAXD),
+                ('H', c_double * LGSS_MAXD * LGSS_MAXD), ('c', c_double * LGSS_MAXD),
+                ('sigma', c_double)]
+
+
 SIGNATURES = {
     'sda_abi_version': (c_int, []),
     'sda_conv_igemm': (c_int, [POINTER(ConvDesc), c_void_p]),
@@ -410,6 +427,16 @@ SIGNATURES = {
     'sda_kfvjp_work_floats': (c_int64, [c_int, c_int, c_int]),
     'sda_kfvjp_explicit': (c_int, [POINTER(KflowModel), c_fp, c_int64, c_fp, c_int64, c_int, c_fp, c_void_p]),
     'sda_kfvjp_transition': (c_int, [POINTER(KflowModel), c_fp, c_int64, c_fp, c_int64, c_int, c_fp, c_fp, c_void_p]),
+    # linear-Gaussian state space (csrc/lgss.hip); sda_lgss_tables takes a HOST table
+    'sda_lgss_advance': (c_int, [POINTER(LgssModel), c_fp, c_int64, c_int, c_int, c_int, c_fp, c_int64, c_int64, c_uint64, c_int64, c_int64,
+                                 c_void_p]),
+    'sda_lgss_table_doubles': (c_int64, [c_int, c_int, c_int]),
+    'sda_lgss_tables': (c_int, [POINTER(LgssModel64), c_int, c_int, c_void_p]),
+    'sda_lgss_filter': (c_int, [POINTER(LgssModel64), c_fp, c_int, c_int, c_fp, c_int, c_fp, c_fp, c_void_p]),
+    'sda_lgss_sample': (c_int, [POINTER(LgssModel64), c_fp, c_fp, c_int, c_int, c_int, c_uint64, c_int64, c_int64, c_fp, c_void_p]),
+    'sda_lgss_score_doubles': (c_int64, [c_int, c_int, c_int]),
+    'sda_lgss_score_factor': (c_int, [c_int, c_int, c_fp, c_fp, c_fp, c_void_p]),
+    'sda_lgss_score': (c_int, [c_int, c_int, c_fp, c_fp, c_fp, c_fp, c_int, c_int, c_fp, c_fp, c_void_p]),
 }
 
 _lib = None

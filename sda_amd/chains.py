@@ -5,7 +5,9 @@ constructor arguments and methods.  ``transition`` and ``trajectory`` of the thr
 ``sda_chain_advance`` (csrc/chain.hip) whatever the length; a user subclass of ``DiscreteODE`` with its own ``f`` -- and any input
 that requires grad -- runs the reference's torch-ops ``rk4`` instead (correct, not fused).  ``KolmogorovFlow`` is the
 incompressible-flow simulator the reference obtains from jax-cfd, here as five launches per sub-step (csrc/kflow.hip: one stencil
-kernel and four products with the Hartley matrix on the fp32 matrix cores); see the class.  ``DampedSpring`` is not rebuilt.
+kernel and four products with the Hartley matrix on the fp32 matrix cores); see the class.  ``DampedSpring`` (sda/mcs.py:60-82) is a
+``LinearGaussian`` chain: one launch of ``sda_lgss_advance`` (csrc/lgss.hip) whatever the length, with the noise convention below; its
+exact posterior and exact score live in ``sda_amd.experiments.spring``.
 
 Noise.  The noisy chain draws one 63-bit seed per call from torch's default CPU generator (``torch.manual_seed`` reproduces a
 run) unless ``seed=`` is given, and advances a draw counter by the number of transitions, so successive calls never reuse
@@ -25,8 +27,8 @@ from torch.distributions import MultivariateNormal, Normal
 from . import ops
 from ._lib import CHAIN_MAXOBS, SdaHipError
 
-__all__ = ['MarkovChain', 'DiscreteODE', 'Lorenz63', 'NoisyLorenz63', 'Lorenz96', 'LotkaVolterra', 'KolmogorovFlow', 'AffineObservation',
-           'probe_affine', 'bpf_fused', 'install']
+__all__ = ['MarkovChain', 'DiscreteODE', 'Lorenz63', 'NoisyLorenz63', 'Lorenz96', 'LotkaVolterra', 'KolmogorovFlow', 'LinearGaussian',
+           'DampedSpring', 'AffineObservation', 'probe_affine', 'probe_linear', 'bpf_fused', 'install']
 
 
 def _draw_seed() -> int:
@@ -486,6 +488,89 @@ def _mcs():
     return importlib.import_module(__package__ + '.mcs')
 
 
+# ---------------------------------------------------------------- linear-Gaussian chains
+class LinearGaussian(MarkovChain):
+    r"""x_0 ~ N(m0, S0), x_{i+1} = A x_i + b + w_i, w_i ~ N(0, Q) with Q symmetric positive definite and 1 <= d <= 8.
+
+    ``transition`` and ``trajectory`` are ONE launch of ``sda_lgss_advance`` whatever the length (fp32; the normal added to state
+    ``r`` at draw ``t`` is ``Lq`` times row ``r`` of ``ops.randn_rows(.., seed, 0, draw=t)``, ``Lq`` the Cholesky factor of Q), with
+    the seed and draw counter of ``NoisyLorenz63``.  An input that requires grad takes the reference's torch expression; a CPU
+    tensor raises, as for the other built-in chains."""
+
+    def __init__(self, A, b, Q, m0, S0):
+        super().__init__()
+        as32 = lambda v: torch.as_tensor(v, dtype=torch.float32).detach().clone().cpu()
+        self.A, self.b, self.Sigma_x = as32(A), as32(b), as32(Q)
+        self.mu_0, self.Sigma_0 = as32(m0), as32(S0)
+        self.d = self.b.numel()
+        self._model = ops.lgss_model(self.A.double(), self.b.double(), self.Sigma_x.double())
+        self._draw = 0
+
+    def model(self):
+        return self._model
+
+    def prior(self, shape: Size = (), *, device=None) -> Tensor:
+        return MultivariateNormal(self.mu_0, self.Sigma_0).sample(shape).to(device)
+
+    def _fused(self, x: Tensor) -> bool:
+        return not (torch.is_grad_enabled() and x.requires_grad)
+
+    def moments(self, x: Tensor) -> Tuple[Tensor, Tensor]:
+        r"""Mean and covariance of p(x_{i+1} | x_i = x), in torch ops on x's device."""
+        return x @ self.A.to(x).T + self.b.to(x), self.Sigma_x.to(x)
+
+    def _advance(self, x: Tensor, length: int, every: bool, seed: Optional[int] = None) -> Tensor:
+        d = self.d
+        if x.shape[-1:] != (d,):
+            raise SdaHipError(f'{type(self).__name__}: states of shape {tuple(x.shape)}, expected (..., {d})')
+        ops._dev(x)
+        batch = x.shape[:-1]
+        flat = x.reshape(-1, d)
+        if flat.stride(-1) != 1:
+            flat = flat.contiguous()
+        m = flat.shape[0]
+        if length < 1 or m < 1:
+            raise SdaHipError(f'{type(self).__name__}: length {length}, {m} states')
+        draw0 = self._draw
+        seed = _draw_seed() if seed is None else int(seed)
+        self._draw += length
+        out = torch.empty((length, m, d) if every else (m, d), device=x.device, dtype=torch.float32)
+        ops.lgss_advance(self._model, flat, out, length, every=every, out_st=m * d, seed=seed, draw0=draw0)
+        return out.reshape((length, *batch, d) if every else (*batch, d))
+
+    def transition(self, x: Tensor, *, seed: Optional[int] = None) -> Tensor:
+        if self._fused(x):
+            return self._advance(x, 1, False, seed)
+        return MultivariateNormal(*self.moments(x)).sample()
+
+    def trajectory(self, x: Tensor, length: int, last: bool = False, *, seed: Optional[int] = None) -> Tensor:
+        if self._fused(x) and length >= 1:
+            return self._advance(x, length, not last, seed)
+        return MarkovChain.trajectory(self, x, length, last)
+
+    def log_prob(self, x1: Tensor, x2: Tensor) -> Tensor:
+        return MultivariateNormal(*self.moments(x1)).log_prob(x2)
+
+
+class DampedSpring(LinearGaussian):
+    r"""Linearized dynamics of a mass attached to a spring, subject to wind and drag (sda/mcs.py:60-82)."""
+
+    def __init__(self, dt: float = 0.01):
+        self.dt = dt
+        super().__init__(
+            A=torch.tensor([
+                [1.0, dt, dt**2 / 2, 0.0],
+                [0.0, 1.0, dt, 0.0],
+                [-0.5, -0.1, 0.0, 0.2],
+                [0.0, 0.0, 0.0, 0.99],
+            ]),
+            b=torch.tensor([0.0, 0.0, 0.0, 0.0]),
+            Q=torch.tensor([0.1, 0.1, 0.1, 1.0]).diag() * dt,
+            m0=torch.tensor([1.0, 0.0, 0.0, 0.0]),
+            S0=torch.tensor([1.0, 1.0, 1.0, 1.0]).diag(),
+        )
+
+
 # ---------------------------------------------------------------- observation operators the fused filter understands
 class AffineObservation:
     r"""A(x) = (x[..., index] - shift) / scale: each output is an affine function of ONE state component."""
@@ -537,6 +622,33 @@ def probe_affine(A: Callable[[Tensor], Tensor], chain: MarkovChain, d: int, rtol
         return None
 
 
+def probe_linear(A: Callable[[Tensor], Tensor], chain: MarkovChain, d: int, rtol: float = 1e-6) -> Optional[Tuple[Tensor, Tensor]]:
+    """Recover (H, c), float64 (k, d) and (k,), with A(x) = H x + c from a callable, or None: evaluate A at 0 and at the d unit vectors
+    (float64, host), then confirm on 64 prior-scale random states to `rtol` of the largest output.  Unlike ``probe_affine`` an output
+    may depend on every component (a dense H); 1 <= k <= 8.  torch's global generator is left as it was."""
+    try:
+        with torch.no_grad():
+            c = A(torch.zeros(d, dtype=torch.float64))
+            if c.dim() != 1 or not 1 <= c.numel() <= 8 or not c.is_floating_point():
+                return None
+            cols = A(torch.eye(d, dtype=torch.float64))
+            if cols.shape != (d, c.numel()):
+                return None
+            H = (cols - c).T.contiguous().double()
+            c = c.double()
+            if not (torch.isfinite(H).all() and torch.isfinite(c).all()):
+                return None
+            with torch.random.fork_rng(devices=[]):
+                torch.manual_seed(0)
+                x = chain.prior((64,)).double().cpu()
+            got, want = A(x), x @ H.T + c
+            if got.shape != want.shape or not ((got - want).abs().max() <= rtol * want.abs().max().clamp_min(1e-300)):
+                return None
+            return H, c
+    except Exception:  # noqa: BLE001 -- a callable that cannot take these inputs is simply not recognised
+        return None
+
+
 def bpf_fused(chain: DiscreteODE, x: Tensor, y: Tensor, obs: AffineObservation, sigma: float, step: int = 1, *,
               seed: Optional[int] = None, record: Optional[dict] = None) -> Tensor:
     r"""Bootstrap particle filter (sda/utils.py:168-200) with ``chain.transition`` and the Gaussian likelihood
@@ -582,6 +694,6 @@ def install() -> None:
     call it before a driver's ``from sda.mcs import *``."""
     import importlib
     mcs = importlib.import_module(__package__ + '.mcs')
-    for name in ('MarkovChain', 'DiscreteODE', 'Lorenz63', 'NoisyLorenz63', 'Lorenz96', 'LotkaVolterra', 'KolmogorovFlow'):
+    for name in ('MarkovChain', 'DiscreteODE', 'Lorenz63', 'NoisyLorenz63', 'Lorenz96', 'LotkaVolterra', 'KolmogorovFlow', 'DampedSpring'):
         setattr(mcs, name, globals()[name])
     mcs.SOURCE = __name__

@@ -1515,3 +1515,172 @@ def kflow_transition_vjp(model, x0: Tensor, g: Tensor) -> Tensor:
     _lib.check(lib.sda_kfvjp_transition(ctypes.byref(model), f.data_ptr(), sb, gf.data_ptr(), gsb, nb, out.data_ptr(), work.data_ptr(),
                                         _stream()), 'sda_kfvjp_transition')
     return out.reshape(x0.shape)
+
+
+# ---------------------------------------------------------------- linear-Gaussian state space (csrc/lgss.hip)
+def _lgss_f64(a, shape, what: str):
+    t = torch.as_tensor(a, dtype=torch.float64, device='cpu') if not torch.is_tensor(a) else a.detach().to('cpu', torch.float64)
+    if tuple(t.shape) != tuple(shape) or not torch.isfinite(t).all():
+        raise _lib.SdaHipError(f'lgss: {what} of shape {tuple(t.shape)}, expected finite {tuple(shape)}')
+    return t
+
+
+def _lgss_fill(field, t):
+    if t.dim() == 1:
+        for i, v in enumerate(t.tolist()):
+            field[i] = v
+    else:
+        for i, row in enumerate(t.tolist()):
+            for j, v in enumerate(row):
+                field[i][j] = v
+
+
+def lgss_model(A, b, Q) -> '_lib.LgssModel':
+    """`sda_lgss_model` of x' = A x + b + w, w ~ N(0, Q): fp32 A, b and the lower Cholesky factor of Q (formed in float64, rounded once)."""
+    b = torch.as_tensor(b)
+    d = b.numel()
+    if not 1 <= d <= _lib.LGSS_MAXD:
+        raise _lib.SdaHipError(f'lgss_model: d = {d}, the kernels serve 1 <= d <= {_lib.LGSS_MAXD}')
+    A, b, Q = _lgss_f64(A, (d, d), 'A'), _lgss_f64(b, (d,), 'b'), _lgss_f64(Q, (d, d), 'Q')
+    Lq, info = torch.linalg.cholesky_ex(Q)
+    if int(info) != 0:
+        raise _lib.SdaHipError('lgss_model: Q is not positive definite')
+    m = _lib.LgssModel()
+    m.d = d
+    _lgss_fill(m.A, A)
+    _lgss_fill(m.b, b)
+    _lgss_fill(m.Lq, Lq)
+    return m
+
+
+def lgss_model64(A, b, Q, m0, P0, H, c, sigma: float) -> '_lib.LgssModel64':
+    """`sda_lgss_model64`: the chain, the law N(m0, P0) of the state at time index 0 and the observation y = H x + c + N(0, sigma^2 I)."""
+    b = torch.as_tensor(b)
+    c = torch.as_tensor(c)
+    d, k = b.numel(), c.numel()
+    if not (1 <= d <= _lib.LGSS_MAXD and 1 <= k <= _lib.LGSS_MAXD) or not float(sigma) > 0:
+        raise _lib.SdaHipError(f'lgss_model64: d = {d}, k = {k}, sigma = {sigma}: the kernels serve 1 <= d, k <= {_lib.LGSS_MAXD}, sigma > 0')
+    m = _lib.LgssModel64()
+    m.d, m.k, m.sigma = d, k, float(sigma)
+    for name, val, shape in (('A', A, (d, d)), ('b', b, (d,)), ('Q', Q, (d, d)), ('m0', m0, (d,)), ('P0', P0, (d, d)), ('H', H, (k, d)),
+                             ('c', c, (k,))):
+        _lgss_fill(getattr(m, name), _lgss_f64(val, shape, name))
+    return m
+
+
+def lgss_advance(model, x: Tensor, out: Tensor, transitions: int, *, every: bool = False, out_st: int = 0, out_sp: Optional[int] = None,
+                 seed: int = 0, row0: int = 0, draw0: int = 0) -> Tensor:
+    """`transitions` transitions of x (m, d) in one launch; `out` and its strides as in ``chain_advance``."""
+    _dev(x, out)
+    m, d = x.shape
+    if x.dim() != 2 or x.stride(1) != 1 or d != model.d:
+        raise _lib.SdaHipError(f'lgss_advance: states {tuple(x.shape)} (strides {x.stride()}) for a {model.d}-component chain')
+    out_sp = d if out_sp is None else out_sp
+    last = (transitions - 1) * out_st if every else 0
+    if out_sp < d or (every and out_st < 0) or last + (m - 1) * out_sp + d > out.numel() or not out.is_contiguous():
+        raise _lib.SdaHipError('lgss_advance: the output strides leave the output tensor')
+    _lib.check(_lib.load().sda_lgss_advance(ctypes.byref(model), x.data_ptr(), x.stride(0) if m > 1 else d, m, transitions, int(every),
+                                            out.data_ptr(), out_st, out_sp, seed & 0xffffffffffffffff, row0, draw0, _stream()),
+               'sda_lgss_advance')
+    return out
+
+
+def lgss_tables(model64, step: int, n_obs: int, device=None, lib=None) -> Tensor:
+    """The Kalman / backward-sampler tables of `n_obs` observations `step` apart (host call, float64), uploaded to `device` if given.
+    ``lib``: another library exporting ``sda_lgss_tables`` (the host replay of the tests)."""
+    lib = _lib.load() if lib is None else lib
+    T = (n_obs - 1) * step
+    n = lib.sda_lgss_table_doubles(model64.d, model64.k, T) if n_obs >= 1 and step >= 1 else -1
+    if n < 0:
+        raise _lib.SdaHipError(f'lgss_tables: {n_obs} observations, step {step}')
+    table = torch.empty(n, dtype=torch.float64)
+    _lib.check(lib.sda_lgss_tables(ctypes.byref(model64), step, n_obs, table.data_ptr()), 'sda_lgss_tables (a covariance is not positive definite?)')
+    return table if device is None else table.to(device)
+
+
+def _lgss_table_check(model64, table: Tensor, T: int, what: str):
+    want = _lib.load().sda_lgss_table_doubles(model64.d, model64.k, T)
+    if not table.is_cuda or table.dtype != torch.float64 or not table.is_contiguous() or table.numel() != want:
+        raise _lib.SdaHipError(f'{what}: the table must be {want} contiguous float64 values on the device')
+
+
+def lgss_filter(model64, table: Tensor, y: Tensor, step: int):
+    """y (B, N, k) fp32 -> (mean (B, T + 1, d), logz (B,)), float64: the filtered means and log p(y)."""
+    _dev(y)
+    if y.dim() != 3 or y.shape[2] != model64.k or y.shape[0] < 1 or y.shape[1] < 1 or step < 1:
+        raise _lib.SdaHipError(f'lgss_filter: observations {tuple(y.shape)} for k = {model64.k}, step {step}')
+    y = y.contiguous()
+    B, N = y.shape[:2]
+    T = (N - 1) * step
+    _lgss_table_check(model64, table, T, 'lgss_filter')
+    mean = torch.empty(B, T + 1, model64.d, device=y.device, dtype=torch.float64)
+    logz = torch.empty(B, device=y.device, dtype=torch.float64)
+    _lib.check(_lib.load().sda_lgss_filter(ctypes.byref(model64), table.data_ptr(), step, N, y.data_ptr(), B, mean.data_ptr(),
+                                           logz.data_ptr(), _stream()), 'sda_lgss_filter')
+    return mean, logz
+
+
+def lgss_sample(model64, table: Tensor, mean: Tensor, samples: int, seed: int, row0: int = 0, draw0: int = 0) -> Tensor:
+    """mean (B, T + 1, d) float64 -> (B, samples, T + 1, d) fp32 exact posterior trajectories; sample (b, r) at time i uses row
+    row0 + b * samples + r of the keyed normals at draw0 + i."""
+    if mean.dim() != 3 or not mean.is_cuda or mean.dtype != torch.float64 or not mean.is_contiguous() or mean.shape[2] != model64.d \
+            or samples < 1:
+        raise _lib.SdaHipError(f'lgss_sample: means {tuple(mean.shape)} ({mean.dtype}) for d = {model64.d}, {samples} samples')
+    B, T = mean.shape[0], mean.shape[1] - 1
+    _lgss_table_check(model64, table, T, 'lgss_sample')
+    out = torch.empty(B, samples, T + 1, model64.d, device=mean.device, dtype=torch.float32)
+    _lib.check(_lib.load().sda_lgss_sample(ctypes.byref(model64), table.data_ptr(), mean.data_ptr(), T, B, samples,
+                                           seed & 0xffffffffffffffff, row0, draw0, out.data_ptr(), _stream()), 'sda_lgss_sample')
+    return out
+
+
+def lgss_score_prec(A, b, Q, m0, P0, T: int) -> Tensor:
+    """The `prec` operand of the exact score (host, float64): {P0^-1, Q^-1, A^T Q^-1, A^T Q^-1 A, mean[T + 1][d]} of the joint law of
+    (x_0 .. x_T), x_0 ~ N(m0, P0)."""
+    b = torch.as_tensor(b)
+    d = b.numel()
+    A, b, Q = _lgss_f64(A, (d, d), 'A'), _lgss_f64(b, (d,), 'b'), _lgss_f64(Q, (d, d), 'Q')
+    m0, P0 = _lgss_f64(m0, (d,), 'm0'), _lgss_f64(P0, (d, d), 'P0')
+    Qi, Si = torch.linalg.inv(Q), torch.linalg.inv(P0)
+    Qi, Si = 0.5 * (Qi + Qi.T), 0.5 * (Si + Si.T)
+    AtQi = A.T @ Qi
+    AtQiA = AtQi @ A
+    mean = [m0]
+    for _ in range(T):
+        mean.append(A @ mean[-1] + b)
+    return torch.cat([Si.reshape(-1), Qi.reshape(-1), AtQi.reshape(-1), (0.5 * (AtQiA + AtQiA.T)).reshape(-1), torch.stack(mean).reshape(-1)])
+
+
+def _lgss_score_check(d: int, T: int, prec: Tensor, coef: Tensor, work: Tensor, what: str):
+    lib = _lib.load()
+    if not 1 <= d <= _lib.LGSS_MAXD or T < 0:
+        raise _lib.SdaHipError(f'{what}: d = {d}, T = {T}')
+    for t, n, dt, name in ((prec, lib.sda_lgss_score_doubles(d, T, 0), torch.float64, 'prec'), (coef, 2, torch.float32, 'coef'),
+                           (work, lib.sda_lgss_score_doubles(d, T, 1), torch.float64, 'work')):
+        if not t.is_cuda or t.dtype != dt or not t.is_contiguous() or t.numel() != n:
+            raise _lib.SdaHipError(f'{what}: {name} must be {n} contiguous {dt} values on the device')
+
+
+def lgss_score_factor(d: int, T: int, prec: Tensor, coef: Tensor, work: Optional[Tensor] = None) -> Tensor:
+    """Block Cholesky of mu^2 I + sigma^2 Lambda, {mu, sigma} = coef read on the device (a captured step replays)."""
+    if work is None:
+        work = torch.empty(_lib.load().sda_lgss_score_doubles(d, T, 1), device=prec.device, dtype=torch.float64)
+    _lgss_score_check(d, T, prec, coef, work, 'lgss_score_factor')
+    _lib.check(_lib.load().sda_lgss_score_factor(d, T, prec.data_ptr(), coef.data_ptr(), work.data_ptr(), _stream()),
+               'sda_lgss_score_factor')
+    return work
+
+
+def lgss_score(d: int, T: int, prec: Tensor, coef: Tensor, work: Tensor, x: Tensor, zero_mean: bool = False) -> Tensor:
+    """x (n, T + 1, d) fp32 -> eps likewise.  zero_mean: the same map around m = 0, which is also its own transpose (the VJP)."""
+    _dev(x)
+    _lgss_score_check(d, T, prec, coef, work, 'lgss_score')
+    if x.dim() != 3 or tuple(x.shape[1:]) != (T + 1, d) or x.shape[0] < 1:
+        raise _lib.SdaHipError(f'lgss_score: trajectories {tuple(x.shape)}, expected (n, {T + 1}, {d})')
+    x = x.contiguous()
+    n = x.shape[0]
+    ywork = torch.empty(n * (T + 1) * d, device=x.device, dtype=torch.float64)
+    out = torch.empty_like(x)
+    _lib.check(_lib.load().sda_lgss_score(d, T, prec.data_ptr(), coef.data_ptr(), work.data_ptr(), x.data_ptr(), n, int(zero_mean),
+                                          ywork.data_ptr(), out.data_ptr(), _stream()), 'sda_lgss_score')
+    return out
