@@ -402,6 +402,10 @@ int sda_step1d_prologue(const float* table, int row_len, int64_t* istep, const f
                         const float* freqs, int nf, const float* w0, const float* b0, int hidden, const float* w2, const float* b2, int e,
                         const float* wp, const float* bp, int cp,
                         float* out_coef, int64_t* out_step, float* mod, void* stream);
+/* Which kernel sda_step1d_prologue launches for these sizes and weight addresses (host, no launch, nothing dereferenced): 1 = staged
+ * (the three weight matrices copied into LDS first: power-of-two row lengths, 2 nf >= 8, 16-byte aligned matrices, at most 140 KiB and
+ * 8192 16-byte loads), 0 = unstaged (rows read from global memory), or the SDA_E_* that sda_step1d_prologue returns for them. */
+int sda_step1d_prologue_path(int nf, int hidden, int e, int cp, const float* w0, const float* w2, const float* wp);
 /* sda_pc_correct with z = the row-keyed N(0, 1) draw of sda_randn_rows generated in the kernel (same Philox counters: identical
  * values), draw index = draw_dev[0] * draw_mul + draw_add  (sda/score.py:257-261). */
 int sda_pc_correct_keyed(float* x, const float* eps, int b, int64_t per_sample, const float* partial, int nchunk, float tau,

@@ -319,6 +319,7 @@ SIGNATURES = {
     'sda_net1d_pack': (c_int, [POINTER(Net1dPackDesc), c_void_p]),
     'sda_step1d_prologue': (c_int, [c_fp, c_int, c_fp, c_fp, c_int, c_int, c_float, c_float, c_int, c_fp, c_int, c_fp, c_fp, c_int,
                                     c_fp, c_fp, c_int, c_fp, c_fp, c_int, c_fp, c_fp, c_fp, c_void_p]),
+    'sda_step1d_prologue_path': (c_int, [c_int, c_int, c_int, c_int, c_fp, c_fp, c_fp]),
     'sda_pc_correct_keyed': (c_int, [c_fp, c_fp, c_int, c_int64, c_fp, c_int, c_float, c_float, c_fp, c_uint64, c_int64, c_fp, c_int64,
                                      c_int64, c_void_p]),
     'sda_conv_parity4': (c_int, [POINTER(ConvDesc), c_void_p]),

@@ -95,15 +95,8 @@ __global__ __launch_bounds__(S1_THREADS) void step1d_prologue_kernel(
         if (table) t = table[step * row_len + tid];       // {t, t - dt}
         else t = t_dev[tid];
         tv[tid] = t;
-        // mu, sigma: vp_schedule_kernel's arithmetic
-        float a;
-        if (alpha_kind == 0) a = 1.0f - (1.0f - eta) * t;
-        else if (alpha_kind == 1) { const float c = cosf(k * t); a = c * c; }
-        else a = expf(k * (t * t));
-        float sg;
-        if (sigma_kind == 0) sg = sqrtf((1.0f - a * a) + eta * eta);
-        else if (sigma_kind == 1) sg = (1.0f - a * a) + eta;
-        else sg = (1.0f - a) + eta;
+        float a, sg;
+        sda_vp_mu_sigma(t, alpha_kind, eta, k, sigma_kind, a, sg);       // (sda_common.hpp: vp_schedule_kernel's arithmetic)
         out_coef[2 * tid] = a;
         out_coef[2 * tid + 1] = sg;
         out_coef[7 + tid] = t;
@@ -222,31 +215,50 @@ __global__ __launch_bounds__(S1_THREADS) void step1d_prologue_kernel(
     if (table && tid == 0) istep[0] = step + 1;            // (after the read above: this workgroup is the step counter's only reader)
 }
 
-extern "C" int sda_step1d_prologue(const float* table, int row_len, int64_t* istep, const float* t_dev, int nt, int alpha_kind,
-                                   float eta, float k, int sigma_kind, const float* freqs, int nf, const float* w0, const float* b0,
-                                   int hidden, const float* w2, const float* b2, int e, const float* wp, const float* bp, int cp,
-                                   float* out_coef, int64_t* out_step, float* mod, void* stream) {
-    if (!freqs || !w0 || !b0 || !w2 || !b2 || !out_coef || !mod || nf <= 0 || hidden <= 0 || e <= 0 || cp < 0 || (cp > 0 && !wp))
-        return SDA_E_BADARG;
-    if (table ? (!istep || row_len < 5 || nt != 2) : (!t_dev || nt < 1 || nt > 2)) return SDA_E_BADARG;
-    if (alpha_kind < 0 || alpha_kind > 2 || sigma_kind < 0 || sigma_kind > 2) return SDA_E_BADARG;
+// dynamic LDS of the two variants: the staged biases + frequencies (both), and the padded weight copies on top (staged)
+static inline int64_t s1_vec_bytes(int nf, int hidden, int e, int cp) { return 4LL * ((int64_t)hidden + e + cp + nf); }
+static inline int64_t s1_staged_bytes(int nf, int hidden, int e, int cp) {
+    return s1_vec_bytes(nf, hidden, e, cp) +
+           4LL * ((int64_t)hidden * (2 * nf + S1_PAD) + (int64_t)e * (hidden + S1_PAD) + (int64_t)cp * (e + S1_PAD));
+}
+
+// Which kernel serves these sizes and weight addresses (host, no launch, nothing dereferenced): 1 staged, 0 unstaged, or the SDA_E_*
+// the launcher returns for them.  THE rule: sda_step1d_prologue calls it.
+extern "C" int sda_step1d_prologue_path(int nf, int hidden, int e, int cp, const float* w0, const float* w2, const float* wp) {
+    if (!w0 || !w2 || nf <= 0 || hidden <= 0 || e <= 0 || cp < 0 || (cp > 0 && !wp)) return SDA_E_BADARG;
     if (2 * nf > S1_MAX_FEAT || hidden > S1_MAX_HIDDEN || e > S1_MAX_E) return SDA_E_UNSUPPORTED;
     const int nin = 2 * nf;
-    const int64_t vecs = 4LL * (hidden + e + cp + nf);                                       // staged biases + frequencies (both variants)
-    const int64_t lds = vecs + 4LL * ((int64_t)hidden * (nin + S1_PAD) + (int64_t)e * (hidden + S1_PAD) + (int64_t)cp * (e + S1_PAD));
     const bool aligned = !(nin & 3) && !(hidden & 3) && !(e & 3) &&
                          !(((uintptr_t)w0 | (uintptr_t)w2 | (uintptr_t)(cp ? wp : w0)) & 15);
     const int64_t quads = ((int64_t)hidden * nin + (int64_t)e * hidden + (int64_t)cp * e) / 4;
     auto pow2 = [](int v) { return v > 0 && !(v & (v - 1)); };
-    if (aligned && lds <= 140 * 1024 && quads <= (int64_t)S1_STAGE_MAX * S1_THREADS && pow2(nin) && pow2(hidden) && pow2(e) && nin >= 8) {
+    if (aligned && s1_staged_bytes(nf, hidden, e, cp) <= 140 * 1024 && quads <= (int64_t)S1_STAGE_MAX * S1_THREADS && pow2(nin) &&
+        pow2(hidden) && pow2(e) && nin >= 8)
+        return 1;
+    if (s1_vec_bytes(nf, hidden, e, cp) > 48 * 1024) return SDA_E_UNSUPPORTED;
+    return 0;
+}
+
+extern "C" int sda_step1d_prologue(const float* table, int row_len, int64_t* istep, const float* t_dev, int nt, int alpha_kind,
+                                   float eta, float k, int sigma_kind, const float* freqs, int nf, const float* w0, const float* b0,
+                                   int hidden, const float* w2, const float* b2, int e, const float* wp, const float* bp, int cp,
+                                   float* out_coef, int64_t* out_step, float* mod, void* stream) {
+    // (every SDA_E_BADARG before the first SDA_E_UNSUPPORTED: the sizes and weight addresses are the pick function's to check)
+    if (!freqs || !b0 || !b2 || !out_coef || !mod) return SDA_E_BADARG;
+    if (table ? (!istep || row_len < 5 || nt != 2) : (!t_dev || nt < 1 || nt > 2)) return SDA_E_BADARG;
+    if (alpha_kind < 0 || alpha_kind > 2 || sigma_kind < 0 || sigma_kind > 2) return SDA_E_BADARG;
+    const int path = sda_step1d_prologue_path(nf, hidden, e, cp, w0, w2, wp);
+    if (path < 0) return path;
+    if (path == 1) {
         static bool raised[SDA_MAX_DEVICES];
         const int rc = sda_raise_dyn_lds(reinterpret_cast<const void*>(step1d_prologue_kernel<true>), 140 * 1024, raised);
         if (rc != SDA_OK) return rc;
-        hipLaunchKernelGGL(step1d_prologue_kernel<true>, dim3(1), dim3(S1_THREADS), (size_t)lds, (hipStream_t)stream, table, row_len, istep,
+        hipLaunchKernelGGL(step1d_prologue_kernel<true>, dim3(1), dim3(S1_THREADS), (size_t)s1_staged_bytes(nf, hidden, e, cp),
+                           (hipStream_t)stream, table, row_len, istep,
                            t_dev, nt, alpha_kind, eta, k, sigma_kind, freqs, nf, w0, b0, hidden, w2, b2, e, wp, bp, cp, out_coef, out_step,
                            mod);
     } else {
-        if (vecs > 48 * 1024) return SDA_E_UNSUPPORTED;
+        const int64_t vecs = s1_vec_bytes(nf, hidden, e, cp);
         hipLaunchKernelGGL(step1d_prologue_kernel<false>, dim3(1), dim3(S1_THREADS), (size_t)vecs, (hipStream_t)stream, table, row_len, istep, t_dev,
                            nt, alpha_kind, eta, k, sigma_kind, freqs, nf, w0, b0, hidden, w2, b2, e, wp, bp, cp, out_coef, out_step, mod);
     }
