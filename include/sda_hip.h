@@ -948,6 +948,46 @@ int sda_bpf_traceback(const float* S, int64_t s_st, int64_t s_sp, const int32_t*
                       void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Adjoint of the Markov chains (csrc/chain.hip; additive, ABI stays v14): what sda_amd.chains(grad='device') and
+ * experiments.lorenz.log_prior(grad='device') launch.  First order, fp32, gather form: every output element is written once by the
+ * lane that owns it, there are NO atomics, so a result is bitwise reproducible and the row of a particle (the gradient of a
+ * trajectory) does not depend on m (on b) or on the other rows.
+ *
+ * sda_chain_advance_vjp: gx[j] = (d sda_chain_advance / d x_in[j])^T g for all three kinds, ONE launch that walks the transitions
+ *   last to first.  Transition t starts from x_in (t = 0) or from states[(t - 1) * st_st + j * st_sp]: `states` is the forward's
+ *   every = 1 output addressed by the forward's strides (its last frame is not read; NULL is allowed when transitions == 1).  Noise
+ *   is additive: it is inside the stored states and absent from the Jacobian, so no seed is taken.  every = 1: g is
+ *   [transitions][m][d] (strides g_st / g_sp) and the running cotangent after transition t is g[t - 1] + J_t^T (running); every = 0:
+ *   g is [m][d], the cotangent of the last state.  An RK4 sub-step is reversed by recomputing its four stage points v_i and
+ *   applying J_f(v_i)^T; with model.steps > 1 the states inside a transition are recomputed from its start
+ *   state, the prefix again for every sub-step (O(steps^2) on d floats, any steps >= 1).  Geometry as sda_chain_advance: one particle
+ *   per lane with state and cotangent in registers (Lorenz-63, Lotka-Volterra: the Jacobian reuses the stage point's expf), or one
+ *   component per lane of a sub-group (Lorenz-96: (J^T g)_j = g_{j+1} x_{j+2} - g_{j-2} x_{j-1} + g_{j-1} (x_{j-2} - x_{j+1}) - g_j
+ *   by four more shuffles per stage).  anc != NULL (the particle filter's gather) is not differentiated: SDA_E_UNSUPPORTED.
+ * sda_chain_log_prob_grad: out[b] exactly as sda_chain_log_prob writes it, and grad[b][i][c] (contiguous, fp32) = d out[b] /
+ *   d x[b][i][c] = J_T(x_i)^T r_i - r_{i-1} with r_i = (x_{i+1} - T(x_i)) / noise_std^2, r_{-1} = 0 and no pair at i = len - 1; one
+ *   launch.  Kinds 0 and 1, as sda_chain_log_prob.  The upstream cotangent of out[b] is NOT an argument: the caller scales
+ *   grad[b] (one multiply), which keeps the kernel's result independent of what is done with the value.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct {
+    sda_chain_model model;
+    const float* x_in;      /* [m][d], particle stride in_sp */
+    int64_t in_sp;
+    const int32_t* anc;     /* must be NULL */
+    const float* states;    /* the forward's every = 1 output; NULL allowed when transitions == 1 */
+    int64_t st_st, st_sp;
+    const float* g;         /* output cotangent */
+    int64_t g_st, g_sp;
+    int32_t every;
+    int32_t m, transitions;
+    float* gx;              /* [m][d], particle stride gx_sp */
+    int64_t gx_sp;
+} sda_chain_vjp;
+int sda_chain_advance_vjp(const sda_chain_vjp* a, void* stream);
+int sda_chain_log_prob_grad(const sda_chain_model* model, const float* x, int b, int len, int64_t sb, int64_t sl, double* out,
+                            float* grad, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Kolmogorov flow (csrc/kflow.hip; additive, ABI stays v14): the simulator behind sda/mcs.py:244-338.  The reference only CALLS
  * jax-cfd, so the scheme (tests/kflow_ref.py) is this project's restatement of semi_implicit_navier_stokes
  * with its defaults: faithful, not pinned to a reference output.

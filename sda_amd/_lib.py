@@ -277,6 +277,19 @@ class ChainAdv(Structure):
     ]
 
 
+class ChainVjp(Structure):
+    """Mirror of `struct sda_chain_vjp` (include/sda_hip.h)."""
+    _fields_ = [
+        ('model', ChainModel),
+        ('x_in', c_fp), ('in_sp', c_int64), ('anc', c_fp),
+        ('states', c_fp), ('st_st', c_int64), ('st_sp', c_int64),
+        ('g', c_fp), ('g_st', c_int64), ('g_sp', c_int64),
+        ('every', c_int32),
+        ('m', c_int32), ('transitions', c_int32),
+        ('gx', c_fp), ('gx_sp', c_int64),
+    ]
+
+
 class KflowModel(Structure):
     """Mirror of `struct sda_kflow_model` (include/sda_hip.h)."""
     _fields_ = [('n', c_int32), ('steps', c_int32), ('delta', c_float), ('nu', c_float), ('hm', c_fp), ('inv', c_fp), ('forcing', c_fp)]
@@ -417,6 +430,8 @@ SIGNATURES = {
     'sda_bpf_cdf': (c_int, [c_fp, c_int, c_fp, c_int, c_fp, c_fp, c_fp, c_void_p]),
     'sda_bpf_resample': (c_int, [c_fp, c_int, c_uint64, c_int64, c_fp, c_void_p]),
     'sda_bpf_traceback': (c_int, [c_fp, c_int64, c_int64, c_fp, c_int, c_int, c_int, c_int, c_fp, c_void_p]),
+    'sda_chain_advance_vjp': (c_int, [POINTER(ChainVjp), c_void_p]),
+    'sda_chain_log_prob_grad': (c_int, [POINTER(ChainModel), c_fp, c_int, c_int, c_int64, c_int64, c_fp, c_fp, c_void_p]),
     'sda_pool3d_sum': (c_int, [c_fp, c_int64, c_int, c_int, c_int, c_int, c_int, c_int, c_fp, c_void_p]),
     'sda_kflow_serves': (c_int, [c_int]),
     'sda_kflow_work_floats': (c_int64, [c_int, c_int]),

@@ -3,7 +3,9 @@ r"""Markov chains of the reference (sda/mcs.py:22-241) on the device, and the fu
 ``MarkovChain``, ``DiscreteODE``, ``Lorenz63``, ``NoisyLorenz63``, ``Lorenz96`` and ``LotkaVolterra`` keep the reference's
 constructor arguments and methods.  ``transition`` and ``trajectory`` of the three built-in systems are ONE launch of
 ``sda_chain_advance`` (csrc/chain.hip) whatever the length; a user subclass of ``DiscreteODE`` with its own ``f`` -- and any input
-that requires grad -- runs the reference's torch-ops ``rk4`` instead (correct, not fused).  ``KolmogorovFlow`` is the
+that requires grad -- runs the reference's torch-ops ``rk4`` instead (correct, not fused), unless the chain was built with
+``grad='device'``: then a float32 device input that requires grad keeps the forward launch and gets its gradient from ONE launch of
+``sda_chain_advance_vjp`` (``_ChainAdvance``; ``LAST_CHAIN_GRAD_ROUTE`` records the route of every call).  ``KolmogorovFlow`` is the
 incompressible-flow simulator the reference obtains from jax-cfd, here as five launches per sub-step (csrc/kflow.hip: one stencil
 kernel and four products with the Hartley matrix on the fp32 matrix cores); see the class.  ``DampedSpring`` (sda/mcs.py:60-82) is a
 ``LinearGaussian`` chain: one launch of ``sda_lgss_advance`` (csrc/lgss.hip) whatever the length, with the noise convention below; its
@@ -35,6 +37,11 @@ def _draw_seed() -> int:
     return int(torch.randint(0, 2 ** 63 - 1, (), dtype=torch.int64))
 
 
+#: gradient route of the last ``transition`` / ``trajectory`` / ``moments`` call of a ``DiscreteODE``: 'device' (the kernel and its
+#: adjoint), 'torch' (torch autograd through the torch-ops rk4), or None when the call's input did not require grad
+LAST_CHAIN_GRAD_ROUTE = None
+
+
 class MarkovChain(abc.ABC):
     r"""Abstract first-order time-invariant Markov chain (sda/mcs.py:22-57)."""
 
@@ -59,14 +66,49 @@ class MarkovChain(abc.ABC):
         return torch.stack(X)
 
 
+class _ChainAdvance(torch.autograd.Function):
+    """``ops.chain_advance`` with its adjoint.  Forward is the no-grad launch itself.  Backward is one ``ops.chain_advance_vjp``
+    launch over the states each transition started from: the kept frames when the caller asked for them; for ``last`` the forward is
+    run again with every frame kept (same seed and first draw, so the noisy chain repeats its noise) into a scratch slab."""
+
+    @staticmethod
+    def forward(ctx, flat, model, length, every, seed, draw0):
+        m, d = flat.shape
+        out = torch.empty((length, m, d) if every else (m, d), device=flat.device, dtype=torch.float32)
+        ops.chain_advance(model, flat, out, length, every=every, out_st=m * d, seed=seed, draw0=draw0)
+        ctx.model, ctx.length, ctx.every, ctx.seed, ctx.draw0 = model, length, every, seed, draw0
+        ctx.save_for_backward(*((flat, out) if every and length > 1 else (flat,)))
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gout):
+        flat, *states = ctx.saved_tensors
+        states = states[0] if states else None
+        length = ctx.length
+        if states is None and length > 1:
+            m, d = flat.shape
+            states = torch.empty(length - 1, m, d, device=flat.device, dtype=torch.float32)
+            ops.chain_advance(ctx.model, flat, states, length - 1, every=True, out_st=m * d, seed=ctx.seed, draw0=ctx.draw0)
+        g = ops.chain_advance_vjp(ctx.model, flat, states, gout.to(torch.float32).contiguous(), length, ctx.every)
+        return g, None, None, None, None, None
+
+
 class DiscreteODE(MarkovChain):
-    r"""Discretized ordinary differential equation (sda/mcs.py:85-122): ``steps`` RK4 sub-steps of ``dt / steps`` per transition."""
+    r"""Discretized ordinary differential equation (sda/mcs.py:85-122): ``steps`` RK4 sub-steps of ``dt / steps`` per transition.
+
+    ``grad='device'`` (opt-in, keyword only) keeps a float32 device input that requires grad on the kernel: forward is the same
+    launch, backward one ``sda_chain_advance_vjp`` launch (first order only).  A user subclass with its own ``f``, Lorenz-96 outside
+    4 <= n <= 64, float64 or CPU inputs and the default ``grad='torch'`` differentiate the torch-ops ``rk4``."""
 
     #: (kernel kind, f of the class the kernel implements); None: torch-ops rk4
     _KERNEL: Optional[Tuple[str, Callable]] = None
 
-    def __init__(self, dt: float = 0.01, steps: int = 1):
+    def __init__(self, dt: float = 0.01, steps: int = 1, *, grad: str = 'torch'):
         super().__init__()
+        if grad not in ('torch', 'device'):
+            raise ValueError(f"{type(self).__name__}: grad={grad!r}, expected 'torch' or 'device'")
+        self.grad = grad
         self.dt, self.steps = dt, steps
         self._draw = 0
 
@@ -89,10 +131,24 @@ class DiscreteODE(MarkovChain):
     def _noise_std(self) -> float:
         return 0.0
 
+    def _served(self) -> bool:
+        """The kernels implement this chain: a built-in system whose ``f`` was not overridden."""
+        k = type(self)._KERNEL
+        return k is not None and type(self).f is k[1]
+
     def _fused(self, x: Tensor) -> bool:
         """The kernel serves this call: a built-in system whose ``f`` was not overridden, no autograd through x."""
-        k = type(self)._KERNEL
-        return k is not None and type(self).f is k[1] and not (torch.is_grad_enabled() and x.requires_grad)
+        return self._served() and not (torch.is_grad_enabled() and x.requires_grad)
+
+    def _grad_route(self, x: Tensor) -> Optional[str]:
+        """What carries the gradient of this call, recorded in ``LAST_CHAIN_GRAD_ROUTE``: None if nothing asks for one."""
+        global LAST_CHAIN_GRAD_ROUTE
+        route = None
+        if torch.is_grad_enabled() and x.requires_grad:
+            device = self.grad == 'device' and self._served() and x.is_cuda and x.dtype == torch.float32
+            route = 'device' if device else 'torch'
+        LAST_CHAIN_GRAD_ROUTE = route
+        return route
 
     def model(self):
         kind = type(self)._KERNEL[0]
@@ -104,7 +160,7 @@ class DiscreteODE(MarkovChain):
             x = self.rk4(self.f, x, self.dt / self.steps)
         return x
 
-    def _advance(self, x: Tensor, length: int, every: bool, seed: Optional[int] = None) -> Tensor:
+    def _advance(self, x: Tensor, length: int, every: bool, seed: Optional[int] = None, *, route: Optional[str] = None) -> Tensor:
         model = self.model()
         if x.shape[-1:] != (model.d,):
             raise SdaHipError(f'{type(self).__name__}: states of shape {tuple(x.shape)}, expected (..., {model.d})')
@@ -119,18 +175,23 @@ class DiscreteODE(MarkovChain):
         if model.noise_std > 0:
             seed = _draw_seed() if seed is None else int(seed)
             self._draw += length
-        out = torch.empty((length, m, model.d) if every else (m, model.d), device=x.device, dtype=torch.float32)
-        ops.chain_advance(model, flat, out, length, every=every, out_st=m * model.d, seed=seed or 0, draw0=draw0)
+        if route == 'device':
+            out = _ChainAdvance.apply(flat, model, length, every, seed or 0, draw0)
+        else:
+            out = torch.empty((length, m, model.d) if every else (m, model.d), device=x.device, dtype=torch.float32)
+            ops.chain_advance(model, flat, out, length, every=every, out_st=m * model.d, seed=seed or 0, draw0=draw0)
         return out.reshape((length, *batch, model.d) if every else (*batch, model.d))
 
     def transition(self, x: Tensor) -> Tensor:
-        if self._fused(x):
-            return self._advance(x, 1, False)
+        route = self._grad_route(x)
+        if route == 'device' or self._fused(x):
+            return self._advance(x, 1, False, route=route)
         return self._rk4_transition(x)
 
     def trajectory(self, x: Tensor, length: int, last: bool = False) -> Tensor:
-        if self._fused(x) and length >= 1:
-            return self._advance(x, length, not last)
+        route = self._grad_route(x)
+        if (route == 'device' or self._fused(x)) and length >= 1:
+            return self._advance(x, length, not last, route=route)
         return super().trajectory(x, length, last)
 
 
@@ -183,24 +244,30 @@ class NoisyLorenz63(Lorenz63):
         return self.dt ** 0.5
 
     def moments(self, x: Tensor) -> Tuple[Tensor, float]:
-        if self._fused(x):
+        route = self._grad_route(x)
+        if route == 'device' or self._fused(x):
             model = self.model()
             model.noise_std = 0.0
             flat = x.reshape(-1, 3)
             flat = flat if flat.stride(-1) == 1 else flat.contiguous()
-            out = torch.empty_like(flat, memory_format=torch.contiguous_format)
-            ops.chain_advance(model, flat, out, 1)
+            if route == 'device':
+                out = _ChainAdvance.apply(flat, model, 1, False, 0, 0)
+            else:
+                out = torch.empty_like(flat, memory_format=torch.contiguous_format)
+                ops.chain_advance(model, flat, out, 1)
             return out.reshape(x.shape), self.dt ** 0.5
         return self._rk4_transition(x), self.dt ** 0.5
 
     def transition(self, x: Tensor, *, seed: Optional[int] = None) -> Tensor:
-        if self._fused(x):
-            return self._advance(x, 1, False, seed)
+        route = self._grad_route(x)
+        if route == 'device' or self._fused(x):
+            return self._advance(x, 1, False, seed, route=route)
         return Normal(*self.moments(x)).sample()
 
     def trajectory(self, x: Tensor, length: int, last: bool = False, *, seed: Optional[int] = None) -> Tensor:
-        if self._fused(x) and length >= 1:
-            return self._advance(x, length, not last, seed)
+        route = self._grad_route(x)
+        if (route == 'device' or self._fused(x)) and length >= 1:
+            return self._advance(x, length, not last, seed, route=route)
         return MarkovChain.trajectory(self, x, length, last)
 
     def log_prob(self, x1: Tensor, x2: Tensor) -> Tensor:
@@ -224,8 +291,8 @@ class Lorenz96(DiscreteODE):
     def _params(self):
         return self.n, (self.F,)
 
-    def _fused(self, x: Tensor) -> bool:
-        return 4 <= self.n <= 64 and super()._fused(x)
+    def _served(self) -> bool:
+        return 4 <= self.n <= 64 and super()._served()
 
 
 Lorenz96._KERNEL = ('lorenz96', Lorenz96.f)

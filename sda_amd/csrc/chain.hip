@@ -35,11 +35,11 @@ __host__ __device__ __forceinline__ float lorenz96_f(float xm1, float xp2, float
     return (xm1 - xp2) * xp1 - x + F;
 }
 
-// one transition (model.steps RK4 sub-steps) of a small-state chain, state in registers
+// `count` RK4 sub-steps of a small-state chain, state in registers
 template <int KIND>
-__host__ __device__ __forceinline__ void chain_small_transition(const sda_chain_model& m, float* x) {
+__host__ __device__ __forceinline__ void chain_small_substeps(const sda_chain_model& m, float* x, int count) {
     constexpr int D = KIND == SDA_CHAIN_LORENZ63 ? 3 : 2;
-    for (int s = 0; s < m.steps; ++s) {
+    for (int s = 0; s < count; ++s) {
         float k1[D], k2[D], k3[D], k4[D], t[D];
         if (KIND == SDA_CHAIN_LORENZ63) lorenz63_f(m.p, x, k1); else lotka_volterra_f(m.p, x, k1);
 #pragma unroll
@@ -53,6 +53,98 @@ __host__ __device__ __forceinline__ void chain_small_transition(const sda_chain_
         if (KIND == SDA_CHAIN_LORENZ63) lorenz63_f(m.p, t, k4); else lotka_volterra_f(m.p, t, k4);
 #pragma unroll
         for (int c = 0; c < D; ++c) x[c] = rk4_comb(x[c], m.h, k1[c], k2[c], k3[c], k4[c]);
+    }
+}
+
+// one transition (model.steps sub-steps)
+template <int KIND>
+__host__ __device__ __forceinline__ void chain_small_transition(const sda_chain_model& m, float* x) {
+    chain_small_substeps<KIND>(m, x, m.steps);
+}
+
+// ---------------------------------------------------------------- the reverse sweep of one RK4 sub-step.  With gy the cotangent of
+// y = x + h (k1 + 2 k2 + 2 k3 + k4) / 6 and jt_i = J_f(v_i)^T gk_i at the recomputed stage point v_i (v_1 = x):
+//   gk4 = h/6 gy, gk3 = h/3 gy + h jt4, gk2 = h/3 gy + h/2 jt3, gk1 = h/6 gy + h/2 jt2, gx = gy + jt4 + jt3 + jt2 + jt1.
+__host__ __device__ __forceinline__ float rk4r_k4(float h, float gy) { return h * gy / 6.0f; }
+__host__ __device__ __forceinline__ float rk4r_k3(float h, float gy, float jt4) { return h * gy / 3.0f + h * jt4; }
+__host__ __device__ __forceinline__ float rk4r_k2(float h, float gy, float jt3) { return h * gy / 3.0f + h * jt3 / 2.0f; }
+__host__ __device__ __forceinline__ float rk4r_k1(float h, float gy, float jt2) { return h * gy / 6.0f + h * jt2 / 2.0f; }
+__host__ __device__ __forceinline__ float rk4r_x(float gy, float jt1, float jt2, float jt3, float jt4) { return gy + jt4 + jt3 + jt2 + jt1; }
+
+// f at a stage point, keeping what its Jacobian reuses: e = exp of the point for Lotka-Volterra (the same two expf as
+// lotka_volterra_f, so f is bitwise the forward's), nothing for Lorenz-63
+template <int KIND>
+__host__ __device__ __forceinline__ void small_f_keep(const float* p, const float* v, float* f, float* e) {
+    if (KIND == SDA_CHAIN_LORENZ63) {
+        lorenz63_f(p, v, f);
+    } else {
+        e[0] = expf(v[0]);
+        e[1] = expf(v[1]);
+        f[0] = p[0] - p[1] * e[1];
+        f[1] = p[2] * e[0] - p[3];
+    }
+}
+// o = J_f(v)^T g
+template <int KIND>
+__host__ __device__ __forceinline__ void small_jt(const float* p, const float* v, const float* e, const float* g, float* o) {
+    if (KIND == SDA_CHAIN_LORENZ63) {
+        o[0] = (p[1] - v[2]) * g[1] - p[0] * g[0] + v[1] * g[2];
+        o[1] = p[0] * g[0] - g[1] + v[0] * g[2];
+        o[2] = -(v[0] * g[1]) - p[2] * g[2];
+    } else {
+        o[0] = p[2] * e[0] * g[1];
+        o[1] = -(p[1] * e[1] * g[0]);
+    }
+}
+// Lorenz-96 in gather form: f_c = (x_{c-1} - x_{c+2}) x_{c+1} - x_c + F reaches x_j from c = j + 1, j - 2 and j - 1 (and j itself)
+__host__ __device__ __forceinline__ float lorenz96_jt(float gp1, float xp2, float gm2, float xm1, float gm1, float xm2, float xp1,
+                                                      float g) {
+    return gp1 * xp2 - gm2 * xm1 + gm1 * (xm2 - xp1) - g;
+}
+
+// g <- (d sub-step / dx at x)^T g for a small-state chain: the four stage points recomputed, everything in registers
+template <int KIND>
+__host__ __device__ __forceinline__ void chain_small_substep_vjp(const sda_chain_model& m, const float* x, float* g) {
+    constexpr int D = KIND == SDA_CHAIN_LORENZ63 ? 3 : 2;
+    const float h = m.h;
+    float k[D], v2[D], v3[D], v4[D], e1[D], e2[D], e3[D], e4[D], gk[D], j1[D], j2[D], j3[D], j4[D];
+    small_f_keep<KIND>(m.p, x, k, e1);
+#pragma unroll
+    for (int c = 0; c < D; ++c) v2[c] = rk4_half(x[c], h, k[c]);
+    small_f_keep<KIND>(m.p, v2, k, e2);
+#pragma unroll
+    for (int c = 0; c < D; ++c) v3[c] = rk4_half(x[c], h, k[c]);
+    small_f_keep<KIND>(m.p, v3, k, e3);
+#pragma unroll
+    for (int c = 0; c < D; ++c) v4[c] = rk4_full(x[c], h, k[c]);
+    small_f_keep<KIND>(m.p, v4, k, e4);                 // (only e4 is used: k4 itself does not enter the reverse sweep)
+#pragma unroll
+    for (int c = 0; c < D; ++c) gk[c] = rk4r_k4(h, g[c]);
+    small_jt<KIND>(m.p, v4, e4, gk, j4);
+#pragma unroll
+    for (int c = 0; c < D; ++c) gk[c] = rk4r_k3(h, g[c], j4[c]);
+    small_jt<KIND>(m.p, v3, e3, gk, j3);
+#pragma unroll
+    for (int c = 0; c < D; ++c) gk[c] = rk4r_k2(h, g[c], j3[c]);
+    small_jt<KIND>(m.p, v2, e2, gk, j2);
+#pragma unroll
+    for (int c = 0; c < D; ++c) gk[c] = rk4r_k1(h, g[c], j2[c]);
+    small_jt<KIND>(m.p, x, e1, gk, j1);
+#pragma unroll
+    for (int c = 0; c < D; ++c) g[c] = rk4r_x(g[c], j1[c], j2[c], j3[c], j4[c]);
+}
+
+// g <- (d transition / dx at x0)^T g.  The states inside a transition are not stored: sub-step s, last to first, starts from x0
+// advanced s sub-steps again (O(steps^2) on D floats, bitwise the forward's states).
+template <int KIND>
+__host__ __device__ __forceinline__ void chain_small_transition_vjp(const sda_chain_model& m, const float* x0, float* g) {
+    constexpr int D = KIND == SDA_CHAIN_LORENZ63 ? 3 : 2;
+    for (int s = m.steps - 1; s >= 0; --s) {
+        float x[D];
+#pragma unroll
+        for (int c = 0; c < D; ++c) x[c] = x0[c];
+        chain_small_substeps<KIND>(m, x, s);
+        chain_small_substep_vjp<KIND>(m, x, g);
     }
 }
 
@@ -127,6 +219,26 @@ __host__ __device__ __forceinline__ double chain_pair_log_prob(const sda_chain_m
     return l;
 }
 
+// pair (x, x_next) of a trajectory: returns log p(x_next | x) exactly as chain_pair_log_prob does, r = (x_next - T(x)) / noise_std^2
+// (= d log p / d T(x) = -d log p / d x_next) and jtr = J_T(x)^T r (= d log p / d x)
+template <int KIND>
+__host__ __device__ __forceinline__ double chain_pair_residual(const sda_chain_model& m, const float* x, const float* x_next, float* r,
+                                                               float* jtr) {
+    constexpr int D = KIND == SDA_CHAIN_LORENZ63 ? 3 : 2;
+    float mu[D];
+#pragma unroll
+    for (int c = 0; c < D; ++c) mu[c] = x[c];
+    chain_small_transition<KIND>(m, mu);
+    double l = 0.0;
+#pragma unroll
+    for (int c = 0; c < D; ++c) l += normal_log_prob((double)x_next[c], (double)mu[c], (double)m.noise_std);
+    const float s2 = m.noise_std * m.noise_std;
+#pragma unroll
+    for (int c = 0; c < D; ++c) { r[c] = (x_next[c] - mu[c]) / s2; jtr[c] = r[c]; }
+    chain_small_transition_vjp<KIND>(m, x, jtr);
+    return l;
+}
+
 static int chain_model_check(const sda_chain_model* m) {
     if (!m || m->steps < 1 || !(m->noise_std >= 0.f)) return SDA_E_BADARG;
     if (m->kind == SDA_CHAIN_LORENZ63) return m->d == 3 ? SDA_OK : SDA_E_BADARG;
@@ -153,6 +265,27 @@ static int chain_adv_check(const sda_chain_adv* a) {
         if (!a->logw || !a->pmax) return SDA_E_BADARG;
         return chain_obs_check(a->obs, a->model.d);
     }
+    return SDA_OK;
+}
+
+static int chain_vjp_check(const sda_chain_vjp* a) {
+    if (!a) return SDA_E_BADARG;
+    int rc = chain_model_check(&a->model);
+    if (rc != SDA_OK) return rc;
+    if (a->anc) return SDA_E_UNSUPPORTED;       // the particle filter's ancestor gather is not differentiated
+    if (!a->x_in || !a->g || !a->gx || a->m < 1 || a->transitions < 1 || (a->transitions > 1 && !a->states)) return SDA_E_BADARG;
+    const int d = a->model.d;
+    if (a->in_sp < d || a->g_sp < d || a->gx_sp < d || (a->states && (a->st_sp < d || a->st_st < 0))) return SDA_E_BADARG;
+    if (a->every && a->g_st < 0) return SDA_E_BADARG;
+    return SDA_OK;
+}
+
+static int chain_lpg_check(const sda_chain_model* model, const float* x, int b, int len, int64_t sb, int64_t sl, const double* out,
+                           const float* grad) {
+    int rc = chain_model_check(model);
+    if (rc != SDA_OK) return rc;
+    if (model->kind == SDA_CHAIN_LORENZ96) return SDA_E_UNSUPPORTED;
+    if (!x || !out || !grad || b < 1 || len < 2 || sl < model->d || !(model->noise_std > 0.f)) return SDA_E_BADARG;
     return SDA_OK;
 }
 
@@ -223,6 +356,48 @@ __global__ __launch_bounds__(CH_THREADS) void chain_advance_small_kernel(ChainAd
     }
 }
 
+// Lorenz-96 on lanes: the lanes that hold components c - 1, c + 1, c + 2 and c - 2 (modulo n) of this lane's particle
+struct L96Lanes { int m1, p1, p2, m2; };
+struct L96Near { float m1, p1, p2; };       // a stage point's values at c - 1, c + 1, c + 2
+__device__ __forceinline__ L96Lanes l96_lanes(int base, int c, int n) {
+    return {base + (c + n - 1) % n, base + (c + 1) % n, base + (c + 2) % n, base + (c + n - 2) % n};
+}
+__device__ __forceinline__ L96Near l96_near(float v, const L96Lanes& l) {
+    return {__shfl(v, l.m1, SDA_WAVE), __shfl(v, l.p1, SDA_WAVE), __shfl(v, l.p2, SDA_WAVE)};
+}
+__device__ __forceinline__ float l96_f_lanes(float v, const L96Lanes& l, float F) {
+    const L96Near a = l96_near(v, l);
+    return lorenz96_f(a.m1, a.p2, a.p1, v, F);
+}
+// one RK4 sub-step of this lane's component; every lane of the wave calls it
+__device__ __forceinline__ float l96_substep_lanes(float x, const L96Lanes& l, float h, float F) {
+    const float k1 = l96_f_lanes(x, l, F);
+    const float k2 = l96_f_lanes(rk4_half(x, h, k1), l, F);
+    const float k3 = l96_f_lanes(rk4_half(x, h, k2), l, F);
+    const float k4 = l96_f_lanes(rk4_full(x, h, k3), l, F);
+    return rk4_comb(x, h, k1, k2, k3, k4);
+}
+// (J_f(v)^T gk)_c: the stage point's three forward shuffles are reused, v_{c-2} and three of gk are the four new ones
+__device__ __forceinline__ float l96_jt_lanes(float v, const L96Near& a, float gk, const L96Lanes& l) {
+    return lorenz96_jt(__shfl(gk, l.p1, SDA_WAVE), a.p2, __shfl(gk, l.m2, SDA_WAVE), a.m1, __shfl(gk, l.m1, SDA_WAVE),
+                       __shfl(v, l.m2, SDA_WAVE), a.p1, gk);
+}
+// g <- (d sub-step / dx at x)^T g, this lane's component; every lane of the wave calls it
+__device__ __forceinline__ float l96_substep_vjp_lanes(float x, float g, const L96Lanes& l, float h, float F) {
+    const L96Near a1 = l96_near(x, l);
+    const float v2 = rk4_half(x, h, lorenz96_f(a1.m1, a1.p2, a1.p1, x, F));
+    const L96Near a2 = l96_near(v2, l);
+    const float v3 = rk4_half(x, h, lorenz96_f(a2.m1, a2.p2, a2.p1, v2, F));
+    const L96Near a3 = l96_near(v3, l);
+    const float v4 = rk4_full(x, h, lorenz96_f(a3.m1, a3.p2, a3.p1, v3, F));
+    const L96Near a4 = l96_near(v4, l);
+    const float j4 = l96_jt_lanes(v4, a4, rk4r_k4(h, g), l);
+    const float j3 = l96_jt_lanes(v3, a3, rk4r_k3(h, g, j4), l);
+    const float j2 = l96_jt_lanes(v2, a2, rk4r_k2(h, g, j3), l);
+    const float j1 = l96_jt_lanes(x, a1, rk4r_k1(h, g, j2), l);
+    return rk4r_x(g, j1, j2, j3, j4);
+}
+
 // Lorenz-96: component c of a particle on lane (group base + c) of a sub-group of W lanes, W = next power of two >= n
 __global__ __launch_bounds__(CH_THREADS) void chain_advance_l96_kernel(ChainAdvArgs a, int W) {
     const int n = a.model.d;
@@ -232,7 +407,7 @@ __global__ __launch_bounds__(CH_THREADS) void chain_advance_l96_kernel(ChainAdvA
     const bool live = j < a.m && sub < n;
     const int c = sub < n ? sub : 0;
     // roll(x, 1)[c] = x[c - 1], roll(x, -1)[c] = x[c + 1], roll(x, -2)[c] = x[c + 2], indices modulo n
-    const int lm1 = base + (c + n - 1) % n, lp1 = base + (c + 1) % n, lp2 = base + (c + 2) % n;
+    const L96Lanes l = l96_lanes(base, c, n);
     const float h = a.model.h, F = a.model.p[0];
     float x = 0.f;
     if (live) {
@@ -241,16 +416,7 @@ __global__ __launch_bounds__(CH_THREADS) void chain_advance_l96_kernel(ChainAdvA
     }
     // every lane of the wave runs the shuffles (dead lanes carry zeros); only the stores are predicated
     for (int t = 0; t < a.transitions; ++t) {
-        for (int s = 0; s < a.model.steps; ++s) {
-            const float k1 = lorenz96_f(__shfl(x, lm1, SDA_WAVE), __shfl(x, lp2, SDA_WAVE), __shfl(x, lp1, SDA_WAVE), x, F);
-            float v = rk4_half(x, h, k1);
-            const float k2 = lorenz96_f(__shfl(v, lm1, SDA_WAVE), __shfl(v, lp2, SDA_WAVE), __shfl(v, lp1, SDA_WAVE), v, F);
-            v = rk4_half(x, h, k2);
-            const float k3 = lorenz96_f(__shfl(v, lm1, SDA_WAVE), __shfl(v, lp2, SDA_WAVE), __shfl(v, lp1, SDA_WAVE), v, F);
-            v = rk4_full(x, h, k3);
-            const float k4 = lorenz96_f(__shfl(v, lm1, SDA_WAVE), __shfl(v, lp2, SDA_WAVE), __shfl(v, lp1, SDA_WAVE), v, F);
-            x = rk4_comb(x, h, k1, k2, k3, k4);
-        }
+        for (int s = 0; s < a.model.steps; ++s) x = l96_substep_lanes(x, l, h, F);
         if (a.model.noise_std > 0.f && live) {
             float z[4];
             chain_noise4(a.seed, (uint64_t)(a.row0 + j), a.draw0 + t, c >> 2, z);
@@ -288,6 +454,150 @@ extern "C" int sda_chain_advance(const sda_chain_adv* a, void* stream) {
         else
             hipLaunchKernelGGL(chain_advance_small_kernel<SDA_CHAIN_LOTKA_VOLTERRA>, dim3(blocks), dim3(CH_THREADS), 0, st, k, obs);
     }
+    return sda_launch_status();
+}
+
+// ---------------------------------------------------------------- the adjoint of sda_chain_advance: one launch walks every
+// transition backwards.  The geometry is the forward's (one particle per lane / per sub-group), a particle's cotangent never leaves
+// its lane or sub-group and nothing is accumulated across particles: no atomics, and a row does not depend on m.
+struct ChainVjpArgs {       // sda_chain_vjp without anc
+    sda_chain_model model;
+    const float* x_in; int64_t in_sp;
+    const float* states; int64_t st_st, st_sp;
+    const float* g; int64_t g_st, g_sp;
+    float* gx; int64_t gx_sp;
+    int32_t every, m, transitions;
+};
+
+template <int KIND>
+__global__ __launch_bounds__(CH_THREADS) void chain_advance_vjp_small_kernel(ChainVjpArgs a) {
+    constexpr int D = KIND == SDA_CHAIN_LORENZ63 ? 3 : 2;
+    const int j = blockIdx.x * CH_THREADS + threadIdx.x;
+    if (j >= a.m) return;
+    const int T = a.transitions;
+    float g[D], x0[D];
+#pragma unroll
+    for (int c = 0; c < D; ++c) g[c] = a.g[(a.every ? (T - 1) * a.g_st : 0) + j * a.g_sp + c];
+    for (int t = T - 1; t >= 0; --t) {
+        const float* xs = t ? a.states + (t - 1) * a.st_st + j * a.st_sp : a.x_in + j * a.in_sp;
+#pragma unroll
+        for (int c = 0; c < D; ++c) x0[c] = xs[c];
+        chain_small_transition_vjp<KIND>(a.model, x0, g);
+        if (a.every && t) {
+#pragma unroll
+            for (int c = 0; c < D; ++c) g[c] = a.g[(t - 1) * a.g_st + j * a.g_sp + c] + g[c];
+        }
+    }
+#pragma unroll
+    for (int c = 0; c < D; ++c) a.gx[j * a.gx_sp + c] = g[c];
+}
+
+__global__ __launch_bounds__(CH_THREADS) void chain_advance_vjp_l96_kernel(ChainVjpArgs a, int W) {
+    const int n = a.model.d;
+    const int lane = threadIdx.x & 63, sub = lane & (W - 1), base = lane - sub;
+    const int per_block = CH_THREADS / W;
+    const int64_t j = (int64_t)blockIdx.x * per_block + threadIdx.x / W;
+    const bool live = j < a.m && sub < n;
+    const int c = sub < n ? sub : 0;
+    const L96Lanes l = l96_lanes(base, c, n);
+    const float h = a.model.h, F = a.model.p[0];
+    const int T = a.transitions;
+    float g = 0.f;
+    if (live) g = a.g[(a.every ? (T - 1) * a.g_st : 0) + j * a.g_sp + c];
+    // every lane of the wave runs the shuffles (dead lanes carry zeros); the trip counts depend on the model alone
+    for (int t = T - 1; t >= 0; --t) {
+        float x0 = 0.f;
+        if (live) x0 = t ? a.states[(t - 1) * a.st_st + j * a.st_sp + c] : a.x_in[j * a.in_sp + c];
+        for (int s = a.model.steps - 1; s >= 0; --s) {
+            float x = x0;
+            for (int q = 0; q < s; ++q) x = l96_substep_lanes(x, l, h, F);
+            g = l96_substep_vjp_lanes(x, g, l, h, F);
+        }
+        if (a.every && t && live) g = a.g[(t - 1) * a.g_st + j * a.g_sp + c] + g;
+    }
+    if (live) a.gx[j * a.gx_sp + c] = g;
+}
+
+extern "C" int sda_chain_advance_vjp(const sda_chain_vjp* a, void* stream) {
+    int rc = chain_vjp_check(a);
+    if (rc != SDA_OK) return rc;
+    ChainVjpArgs k;
+    k.model = a->model;
+    k.x_in = a->x_in; k.in_sp = a->in_sp;
+    k.states = a->states; k.st_st = a->st_st; k.st_sp = a->st_sp;
+    k.g = a->g; k.g_st = a->every ? a->g_st : 0; k.g_sp = a->g_sp;
+    k.gx = a->gx; k.gx_sp = a->gx_sp;
+    k.every = a->every ? 1 : 0; k.m = a->m; k.transitions = a->transitions;
+    const hipStream_t st = (hipStream_t)stream;
+    if (a->model.kind == SDA_CHAIN_LORENZ96) {
+        int W = 4;
+        while (W < a->model.d) W <<= 1;
+        const int per_block = CH_THREADS / W;
+        const int64_t blocks = ((int64_t)a->m + per_block - 1) / per_block;
+        if (blocks > 0x7fffffff) return SDA_E_UNSUPPORTED;
+        hipLaunchKernelGGL(chain_advance_vjp_l96_kernel, dim3((unsigned)blocks), dim3(CH_THREADS), 0, st, k, W);
+    } else {
+        const unsigned blocks = (unsigned)((a->m + CH_THREADS - 1) / CH_THREADS);
+        if (a->model.kind == SDA_CHAIN_LORENZ63)
+            hipLaunchKernelGGL(chain_advance_vjp_small_kernel<SDA_CHAIN_LORENZ63>, dim3(blocks), dim3(CH_THREADS), 0, st, k);
+        else
+            hipLaunchKernelGGL(chain_advance_vjp_small_kernel<SDA_CHAIN_LOTKA_VOLTERRA>, dim3(blocks), dim3(CH_THREADS), 0, st, k);
+    }
+    return sda_launch_status();
+}
+
+// value and gradient of sda_chain_log_prob: one wave per trajectory, lanes stride over the time indices.  The lane that owns index
+// i evaluates pair (i, i + 1): its log-density (summed exactly as chain_log_prob_kernel sums it), r_i and J_T(x_i)^T r_i; r_{i-1}
+// comes from the lane below, and for lane 0 from lane 63 of the previous stride.  Gather form: one store per element, no atomics.
+template <int KIND>
+__global__ __launch_bounds__(CH_THREADS) void chain_log_prob_grad_kernel(sda_chain_model model, const float* __restrict__ x, int b,
+                                                                         int len, int64_t sb, int64_t sl, double* __restrict__ out,
+                                                                         float* __restrict__ grad) {
+    constexpr int D = KIND == SDA_CHAIN_LORENZ63 ? 3 : 2;
+    const int lane = threadIdx.x & 63;
+    const int traj = blockIdx.x * (CH_THREADS / SDA_WAVE) + (threadIdx.x >> 6);
+    const bool have = traj < b;                 // the same in every lane of the wave
+    const float* xt = x + traj * sb;
+    float* gt = grad + (int64_t)traj * len * D;
+    double acc = 0.0;
+    float carry[D];
+#pragma unroll
+    for (int c = 0; c < D; ++c) carry[c] = 0.f;
+    for (int i0 = 0; i0 < len; i0 += SDA_WAVE) {        // every lane takes every trip: the shuffles below need the whole wave
+        const int i = i0 + lane;
+        float r[D], jtr[D];
+#pragma unroll
+        for (int c = 0; c < D; ++c) { r[c] = 0.f; jtr[c] = 0.f; }
+        if (have && i + 1 < len) {
+            float p[D], q[D];
+#pragma unroll
+            for (int c = 0; c < D; ++c) { p[c] = xt[i * sl + c]; q[c] = xt[(i + 1) * sl + c]; }
+            acc += chain_pair_residual<KIND>(model, p, q, r, jtr);
+        }
+#pragma unroll
+        for (int c = 0; c < D; ++c) {
+            const float below = __shfl_up(r[c], 1, SDA_WAVE);
+            const float prev = lane ? below : carry[c];
+            carry[c] = __shfl(r[c], SDA_WAVE - 1, SDA_WAVE);
+            if (have && i < len) gt[(int64_t)i * D + c] = jtr[c] - prev;
+        }
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off, SDA_WAVE);
+    if (lane == 0 && have) out[traj] = acc;
+}
+
+extern "C" int sda_chain_log_prob_grad(const sda_chain_model* model, const float* x, int b, int len, int64_t sb, int64_t sl,
+                                       double* out, float* grad, void* stream) {
+    int rc = chain_lpg_check(model, x, b, len, sb, sl, out, grad);
+    if (rc != SDA_OK) return rc;
+    const unsigned blocks = (unsigned)((b + CH_THREADS / SDA_WAVE - 1) / (CH_THREADS / SDA_WAVE));
+    if (model->kind == SDA_CHAIN_LORENZ63)
+        hipLaunchKernelGGL(chain_log_prob_grad_kernel<SDA_CHAIN_LORENZ63>, dim3(blocks), dim3(CH_THREADS), 0, (hipStream_t)stream,
+                           *model, x, b, len, sb, sl, out, grad);
+    else
+        hipLaunchKernelGGL(chain_log_prob_grad_kernel<SDA_CHAIN_LOTKA_VOLTERRA>, dim3(blocks), dim3(CH_THREADS), 0,
+                           (hipStream_t)stream, *model, x, b, len, sb, sl, out, grad);
     return sda_launch_status();
 }
 
@@ -496,6 +806,95 @@ extern "C" int sda_chain_advance_host(const sda_chain_adv* a) {
         if (!a->every)
             for (int c = 0; c < d; ++c) a->out[j * a->out_sp + c] = x[c];
         if (a->obs) a->logw[j] = obs_logweight(*a->obs, a->obs->y, x);
+    }
+    return SDA_OK;
+}
+
+static void l96_substep_host(const sda_chain_model& m, float* x) {
+    sda_chain_model one = m;
+    one.steps = 1;
+    l96_transition_host(one, x);
+}
+
+static void l96_jt_host(const float* v, const float* g, int n, float* o) {
+    for (int j = 0; j < n; ++j)
+        o[j] = lorenz96_jt(g[(j + 1) % n], v[(j + 2) % n], g[(j + n - 2) % n], v[(j + n - 1) % n], g[(j + n - 1) % n],
+                           v[(j + n - 2) % n], v[(j + 1) % n], g[j]);
+}
+
+// the array form of l96_substep_vjp_lanes
+static void l96_substep_vjp_host(const sda_chain_model& m, const float* x, float* g) {
+    const int n = m.d;
+    const float h = m.h, F = m.p[0];
+    float k[64], v2[64], v3[64], v4[64], gk[64], j1[64], j2[64], j3[64], j4[64];
+    l96_f_host(x, n, F, k);
+    for (int c = 0; c < n; ++c) v2[c] = rk4_half(x[c], h, k[c]);
+    l96_f_host(v2, n, F, k);
+    for (int c = 0; c < n; ++c) v3[c] = rk4_half(x[c], h, k[c]);
+    l96_f_host(v3, n, F, k);
+    for (int c = 0; c < n; ++c) v4[c] = rk4_full(x[c], h, k[c]);
+    for (int c = 0; c < n; ++c) gk[c] = rk4r_k4(h, g[c]);
+    l96_jt_host(v4, gk, n, j4);
+    for (int c = 0; c < n; ++c) gk[c] = rk4r_k3(h, g[c], j4[c]);
+    l96_jt_host(v3, gk, n, j3);
+    for (int c = 0; c < n; ++c) gk[c] = rk4r_k2(h, g[c], j3[c]);
+    l96_jt_host(v2, gk, n, j2);
+    for (int c = 0; c < n; ++c) gk[c] = rk4r_k1(h, g[c], j2[c]);
+    l96_jt_host(x, gk, n, j1);
+    for (int c = 0; c < n; ++c) g[c] = rk4r_x(g[c], j1[c], j2[c], j3[c], j4[c]);
+}
+
+static void l96_transition_vjp_host(const sda_chain_model& m, const float* x0, float* g) {
+    for (int s = m.steps - 1; s >= 0; --s) {
+        float x[64];
+        for (int c = 0; c < m.d; ++c) x[c] = x0[c];
+        for (int q = 0; q < s; ++q) l96_substep_host(m, x);
+        l96_substep_vjp_host(m, x, g);
+    }
+}
+
+extern "C" int sda_chain_advance_vjp_host(const sda_chain_vjp* a) {
+    int rc = chain_vjp_check(a);
+    if (rc != SDA_OK) return rc;
+    const sda_chain_model& md = a->model;
+    const int d = md.d, T = a->transitions;
+    for (int64_t j = 0; j < a->m; ++j) {
+        float g[64], x0[64];
+        for (int c = 0; c < d; ++c) g[c] = a->g[(a->every ? (T - 1) * a->g_st : 0) + j * a->g_sp + c];
+        for (int t = T - 1; t >= 0; --t) {
+            const float* xs = t ? a->states + (t - 1) * a->st_st + j * a->st_sp : a->x_in + j * a->in_sp;
+            for (int c = 0; c < d; ++c) x0[c] = xs[c];
+            if (md.kind == SDA_CHAIN_LORENZ63) chain_small_transition_vjp<SDA_CHAIN_LORENZ63>(md, x0, g);
+            else if (md.kind == SDA_CHAIN_LOTKA_VOLTERRA) chain_small_transition_vjp<SDA_CHAIN_LOTKA_VOLTERRA>(md, x0, g);
+            else l96_transition_vjp_host(md, x0, g);
+            if (a->every && t)
+                for (int c = 0; c < d; ++c) g[c] = a->g[(t - 1) * a->g_st + j * a->g_sp + c] + g[c];
+        }
+        for (int c = 0; c < d; ++c) a->gx[j * a->gx_sp + c] = g[c];
+    }
+    return SDA_OK;
+}
+
+extern "C" int sda_chain_log_prob_grad_host(const sda_chain_model* model, const float* x, int b, int len, int64_t sb, int64_t sl,
+                                            double* out, float* grad) {
+    int rc = chain_lpg_check(model, x, b, len, sb, sl, out, grad);
+    if (rc != SDA_OK) return rc;
+    const int d = model->d;
+    for (int t = 0; t < b; ++t) {
+        double acc = 0.0;
+        float prev[3] = {0.f, 0.f, 0.f};
+        for (int i = 0; i < len; ++i) {
+            float r[3] = {0.f, 0.f, 0.f}, jtr[3] = {0.f, 0.f, 0.f};
+            const float* p = x + t * sb + i * sl;
+            if (i + 1 < len)
+                acc += model->kind == SDA_CHAIN_LORENZ63 ? chain_pair_residual<SDA_CHAIN_LORENZ63>(*model, p, p + sl, r, jtr)
+                                                         : chain_pair_residual<SDA_CHAIN_LOTKA_VOLTERRA>(*model, p, p + sl, r, jtr);
+            for (int c = 0; c < d; ++c) {
+                grad[((int64_t)t * len + i) * d + c] = jtr[c] - prev[c];
+                prev[c] = r[c];
+            }
+        }
+        out[t] = acc;
     }
     return SDA_OK;
 }

@@ -1,6 +1,7 @@
 r"""Lorenz experiment helpers (experiments/lorenz/utils.py:22-147 of the reference): the score-network factories, and the
 ground truth the evaluation is measured against -- ``make_chain``, ``log_prior``, ``log_likelihood``, the particle-filter
-``posterior`` and ``weak_4d_var``."""
+``posterior`` and ``weak_4d_var`` -- and ``strong_4d_var``, its strong-constraint counterpart.  ``grad='device'`` (opt-in) keeps the
+gradients of ``log_prior`` / ``weak_4d_var`` on the chain kernels; every default launches what it always launched."""
 
 from pathlib import Path
 from typing import Callable, Optional, Sequence
@@ -19,8 +20,8 @@ from ..utils import ACTIVATIONS, load_config
 LAST_POSTERIOR_ROUTE = None
 
 
-def make_chain() -> chains.MarkovChain:
-    return chains.NoisyLorenz63(dt=0.025)
+def make_chain(grad: str = 'torch') -> chains.MarkovChain:
+    return chains.NoisyLorenz63(dt=0.025, grad=grad)
 
 
 def make_global_score(
@@ -57,12 +58,33 @@ def load_score(file: Path, local: bool = False, device: str = 'cpu', **kwargs) -
     return score
 
 
-def log_prior(x: Tensor) -> Tensor:
+class _ChainLogProb(torch.autograd.Function):
+    """``ops.chain_log_prob_grad``: value and gradient in the forward's one launch.  The kernel takes no upstream cotangent, so
+    backward is one torch multiply of the kept gradient by the cotangent of each trajectory's value."""
+
+    @staticmethod
+    def forward(ctx, flat, model):
+        value, grad = ops.chain_log_prob_grad(model, flat)
+        ctx.save_for_backward(grad)
+        return value
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gout):
+        grad, = ctx.saved_tensors
+        return grad * gout.to(torch.float32)[:, None, None], None
+
+
+def log_prior(x: Tensor, *, grad: str = 'torch') -> Tensor:
     r"""sum_i log p(x_{i+1} | x_i) of (..., L, 3) trajectories under ``make_chain()`` (experiments/lorenz/utils.py:82-88): one
     ``sda_chain_log_prob`` launch, summed in float64.  An input that requires grad takes the torch-ops rk4, which autograd
-    differentiates (``weak_4d_var``)."""
-    chain = make_chain()
+    differentiates (``weak_4d_var``) -- or, with ``grad='device'`` and a float32 device input, one ``sda_chain_log_prob_grad`` launch
+    that returns the same value with its gradient (first order only).  ``chains.LAST_CHAIN_GRAD_ROUTE`` records which."""
+    chain = make_chain(grad)
     if torch.is_grad_enabled() and x.requires_grad:
+        if grad == 'device' and x.is_cuda and x.dtype == torch.float32:
+            chains.LAST_CHAIN_GRAD_ROUTE = 'device'
+            return _ChainLogProb.apply(x.reshape(-1, *x.shape[-2:]), chain.model()).to(x.dtype).reshape(x.shape[:-2])
         return chain.log_prob(x[..., :-1, :], x[..., 1:, :]).sum(dim=-1)
     ops._dev(x)
     flat = x.reshape(-1, *x.shape[-2:])
@@ -109,16 +131,16 @@ def posterior(y: Tensor, A: Callable[[Tensor], Tensor] = lambda x: x, sigma: flo
 
 
 def weak_4d_var(x: Tensor, y: Tensor, A: Callable[[Tensor], Tensor] = lambda x: x, sigma: float = 1.0, step: int = 1,
-                iterations: int = 16) -> Tensor:
+                iterations: int = 16, grad: str = 'torch') -> Tensor:
     r"""Weak-constraint 4D-Var by L-BFGS on the log-posterior (experiments/lorenz/utils.py:126-147); torch autograd around
-    ``log_prior``'s differentiable route."""
+    ``log_prior``'s differentiable route, which ``grad`` selects."""
     x_b = x[0]
     x = torch.nn.Parameter(x.clone())
     optimizer = torch.optim.LBFGS((x,))
 
     def closure():
         optimizer.zero_grad()
-        loss = (x[0] - x_b).square().sum() - log_prior(x) - log_likelihood(y, x, A, sigma, step)
+        loss = (x[0] - x_b).square().sum() - log_prior(x, grad=grad) - log_likelihood(y, x, A, sigma, step)
         loss.backward()
         return loss
 
@@ -126,3 +148,26 @@ def weak_4d_var(x: Tensor, y: Tensor, A: Callable[[Tensor], Tensor] = lambda x: 
         optimizer.step(closure)
 
     return x.data
+
+
+def strong_4d_var(x_b: Tensor, y: Tensor, A: Callable[[Tensor], Tensor] = lambda x: x, sigma: float = 1.0, step: int = 1,
+                  iterations: int = 16, chain: Optional[chains.MarkovChain] = None) -> Tensor:
+    r"""Strong-constraint 4D-Var by L-BFGS over the initial state of a deterministic chain, with the signature and objective of
+    ``experiments.kolmogorov.strong_4d_var``: minimises :math:`|x_0 - x_b|^2 + \sum |y - A(x_{1:L:step})|^2 / \sigma^2` where
+    ``x_{1:L} = chain.trajectory(x0, L)`` and ``L = len(y) * step``.  ``chain`` defaults to ``chains.Lorenz63(dt=0.025,
+    grad='device')``: per closure one forward launch and one adjoint launch, whatever L.  Any ``DiscreteODE`` serves (``Lorenz96``)."""
+    chain = chains.Lorenz63(dt=0.025, grad='device') if chain is None else chain
+    length = len(y) * step
+    x0 = torch.nn.Parameter(x_b.detach().clone())
+    optimizer = torch.optim.LBFGS((x0,))
+
+    def closure():
+        optimizer.zero_grad()
+        loss = (x0 - x_b).square().sum() + ((y - A(chain.trajectory(x0, length)[::step])).square() / sigma ** 2).sum()
+        loss.backward()
+        return loss
+
+    for _ in range(iterations):
+        optimizer.step(closure)
+
+    return x0.data

@@ -1271,6 +1271,55 @@ def chain_log_prob(model, x: Tensor) -> Tensor:
     return out
 
 
+def _rows(t: Tensor, shape, what: str) -> Tensor:
+    """t as fp32 rows of the given shape whose components are contiguous (strides stay the caller's otherwise)."""
+    _dev(t)
+    if tuple(t.shape) != tuple(shape):
+        raise _lib.SdaHipError(f'{what}: shape {tuple(t.shape)}, expected {tuple(shape)}')
+    return t if t.stride(-1) == 1 else t.contiguous()
+
+
+def chain_advance_vjp(model, x_in: Tensor, states: Optional[Tensor], g: Tensor, transitions: int, every: bool) -> Tensor:
+    """The cotangent (m, d) of x_in under `chain_advance(model, x_in, .., transitions, every=every)`, one launch.  `states`
+    (>= transitions - 1, m, d): the states after each transition as an every=True forward wrote them (with its noise, if any); None is
+    allowed for one transition.  g: (transitions, m, d) with every=True, the cotangent of every kept state, else (m, d)."""
+    if x_in.dim() != 2 or x_in.shape[1] != model.d or transitions < 1:
+        raise _lib.SdaHipError(f'chain_advance_vjp: states {tuple(x_in.shape)} for a {model.d}-component chain, {transitions} transitions')
+    m, d = x_in.shape
+    x_in = _rows(x_in, (m, d), 'chain_advance_vjp: x_in')
+    g = _rows(g, (transitions, m, d) if every else (m, d), 'chain_advance_vjp: g')
+    a = _lib.ChainVjp()
+    a.model = model
+    a.x_in, a.in_sp = x_in.data_ptr(), x_in.stride(0) if m > 1 else d
+    if transitions > 1:
+        if states is None or states.dim() != 3 or states.shape[0] < transitions - 1:
+            raise _lib.SdaHipError(f'chain_advance_vjp: {transitions} transitions need the {transitions - 1} states between them')
+        states = _rows(states, (states.shape[0], m, d), 'chain_advance_vjp: states')
+        a.states, a.st_st, a.st_sp = states.data_ptr(), states.stride(0), states.stride(1) if m > 1 else d
+    a.g, a.g_sp = g.data_ptr(), g.stride(-2) if m > 1 else d
+    a.g_st = g.stride(0) if every and transitions > 1 else 0
+    a.every, a.m, a.transitions = int(every), m, transitions
+    gx = torch.empty(m, d, device=x_in.device, dtype=torch.float32)
+    a.gx, a.gx_sp = gx.data_ptr(), d
+    _lib.check(_lib.load().sda_chain_advance_vjp(ctypes.byref(a), _stream()), 'sda_chain_advance_vjp')
+    return gx
+
+
+def chain_log_prob_grad(model, x: Tensor):
+    """x (b, L, d) -> (value (b,) float64 -- bitwise `chain_log_prob` -- and its gradient (b, L, d) fp32), one launch.  The
+    gradient is that of each value with cotangent 1; a caller with another cotangent scales it."""
+    _dev(x)
+    if x.dim() != 3 or x.shape[2] != model.d or x.shape[1] < 2:
+        raise _lib.SdaHipError(f'chain_log_prob_grad: trajectories {tuple(x.shape)} for a {model.d}-component chain')
+    if x.stride(2) != 1:
+        x = x.contiguous()
+    out = torch.empty(x.shape[0], device=x.device, dtype=torch.float64)
+    grad = torch.empty(x.shape, device=x.device, dtype=torch.float32)
+    _lib.check(_lib.load().sda_chain_log_prob_grad(ctypes.byref(model), x.data_ptr(), x.shape[0], x.shape[1], x.stride(0), x.stride(1),
+                                                   out.data_ptr(), grad.data_ptr(), _stream()), 'sda_chain_log_prob_grad')
+    return out, grad
+
+
 def bpf_logweights(x: Tensor, obs):
     """x (m, d) -> (logw (m,), pmax (blocks,)): affine-select Gaussian log-weights and the per-workgroup maxima."""
     _dev(x)
