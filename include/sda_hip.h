@@ -1094,6 +1094,30 @@ int sda_lgss_score_factor(int d, int T, const double* prec, const float* coef, d
 int sda_lgss_score(int d, int T, const double* prec, const float* coef, const double* work, const float* x, int n, int zero_mean,
                    double* ywork, float* out, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Stochastic ensemble Kalman smoother (csrc/enks.hip; additive, ABI stays v14): per observation one gain launch and one update
+ * launch, whatever the ensemble size m, the observed components k or the window length.  Ensemble slabs are [m][d] fp32 (member
+ * stride in floats given per call, components contiguous); a, z and work are [k][m] fp32 scratch.  One analysis is
+ *   step 1  inflation of the observed slab: x_j <- xbar + lambda (x_j - xbar); lambda == 1 touches nothing;
+ *   step 2  h_j = (x_j[idx[r]] - shift[r]) / scale[r] (the sda_chain_obs selection), hbar, a_j = h_j - hbar;
+ *   step 3  C = sum_j a_j a_j^T / (m - 1) + sigma^2 I, its Cholesky factor and inverse, all float64;
+ *   step 4  z_j = C^-1 ((y + sigma eps_j) - h_j), eps_j[r] = element r of row j of sda_randn_rows(.., seed ^ 0x454E4B53, 0, draw);
+ *   step 5  for every slab s of the window and component c: p = sum_j (x_j[s][c] - xbar[s][c]) a_j / (m - 1), x_j[s][c] += p . z_j.
+ * Every sum over the members is float64 with an order fixed by m alone; no atomics; bitwise reproducible.
+ *
+ * sda_enks_gain: steps 2 - 4 in ONE launch of one workgroup.  x = the observed slab, read as step 1 WOULD leave it (it is not
+ *   written).  status[0] = 0, or 1 when a pivot of the factor is not positive and finite (z is then 0, so the update adds
+ *   nothing); read it once, at the end, as sda_bpf_cdf's.
+ * sda_enks_update: steps 1 and 5 in ONE launch over the nslab slabs S + s * s_st, one workgroup per slab; the LAST slab is the
+ *   observed one and the only one inflated.  A slab's result does not depend on nslab.  Memory outside those slabs is not touched.
+ * Served: 2 <= m <= 2^22, 1 <= d <= 64, 1 <= k <= min(d, SDA_CHAIN_MAXOBS); anything else is SDA_E_BADARG / SDA_E_UNSUPPORTED
+ * before any launch.
+ * ------------------------------------------------------------------------------------------ */
+int sda_enks_gain(const float* x, int m, int64_t sp, int d, const sda_chain_obs* obs, float inflation, uint64_t seed, int64_t draw,
+                  float* a, float* z, float* work, int32_t* status, void* stream);
+int sda_enks_update(float* S, int64_t s_st, int64_t s_sp, int nslab, int m, int d, int k, float inflation, const float* a,
+                    const float* z, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

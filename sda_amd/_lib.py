@@ -453,6 +453,9 @@ SIGNATURES = {
     'sda_lgss_score_doubles': (c_int64, [c_int, c_int, c_int]),
     'sda_lgss_score_factor': (c_int, [c_int, c_int, c_fp, c_fp, c_fp, c_void_p]),
     'sda_lgss_score': (c_int, [c_int, c_int, c_fp, c_fp, c_fp, c_fp, c_int, c_int, c_fp, c_fp, c_void_p]),
+    # ensemble Kalman smoother (csrc/enks.hip)
+    'sda_enks_gain': (c_int, [c_fp, c_int, c_int64, c_int, POINTER(ChainObs), c_float, c_uint64, c_int64, c_fp, c_fp, c_fp, c_fp, c_void_p]),
+    'sda_enks_update': (c_int, [c_fp, c_int64, c_int64, c_int, c_int, c_int, c_int, c_float, c_fp, c_fp, c_void_p]),
 }
 
 _lib = None

@@ -30,7 +30,7 @@ from . import ops
 from ._lib import CHAIN_MAXOBS, SdaHipError
 
 __all__ = ['MarkovChain', 'DiscreteODE', 'Lorenz63', 'NoisyLorenz63', 'Lorenz96', 'LotkaVolterra', 'KolmogorovFlow', 'LinearGaussian',
-           'DampedSpring', 'AffineObservation', 'probe_affine', 'probe_linear', 'bpf_fused', 'install']
+           'DampedSpring', 'AffineObservation', 'probe_affine', 'probe_linear', 'bpf_fused', 'enks_fused', 'install']
 
 
 def _draw_seed() -> int:
@@ -754,6 +754,69 @@ def bpf_fused(chain: DiscreteODE, x: Tensor, y: Tensor, obs: AffineObservation, 
     if record is not None:
         record.update(S=S, anc=anc, seed=seed, draw0=draw0)
     return out
+
+
+def enks_fused(chain: MarkovChain, x: Tensor, y: Tensor, obs: AffineObservation, sigma: float, step: int = 1, *,
+               lag: Optional[int] = None, inflation: float = 1.0, seed: Optional[int] = None, record: Optional[dict] = None) -> Tensor:
+    r"""Stochastic (perturbed-observation) ensemble Kalman smoother with ``chain``'s transitions and the Gaussian likelihood
+    N(y_i; obs(x), sigma): per observation ONE forecast launch (``step`` transitions written straight into the time-major
+    ensemble), one gain launch and one update launch over the smoothing window (csrc/enks.hip; the five steps are in
+    include/sda_hip.h).  x (M, d) initial members, y (N, k); returns (M, N step + 1, d).  Observation i sits at time (i + 1) step;
+    its analysis updates the times lo .. (i + 1) step with lo = 0, or max(0, (i + 1 - lag) step) when ``lag`` (in observations) is
+    given; ``lag=0`` is the ensemble Kalman filter.  ``inflation`` scales the forecast anomalies of the observed time.
+
+    The forecast of a served ``DiscreteODE`` is ``ops.chain_advance`` with ``bpf_fused``'s draw bookkeeping; any other chain
+    (``DampedSpring``) forecasts with ``chain.trajectory``.  The perturbation of member j at observation i is row j of
+    ``ops.randn_rows(.., seed ^ 0x454E4B53, 0, draw=i)``.  One read-back, at the end: raises SdaHipError if an innovation
+    covariance had no Cholesky factor.  ``record``: a dict that receives, per analysis, the ensemble before it (``S``), ``a``,
+    ``z``, and the status words (tests and small shapes only: every entry is a copy)."""
+    ops._dev(x)
+    if x.dim() != 2:
+        raise SdaHipError(f'enks_fused: members of shape {tuple(x.shape)}, expected (M, d)')
+    m, d = x.shape
+    n = len(y)
+    y = y.to(device=x.device, dtype=torch.float32).reshape(n, -1).contiguous()
+    if y.shape[1] != len(obs.index) or n < 1 or step < 1 or m < 2 or (lag is not None and lag < 0):
+        raise SdaHipError(f'enks_fused: {tuple(y.shape)} observations for {len(obs.index)} observed components, {m} members, step '
+                          f'{step}, lag {lag}')
+    served = isinstance(chain, DiscreteODE) and chain._served()
+    seed = _draw_seed() if seed is None else int(seed)
+    dev = x.device
+    S = torch.empty(n * step + 1, m, d, device=dev, dtype=torch.float32)
+    S[0] = x
+    if served:
+        model = chain.model()
+        if model.d != d:
+            raise SdaHipError(f'enks_fused: members of shape {tuple(x.shape)} for a {model.d}-component chain')
+        draw0 = chain._draw
+        chain._draw += n * step
+    k = len(obs.index)
+    a, z, work = (torch.empty(k, m, device=dev, dtype=torch.float32) for _ in range(3))
+    status = torch.zeros(n, device=dev, dtype=torch.int32)
+    o = ops.chain_obs(obs.index, obs.shift, obs.scale, sigma, y[0])
+    if record is not None:
+        record.update(S=[], a=[], z=[], seed=seed)
+    for i in range(n):
+        t = (i + 1) * step
+        if served:
+            ops.chain_advance(model, S[i * step], S[i * step + 1:], step, every=True, out_st=m * d, seed=seed, draw0=draw0 + i * step)
+        elif isinstance(chain, (LinearGaussian, NoisyLorenz63)):
+            S[i * step + 1:t + 1] = chain.trajectory(S[i * step], step, seed=seed)
+        else:
+            S[i * step + 1:t + 1] = chain.trajectory(S[i * step], step)
+        lo = 0 if lag is None else max(0, t - lag * step)
+        o.y = y[i].data_ptr()
+        if record is not None:
+            record['S'].append(S.clone())
+        ops.enks_gain(S, t, o, inflation=inflation, seed=seed, draw=i, a=a, z=z, work=work, status=status[i:i + 1])
+        ops.enks_update(S, lo, t, a, z, inflation=inflation)
+        if record is not None:
+            record['a'].append(a.clone())
+            record['z'].append(z.clone())
+    if record is not None:
+        record.update(status=status.clone())
+    ops.enks_check(status)                                   # the one read-back of the smoother
+    return S.permute(1, 0, 2).contiguous()
 
 
 def install() -> None:

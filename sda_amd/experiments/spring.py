@@ -78,6 +78,25 @@ def posterior(y: Tensor, A: Callable[[Tensor], Tensor] = _IDENTITY, sigma: float
     return out if y.dim() == 3 else out[0]
 
 
+def enks(y: Tensor, A: Callable[[Tensor], Tensor] = _IDENTITY, sigma: float = 1.0, step: int = 1, members: int = 1024, *,
+         lag: Optional[int] = None, inflation: float = 1.0, chain: Optional[chains.LinearGaussian] = None, burn: int = 64,
+         seed: Optional[int] = None, device=None) -> Tensor:
+    r"""Ensemble-Kalman-smoother samples of p(x_{0:L} | y), (members, T + 1, d) fp32 on the device under the time convention above
+    (``chains.enks_fused(...)[:, step:]``): the approximate counterpart of ``posterior``, which it approaches as ``members`` grows.
+    ``A`` must probe as an affine selection of state components (``chains.probe_affine``)."""
+    chain = make_chain() if chain is None else chain
+    if device is None:
+        device = y.device if y.is_cuda else torch.device('cuda')
+    obs = chains.probe_affine(A, chain, chain.d)
+    if obs is None:
+        raise SdaHipError('enks: A is not an affine selection of state components (each output an affine function of exactly one '
+                          'component)')
+    x = chain.prior((members,), device=device)
+    if burn > 0:
+        x = chain.trajectory(x, length=burn, last=True, seed=seed)
+    return chains.enks_fused(chain, x, y.to(device), obs, sigma, step, lag=lag, inflation=inflation, seed=seed)[:, step:]
+
+
 def log_evidence(y: Tensor, A: Callable[[Tensor], Tensor] = _IDENTITY, sigma: float = 1.0, step: int = 1, burn: int = 64, *,
                  chain: Optional[chains.LinearGaussian] = None, device=None) -> Tensor:
     """log p(y), float64 on the device: () for y (N, k), (B,) for y (B, N, k)."""

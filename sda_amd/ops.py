@@ -1387,6 +1387,65 @@ def bpf_traceback(S: Tensor, anc: Tensor, step: int) -> Tensor:
     return out
 
 
+# ---------------------------------------------------------------- ensemble Kalman smoother (csrc/enks.hip)
+def _enks_slabs(S: Tensor, what: str):
+    _dev(S)
+    if S.dim() != 3 or S.stride(2) != 1 or S.shape[1] < 2 or (S.stride(1) < S.shape[2]) or S.stride(0) < 0:
+        raise _lib.SdaHipError(f'{what}: ensemble slabs {tuple(S.shape)} (strides {S.stride()}), expected (time, members, d) with '
+                               f'contiguous components')
+
+
+def _enks_scratch(t: Optional[Tensor], k: int, m: int, like: Tensor, what: str) -> Tensor:
+    if t is None:
+        return torch.empty(k, m, device=like.device, dtype=torch.float32)
+    _dev(t)
+    if tuple(t.shape) != (k, m) or not t.is_contiguous():
+        raise _lib.SdaHipError(f'{what}: a contiguous ({k}, {m}) fp32 device tensor expected')
+    return t
+
+
+def enks_gain(S: Tensor, t: int, obs, *, inflation: float = 1.0, seed: int = 0, draw: int = 0, a: Optional[Tensor] = None,
+              z: Optional[Tensor] = None, work: Optional[Tensor] = None, status: Optional[Tensor] = None):
+    """Steps 2 - 4 of one analysis (include/sda_hip.h) on slab ``S[t]`` of the time-major ensemble S (time, members, d): the observed
+    anomalies ``a`` and the solved perturbed innovations ``z``, both (k, members), and status (1,) int32 (1: the factorisation
+    failed), one launch, nothing read back.  ``obs``: an ``ops.chain_obs`` carrying this observation's y.  S is only read."""
+    _enks_slabs(S, 'enks_gain')
+    if not 0 <= t < S.shape[0]:
+        raise _lib.SdaHipError(f'enks_gain: slab {t} of {S.shape[0]}')
+    m, d, k = S.shape[1], S.shape[2], obs.k
+    a, z, work = (_enks_scratch(v, k, m, S, 'enks_gain') for v in (a, z, work))
+    status = torch.zeros(1, device=S.device, dtype=torch.int32) if status is None else status
+    if status.dtype != torch.int32 or status.numel() < 1 or not status.is_cuda:
+        raise _lib.SdaHipError('enks_gain: status (1,) int32 on the device expected')
+    x = S[t]
+    _lib.check(_lib.load().sda_enks_gain(x.data_ptr(), m, S.stride(1), d, ctypes.byref(obs), float(inflation),
+                                         seed & 0xffffffffffffffff, draw, a.data_ptr(), z.data_ptr(), work.data_ptr(),
+                                         status.data_ptr(), _stream()), 'sda_enks_gain')
+    return a, z, status
+
+
+def enks_update(S: Tensor, lo: int, t: int, a: Tensor, z: Tensor, *, inflation: float = 1.0) -> Tensor:
+    """Steps 1 and 5 of one analysis, in place on the slabs ``S[lo] .. S[t]`` (``S[t]`` the observed one), one launch."""
+    _enks_slabs(S, 'enks_update')
+    if not 0 <= lo <= t < S.shape[0]:
+        raise _lib.SdaHipError(f'enks_update: window {lo} .. {t} of {S.shape[0]} slabs')
+    m, d = S.shape[1], S.shape[2]
+    _dev(a, z)
+    k = a.shape[0] if a.dim() == 2 else 0
+    if tuple(a.shape) != (k, m) or tuple(z.shape) != (k, m) or not a.is_contiguous() or not z.is_contiguous():
+        raise _lib.SdaHipError(f'enks_update: a {tuple(a.shape)} and z {tuple(z.shape)}, expected contiguous (k, {m})')
+    _lib.check(_lib.load().sda_enks_update(S[lo].data_ptr(), S.stride(0), S.stride(1), t - lo + 1, m, d, k, float(inflation),
+                                           a.data_ptr(), z.data_ptr(), _stream()), 'sda_enks_update')
+    return S
+
+
+def enks_check(status: Tensor) -> None:
+    """Raise if the innovation covariance of any analysis had no Cholesky factor (a pivot not positive and finite)."""
+    bad = status.nonzero().flatten().tolist()
+    if bad:
+        raise _lib.SdaHipError(f'ensemble Kalman smoother: the innovation covariance is not positive definite at observation(s) {bad}')
+
+
 # ---------------------------------------------------------------- Kolmogorov flow (csrc/kflow.hip)
 _KFLOW_CONST = {}
 _KFLOW_SOLVE = {}
