@@ -1,158 +1,30 @@
 // Markov chains (sda/mcs.py:85-241) and the bootstrap particle filter (sda/utils.py:168-200) of the reference's Lorenz
 // evaluation (experiments/lorenz/eval.py:44-68), as one launch per PHASE: advance (+ log-weights) -> cdf -> resample per
 // observation, one traceback at the end.  No kernel waits for another workgroup: every hand-off is a launch boundary.
-// The arithmetic of a transition lives in __host__ __device__ functions; under SDA_HOST_EMU the same functions run as plain
-// loops over host arrays (bottom of the file), which is what the CPU tests check.
+// The arithmetic of a transition is not mirrored between device and host: it IS one piece of code.  The RK4 stage sequence, its
+// reverse sweep and the recompute loop are templates over a system policy (chain_rk4.hpp), and the noise, log-density, resampling
+// and traceback are __host__ __device__ functions here; under SDA_HOST_EMU the same functions run inside plain loops over host
+// arrays (bottom of the file), which is what the CPU tests check.  Shared: every float operation and its order.  Not shared: the
+// kernels' geometry and wave reductions, and how Lorenz-96 reaches a neighbour component -- a shuffle on the device (L96LaneSys),
+// an array index on the host (L96ArraySys), both wired by l96_lanes.
 //
 // Latency-bound by design: 16 384 particles x 3 floats is 192 KiB, one RK4 transition is ~100 flops per particle.  What the
 // fusion removes is the ~40 elementwise launches per transition and the O(M T^2) history copies of the reference's
 // cat / x[j] (sda/utils.py:193-200).
 #include "sda_common.hpp"
+#include "chain_check.hpp"
+#include "chain_rk4.hpp"
 #include "philox.hpp"
 
 #define CH_THREADS 256
 
-// ---------------------------------------------------------------- RK4 (sda/mcs.py:98-110), one component, reference order
-__host__ __device__ __forceinline__ float rk4_half(float x, float h, float k) { return x + h * k / 2.0f; }
-__host__ __device__ __forceinline__ float rk4_full(float x, float h, float k) { return x + h * k; }
-__host__ __device__ __forceinline__ float rk4_comb(float x, float h, float k1, float k2, float k3, float k4) {
-    return x + h * (k1 + 2.0f * k2 + 2.0f * k3 + k4) / 6.0f;
-}
+// the system of a small-state model kind (one particle in the registers of one lane)
+template <int KIND> struct ChainSmall { typedef Lorenz63Sys Sys; };
+template <> struct ChainSmall<SDA_CHAIN_LOTKA_VOLTERRA> { typedef LotkaVolterraSys Sys; };
 
-// sda/mcs.py:153-158
-__host__ __device__ __forceinline__ void lorenz63_f(const float* p, const float* x, float* f) {
-    f[0] = p[0] * (x[1] - x[0]);
-    f[1] = x[0] * (p[1] - x[2]) - x[1];
-    f[2] = x[0] * x[1] - p[2] * x[2];
-}
-// sda/mcs.py:237-241
-__host__ __device__ __forceinline__ void lotka_volterra_f(const float* p, const float* x, float* f) {
-    f[0] = p[0] - p[1] * expf(x[1]);
-    f[1] = p[2] * expf(x[0]) - p[3];
-}
-// sda/mcs.py:208-211: (roll(x, 1) - roll(x, -2)) roll(x, -1) - x + F, one component
-__host__ __device__ __forceinline__ float lorenz96_f(float xm1, float xp2, float xp1, float x, float F) {
-    return (xm1 - xp2) * xp1 - x + F;
-}
-
-// `count` RK4 sub-steps of a small-state chain, state in registers
-template <int KIND>
-__host__ __device__ __forceinline__ void chain_small_substeps(const sda_chain_model& m, float* x, int count) {
-    constexpr int D = KIND == SDA_CHAIN_LORENZ63 ? 3 : 2;
-    for (int s = 0; s < count; ++s) {
-        float k1[D], k2[D], k3[D], k4[D], t[D];
-        if (KIND == SDA_CHAIN_LORENZ63) lorenz63_f(m.p, x, k1); else lotka_volterra_f(m.p, x, k1);
-#pragma unroll
-        for (int c = 0; c < D; ++c) t[c] = rk4_half(x[c], m.h, k1[c]);
-        if (KIND == SDA_CHAIN_LORENZ63) lorenz63_f(m.p, t, k2); else lotka_volterra_f(m.p, t, k2);
-#pragma unroll
-        for (int c = 0; c < D; ++c) t[c] = rk4_half(x[c], m.h, k2[c]);
-        if (KIND == SDA_CHAIN_LORENZ63) lorenz63_f(m.p, t, k3); else lotka_volterra_f(m.p, t, k3);
-#pragma unroll
-        for (int c = 0; c < D; ++c) t[c] = rk4_full(x[c], m.h, k3[c]);
-        if (KIND == SDA_CHAIN_LORENZ63) lorenz63_f(m.p, t, k4); else lotka_volterra_f(m.p, t, k4);
-#pragma unroll
-        for (int c = 0; c < D; ++c) x[c] = rk4_comb(x[c], m.h, k1[c], k2[c], k3[c], k4[c]);
-    }
-}
-
-// one transition (model.steps sub-steps)
-template <int KIND>
-__host__ __device__ __forceinline__ void chain_small_transition(const sda_chain_model& m, float* x) {
-    chain_small_substeps<KIND>(m, x, m.steps);
-}
-
-// ---------------------------------------------------------------- the reverse sweep of one RK4 sub-step.  With gy the cotangent of
-// y = x + h (k1 + 2 k2 + 2 k3 + k4) / 6 and jt_i = J_f(v_i)^T gk_i at the recomputed stage point v_i (v_1 = x):
-//   gk4 = h/6 gy, gk3 = h/3 gy + h jt4, gk2 = h/3 gy + h/2 jt3, gk1 = h/6 gy + h/2 jt2, gx = gy + jt4 + jt3 + jt2 + jt1.
-__host__ __device__ __forceinline__ float rk4r_k4(float h, float gy) { return h * gy / 6.0f; }
-__host__ __device__ __forceinline__ float rk4r_k3(float h, float gy, float jt4) { return h * gy / 3.0f + h * jt4; }
-__host__ __device__ __forceinline__ float rk4r_k2(float h, float gy, float jt3) { return h * gy / 3.0f + h * jt3 / 2.0f; }
-__host__ __device__ __forceinline__ float rk4r_k1(float h, float gy, float jt2) { return h * gy / 6.0f + h * jt2 / 2.0f; }
-__host__ __device__ __forceinline__ float rk4r_x(float gy, float jt1, float jt2, float jt3, float jt4) { return gy + jt4 + jt3 + jt2 + jt1; }
-
-// f at a stage point, keeping what its Jacobian reuses: e = exp of the point for Lotka-Volterra (the same two expf as
-// lotka_volterra_f, so f is bitwise the forward's), nothing for Lorenz-63
-template <int KIND>
-__host__ __device__ __forceinline__ void small_f_keep(const float* p, const float* v, float* f, float* e) {
-    if (KIND == SDA_CHAIN_LORENZ63) {
-        lorenz63_f(p, v, f);
-    } else {
-        e[0] = expf(v[0]);
-        e[1] = expf(v[1]);
-        f[0] = p[0] - p[1] * e[1];
-        f[1] = p[2] * e[0] - p[3];
-    }
-}
-// o = J_f(v)^T g
-template <int KIND>
-__host__ __device__ __forceinline__ void small_jt(const float* p, const float* v, const float* e, const float* g, float* o) {
-    if (KIND == SDA_CHAIN_LORENZ63) {
-        o[0] = (p[1] - v[2]) * g[1] - p[0] * g[0] + v[1] * g[2];
-        o[1] = p[0] * g[0] - g[1] + v[0] * g[2];
-        o[2] = -(v[0] * g[1]) - p[2] * g[2];
-    } else {
-        o[0] = p[2] * e[0] * g[1];
-        o[1] = -(p[1] * e[1] * g[0]);
-    }
-}
-// Lorenz-96 in gather form: f_c = (x_{c-1} - x_{c+2}) x_{c+1} - x_c + F reaches x_j from c = j + 1, j - 2 and j - 1 (and j itself)
-__host__ __device__ __forceinline__ float lorenz96_jt(float gp1, float xp2, float gm2, float xm1, float gm1, float xm2, float xp1,
-                                                      float g) {
-    return gp1 * xp2 - gm2 * xm1 + gm1 * (xm2 - xp1) - g;
-}
-
-// g <- (d sub-step / dx at x)^T g for a small-state chain: the four stage points recomputed, everything in registers
-template <int KIND>
-__host__ __device__ __forceinline__ void chain_small_substep_vjp(const sda_chain_model& m, const float* x, float* g) {
-    constexpr int D = KIND == SDA_CHAIN_LORENZ63 ? 3 : 2;
-    const float h = m.h;
-    float k[D], v2[D], v3[D], v4[D], e1[D], e2[D], e3[D], e4[D], gk[D], j1[D], j2[D], j3[D], j4[D];
-    small_f_keep<KIND>(m.p, x, k, e1);
-#pragma unroll
-    for (int c = 0; c < D; ++c) v2[c] = rk4_half(x[c], h, k[c]);
-    small_f_keep<KIND>(m.p, v2, k, e2);
-#pragma unroll
-    for (int c = 0; c < D; ++c) v3[c] = rk4_half(x[c], h, k[c]);
-    small_f_keep<KIND>(m.p, v3, k, e3);
-#pragma unroll
-    for (int c = 0; c < D; ++c) v4[c] = rk4_full(x[c], h, k[c]);
-    small_f_keep<KIND>(m.p, v4, k, e4);                 // (only e4 is used: k4 itself does not enter the reverse sweep)
-#pragma unroll
-    for (int c = 0; c < D; ++c) gk[c] = rk4r_k4(h, g[c]);
-    small_jt<KIND>(m.p, v4, e4, gk, j4);
-#pragma unroll
-    for (int c = 0; c < D; ++c) gk[c] = rk4r_k3(h, g[c], j4[c]);
-    small_jt<KIND>(m.p, v3, e3, gk, j3);
-#pragma unroll
-    for (int c = 0; c < D; ++c) gk[c] = rk4r_k2(h, g[c], j3[c]);
-    small_jt<KIND>(m.p, v2, e2, gk, j2);
-#pragma unroll
-    for (int c = 0; c < D; ++c) gk[c] = rk4r_k1(h, g[c], j2[c]);
-    small_jt<KIND>(m.p, x, e1, gk, j1);
-#pragma unroll
-    for (int c = 0; c < D; ++c) g[c] = rk4r_x(g[c], j1[c], j2[c], j3[c], j4[c]);
-}
-
-// g <- (d transition / dx at x0)^T g.  The states inside a transition are not stored: sub-step s, last to first, starts from x0
-// advanced s sub-steps again (O(steps^2) on D floats, bitwise the forward's states).
-template <int KIND>
-__host__ __device__ __forceinline__ void chain_small_transition_vjp(const sda_chain_model& m, const float* x0, float* g) {
-    constexpr int D = KIND == SDA_CHAIN_LORENZ63 ? 3 : 2;
-    for (int s = m.steps - 1; s >= 0; --s) {
-        float x[D];
-#pragma unroll
-        for (int c = 0; c < D; ++c) x[c] = x0[c];
-        chain_small_substeps<KIND>(m, x, s);
-        chain_small_substep_vjp<KIND>(m, x, g);
-    }
-}
-
-// the four normals of quad q of global row `grow` in draw t: what sda_randn_rows writes to elements 4q .. 4q+3 of that row
+// the four normals of quad q of global row `grow` in draw t of the sda_randn_rows stream
 __host__ __device__ __forceinline__ void chain_noise4(uint64_t seed, uint64_t grow, int64_t t, int64_t q, float* z) {
-    const philox4 w = philox_noise_words(q, grow, t, (uint32_t)seed, (uint32_t)(seed >> 32));
-    box_muller(w.v[0], w.v[1], z[0], z[1]);
-    box_muller(w.v[2], w.v[3], z[2], z[3]);
+    philox_normal4(q, grow, t, (uint32_t)seed, (uint32_t)(seed >> 32), z);
 }
 
 // log N(v; mu, s) as torch.distributions.Normal.log_prob writes it, in float64
@@ -208,14 +80,14 @@ __host__ __device__ __forceinline__ void bpf_traceback_one(const float* S, int64
 // log p(x_next | x) of a small-state chain (NoisyLorenz63.log_prob, sda/mcs.py:184-185)
 template <int KIND>
 __host__ __device__ __forceinline__ double chain_pair_log_prob(const sda_chain_model& m, const float* x, const float* x_next) {
-    constexpr int D = KIND == SDA_CHAIN_LORENZ63 ? 3 : 2;
-    float mu[D];
+    using Sys = typename ChainSmall<KIND>::Sys;
+    float mu[Sys::N];
 #pragma unroll
-    for (int c = 0; c < D; ++c) mu[c] = x[c];
-    chain_small_transition<KIND>(m, mu);
+    for (int c = 0; c < Sys::N; ++c) mu[c] = x[c];
+    rk4_transition(Sys{m.p}, m.h, m.steps, mu);
     double l = 0.0;
 #pragma unroll
-    for (int c = 0; c < D; ++c) l += normal_log_prob((double)x_next[c], (double)mu[c], (double)m.noise_std);
+    for (int c = 0; c < Sys::N; ++c) l += normal_log_prob((double)x_next[c], (double)mu[c], (double)m.noise_std);
     return l;
 }
 
@@ -224,18 +96,19 @@ __host__ __device__ __forceinline__ double chain_pair_log_prob(const sda_chain_m
 template <int KIND>
 __host__ __device__ __forceinline__ double chain_pair_residual(const sda_chain_model& m, const float* x, const float* x_next, float* r,
                                                                float* jtr) {
-    constexpr int D = KIND == SDA_CHAIN_LORENZ63 ? 3 : 2;
-    float mu[D];
+    using Sys = typename ChainSmall<KIND>::Sys;
+    const Sys sys{m.p};
+    float mu[Sys::N];
 #pragma unroll
-    for (int c = 0; c < D; ++c) mu[c] = x[c];
-    chain_small_transition<KIND>(m, mu);
+    for (int c = 0; c < Sys::N; ++c) mu[c] = x[c];
+    rk4_transition(sys, m.h, m.steps, mu);
     double l = 0.0;
 #pragma unroll
-    for (int c = 0; c < D; ++c) l += normal_log_prob((double)x_next[c], (double)mu[c], (double)m.noise_std);
+    for (int c = 0; c < Sys::N; ++c) l += normal_log_prob((double)x_next[c], (double)mu[c], (double)m.noise_std);
     const float s2 = m.noise_std * m.noise_std;
 #pragma unroll
-    for (int c = 0; c < D; ++c) { r[c] = (x_next[c] - mu[c]) / s2; jtr[c] = r[c]; }
-    chain_small_transition_vjp<KIND>(m, x, jtr);
+    for (int c = 0; c < Sys::N; ++c) { r[c] = (x_next[c] - mu[c]) / s2; jtr[c] = r[c]; }
+    rk4_transition_vjp(sys, m.h, m.steps, x, jtr);
     return l;
 }
 
@@ -245,13 +118,6 @@ static int chain_model_check(const sda_chain_model* m) {
     if (m->kind == SDA_CHAIN_LOTKA_VOLTERRA) return m->d == 2 ? SDA_OK : SDA_E_BADARG;
     if (m->kind == SDA_CHAIN_LORENZ96) return m->d >= 4 && m->d <= 64 ? SDA_OK : SDA_E_UNSUPPORTED;
     return SDA_E_UNSUPPORTED;
-}
-
-static int chain_obs_check(const sda_chain_obs* o, int d) {
-    if (!o || !o->y || o->k < 1 || o->k > d || o->k > SDA_CHAIN_MAXOBS || !(o->sigma > 0.f)) return SDA_E_BADARG;
-    for (int k = 0; k < o->k; ++k)
-        if (o->idx[k] < 0 || o->idx[k] >= d || o->scale[k] == 0.f) return SDA_E_BADARG;
-    return SDA_OK;
 }
 
 static int chain_adv_check(const sda_chain_adv* a) {
@@ -280,19 +146,47 @@ static int chain_vjp_check(const sda_chain_vjp* a) {
     return SDA_OK;
 }
 
-static int chain_lpg_check(const sda_chain_model* model, const float* x, int b, int len, int64_t sb, int64_t sl, const double* out,
-                           const float* grad) {
+static int chain_lp_check(const sda_chain_model* model, const float* x, int b, int len, int64_t sl, const double* out) {
     int rc = chain_model_check(model);
     if (rc != SDA_OK) return rc;
     if (model->kind == SDA_CHAIN_LORENZ96) return SDA_E_UNSUPPORTED;
-    if (!x || !out || !grad || b < 1 || len < 2 || sl < model->d || !(model->noise_std > 0.f)) return SDA_E_BADARG;
+    if (!x || !out || b < 1 || len < 2 || sl < model->d || !(model->noise_std > 0.f)) return SDA_E_BADARG;
     return SDA_OK;
+}
+
+static int chain_lpg_check(const sda_chain_model* model, const float* x, int b, int len, int64_t sl, const double* out,
+                           const float* grad) {
+    int rc = chain_lp_check(model, x, b, len, sl, out);
+    return rc != SDA_OK ? rc : (grad ? SDA_OK : SDA_E_BADARG);
 }
 
 extern "C" int sda_bpf_logweights_blocks(int m) { return m < 1 ? SDA_E_BADARG : (m + CH_THREADS - 1) / CH_THREADS; }
 
 #ifndef SDA_HOST_EMU
 // ---------------------------------------------------------------- device kernels
+// launch KERNEL<kind> for one of the two small-state kinds (the checks have refused every other kind for these entries) on
+// ceil(items / per_block) workgroups
+#define CHAIN_LAUNCH_SMALL(kind, KERNEL, items, per_block, stream, ...)                                                        \
+    do {                                                                                                                       \
+        const dim3 grid((unsigned)(((items) + (per_block) - 1) / (per_block)));                                                \
+        if ((kind) == SDA_CHAIN_LORENZ63)                                                                                      \
+            hipLaunchKernelGGL(KERNEL<SDA_CHAIN_LORENZ63>, grid, dim3(CH_THREADS), 0, stream, __VA_ARGS__);                    \
+        else                                                                                                                   \
+            hipLaunchKernelGGL(KERNEL<SDA_CHAIN_LOTKA_VOLTERRA>, grid, dim3(CH_THREADS), 0, stream, __VA_ARGS__);              \
+    } while (0)
+
+// the Lorenz-96 launch: sub-groups of W lanes (W = next power of two >= d, at least 4), CH_THREADS / W particles per workgroup
+static int chain_l96_geometry(int d, int m, int* W, unsigned* blocks) {
+    int w = 4;
+    while (w < d) w <<= 1;
+    const int per_block = CH_THREADS / w;
+    const int64_t nb = ((int64_t)m + per_block - 1) / per_block;
+    if (nb > 0x7fffffff) return SDA_E_UNSUPPORTED;
+    *W = w;
+    *blocks = (unsigned)nb;
+    return SDA_OK;
+}
+
 struct ChainAdvArgs {       // sda_chain_adv without the host pointer
     sda_chain_model model;
     const float* x_in; int64_t in_sp; const int32_t* anc;
@@ -304,8 +198,7 @@ struct ChainAdvArgs {       // sda_chain_adv without the host pointer
 // max over the workgroup's CH_THREADS values -> pmax[blockIdx.x] (every thread of the workgroup calls it)
 __device__ __forceinline__ void block_max_store(float v, float* pmax) {
     __shared__ float s_max[CH_THREADS / SDA_WAVE];
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v = fmaxf(v, __shfl_down(v, off, SDA_WAVE));
+    v = sda_wave_max(v);
     if ((threadIdx.x & 63) == 0) s_max[threadIdx.x >> 6] = v;
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -318,32 +211,32 @@ __device__ __forceinline__ void block_max_store(float v, float* pmax) {
 
 template <int KIND>
 __global__ __launch_bounds__(CH_THREADS) void chain_advance_small_kernel(ChainAdvArgs a, sda_chain_obs obs) {
-    constexpr int D = KIND == SDA_CHAIN_LORENZ63 ? 3 : 2;
+    using Sys = typename ChainSmall<KIND>::Sys;
     const int j = blockIdx.x * CH_THREADS + threadIdx.x;
     const bool live = j < a.m;
-    float x[D];
+    float x[Sys::N];
 #pragma unroll
-    for (int c = 0; c < D; ++c) x[c] = 0.f;
+    for (int c = 0; c < Sys::N; ++c) x[c] = 0.f;
     if (live) {
         const int src = a.anc ? clamp_slot(a.anc[j], a.m) : j;
 #pragma unroll
-        for (int c = 0; c < D; ++c) x[c] = a.x_in[src * a.in_sp + c];
+        for (int c = 0; c < Sys::N; ++c) x[c] = a.x_in[src * a.in_sp + c];
         for (int t = 0; t < a.transitions; ++t) {
-            chain_small_transition<KIND>(a.model, x);
+            rk4_transition(Sys{a.model.p}, a.model.h, a.model.steps, x);
             if (a.model.noise_std > 0.f) {
                 float z[4];
                 chain_noise4(a.seed, (uint64_t)(a.row0 + j), a.draw0 + t, 0, z);
 #pragma unroll
-                for (int c = 0; c < D; ++c) x[c] = x[c] + a.model.noise_std * z[c];
+                for (int c = 0; c < Sys::N; ++c) x[c] = x[c] + a.model.noise_std * z[c];
             }
             if (a.every) {
 #pragma unroll
-                for (int c = 0; c < D; ++c) a.out[t * a.out_st + j * a.out_sp + c] = x[c];
+                for (int c = 0; c < Sys::N; ++c) a.out[t * a.out_st + j * a.out_sp + c] = x[c];
             }
         }
         if (!a.every) {
 #pragma unroll
-            for (int c = 0; c < D; ++c) a.out[j * a.out_sp + c] = x[c];
+            for (int c = 0; c < Sys::N; ++c) a.out[j * a.out_sp + c] = x[c];
         }
     }
     if (a.has_obs) {        // wave-uniform: the whole workgroup takes it
@@ -356,48 +249,6 @@ __global__ __launch_bounds__(CH_THREADS) void chain_advance_small_kernel(ChainAd
     }
 }
 
-// Lorenz-96 on lanes: the lanes that hold components c - 1, c + 1, c + 2 and c - 2 (modulo n) of this lane's particle
-struct L96Lanes { int m1, p1, p2, m2; };
-struct L96Near { float m1, p1, p2; };       // a stage point's values at c - 1, c + 1, c + 2
-__device__ __forceinline__ L96Lanes l96_lanes(int base, int c, int n) {
-    return {base + (c + n - 1) % n, base + (c + 1) % n, base + (c + 2) % n, base + (c + n - 2) % n};
-}
-__device__ __forceinline__ L96Near l96_near(float v, const L96Lanes& l) {
-    return {__shfl(v, l.m1, SDA_WAVE), __shfl(v, l.p1, SDA_WAVE), __shfl(v, l.p2, SDA_WAVE)};
-}
-__device__ __forceinline__ float l96_f_lanes(float v, const L96Lanes& l, float F) {
-    const L96Near a = l96_near(v, l);
-    return lorenz96_f(a.m1, a.p2, a.p1, v, F);
-}
-// one RK4 sub-step of this lane's component; every lane of the wave calls it
-__device__ __forceinline__ float l96_substep_lanes(float x, const L96Lanes& l, float h, float F) {
-    const float k1 = l96_f_lanes(x, l, F);
-    const float k2 = l96_f_lanes(rk4_half(x, h, k1), l, F);
-    const float k3 = l96_f_lanes(rk4_half(x, h, k2), l, F);
-    const float k4 = l96_f_lanes(rk4_full(x, h, k3), l, F);
-    return rk4_comb(x, h, k1, k2, k3, k4);
-}
-// (J_f(v)^T gk)_c: the stage point's three forward shuffles are reused, v_{c-2} and three of gk are the four new ones
-__device__ __forceinline__ float l96_jt_lanes(float v, const L96Near& a, float gk, const L96Lanes& l) {
-    return lorenz96_jt(__shfl(gk, l.p1, SDA_WAVE), a.p2, __shfl(gk, l.m2, SDA_WAVE), a.m1, __shfl(gk, l.m1, SDA_WAVE),
-                       __shfl(v, l.m2, SDA_WAVE), a.p1, gk);
-}
-// g <- (d sub-step / dx at x)^T g, this lane's component; every lane of the wave calls it
-__device__ __forceinline__ float l96_substep_vjp_lanes(float x, float g, const L96Lanes& l, float h, float F) {
-    const L96Near a1 = l96_near(x, l);
-    const float v2 = rk4_half(x, h, lorenz96_f(a1.m1, a1.p2, a1.p1, x, F));
-    const L96Near a2 = l96_near(v2, l);
-    const float v3 = rk4_half(x, h, lorenz96_f(a2.m1, a2.p2, a2.p1, v2, F));
-    const L96Near a3 = l96_near(v3, l);
-    const float v4 = rk4_full(x, h, lorenz96_f(a3.m1, a3.p2, a3.p1, v3, F));
-    const L96Near a4 = l96_near(v4, l);
-    const float j4 = l96_jt_lanes(v4, a4, rk4r_k4(h, g), l);
-    const float j3 = l96_jt_lanes(v3, a3, rk4r_k3(h, g, j4), l);
-    const float j2 = l96_jt_lanes(v2, a2, rk4r_k2(h, g, j3), l);
-    const float j1 = l96_jt_lanes(x, a1, rk4r_k1(h, g, j2), l);
-    return rk4r_x(g, j1, j2, j3, j4);
-}
-
 // Lorenz-96: component c of a particle on lane (group base + c) of a sub-group of W lanes, W = next power of two >= n
 __global__ __launch_bounds__(CH_THREADS) void chain_advance_l96_kernel(ChainAdvArgs a, int W) {
     const int n = a.model.d;
@@ -406,9 +257,7 @@ __global__ __launch_bounds__(CH_THREADS) void chain_advance_l96_kernel(ChainAdvA
     const int64_t j = (int64_t)blockIdx.x * per_block + threadIdx.x / W;
     const bool live = j < a.m && sub < n;
     const int c = sub < n ? sub : 0;
-    // roll(x, 1)[c] = x[c - 1], roll(x, -1)[c] = x[c + 1], roll(x, -2)[c] = x[c + 2], indices modulo n
-    const L96Lanes l = l96_lanes(base, c, n);
-    const float h = a.model.h, F = a.model.p[0];
+    const L96LaneSys sys{l96_lanes(base, c, n), a.model.p[0]};
     float x = 0.f;
     if (live) {
         const int64_t src = a.anc ? clamp_slot(a.anc[j], a.m) : j;
@@ -416,7 +265,7 @@ __global__ __launch_bounds__(CH_THREADS) void chain_advance_l96_kernel(ChainAdvA
     }
     // every lane of the wave runs the shuffles (dead lanes carry zeros); only the stores are predicated
     for (int t = 0; t < a.transitions; ++t) {
-        for (int s = 0; s < a.model.steps; ++s) x = l96_substep_lanes(x, l, h, F);
+        rk4_transition(sys, a.model.h, a.model.steps, &x);
         if (a.model.noise_std > 0.f && live) {
             float z[4];
             chain_noise4(a.seed, (uint64_t)(a.row0 + j), a.draw0 + t, c >> 2, z);
@@ -441,18 +290,13 @@ extern "C" int sda_chain_advance(const sda_chain_adv* a, void* stream) {
     if (a->obs) obs = *a->obs;
     const hipStream_t st = (hipStream_t)stream;
     if (a->model.kind == SDA_CHAIN_LORENZ96) {
-        int W = 4;
-        while (W < a->model.d) W <<= 1;
-        const int per_block = CH_THREADS / W;
-        const int64_t blocks = ((int64_t)a->m + per_block - 1) / per_block;
-        if (blocks > 0x7fffffff) return SDA_E_UNSUPPORTED;
-        hipLaunchKernelGGL(chain_advance_l96_kernel, dim3((unsigned)blocks), dim3(CH_THREADS), 0, st, k, W);
+        int W;
+        unsigned blocks;
+        rc = chain_l96_geometry(a->model.d, a->m, &W, &blocks);
+        if (rc != SDA_OK) return rc;
+        hipLaunchKernelGGL(chain_advance_l96_kernel, dim3(blocks), dim3(CH_THREADS), 0, st, k, W);
     } else {
-        const unsigned blocks = (unsigned)((a->m + CH_THREADS - 1) / CH_THREADS);
-        if (a->model.kind == SDA_CHAIN_LORENZ63)
-            hipLaunchKernelGGL(chain_advance_small_kernel<SDA_CHAIN_LORENZ63>, dim3(blocks), dim3(CH_THREADS), 0, st, k, obs);
-        else
-            hipLaunchKernelGGL(chain_advance_small_kernel<SDA_CHAIN_LOTKA_VOLTERRA>, dim3(blocks), dim3(CH_THREADS), 0, st, k, obs);
+        CHAIN_LAUNCH_SMALL(a->model.kind, chain_advance_small_kernel, a->m, CH_THREADS, st, k, obs);
     }
     return sda_launch_status();
 }
@@ -471,25 +315,25 @@ struct ChainVjpArgs {       // sda_chain_vjp without anc
 
 template <int KIND>
 __global__ __launch_bounds__(CH_THREADS) void chain_advance_vjp_small_kernel(ChainVjpArgs a) {
-    constexpr int D = KIND == SDA_CHAIN_LORENZ63 ? 3 : 2;
+    using Sys = typename ChainSmall<KIND>::Sys;
     const int j = blockIdx.x * CH_THREADS + threadIdx.x;
     if (j >= a.m) return;
     const int T = a.transitions;
-    float g[D], x0[D];
+    float g[Sys::N], x0[Sys::N];
 #pragma unroll
-    for (int c = 0; c < D; ++c) g[c] = a.g[(a.every ? (T - 1) * a.g_st : 0) + j * a.g_sp + c];
+    for (int c = 0; c < Sys::N; ++c) g[c] = a.g[(a.every ? (T - 1) * a.g_st : 0) + j * a.g_sp + c];
     for (int t = T - 1; t >= 0; --t) {
         const float* xs = t ? a.states + (t - 1) * a.st_st + j * a.st_sp : a.x_in + j * a.in_sp;
 #pragma unroll
-        for (int c = 0; c < D; ++c) x0[c] = xs[c];
-        chain_small_transition_vjp<KIND>(a.model, x0, g);
+        for (int c = 0; c < Sys::N; ++c) x0[c] = xs[c];
+        rk4_transition_vjp(Sys{a.model.p}, a.model.h, a.model.steps, x0, g);
         if (a.every && t) {
 #pragma unroll
-            for (int c = 0; c < D; ++c) g[c] = a.g[(t - 1) * a.g_st + j * a.g_sp + c] + g[c];
+            for (int c = 0; c < Sys::N; ++c) g[c] = a.g[(t - 1) * a.g_st + j * a.g_sp + c] + g[c];
         }
     }
 #pragma unroll
-    for (int c = 0; c < D; ++c) a.gx[j * a.gx_sp + c] = g[c];
+    for (int c = 0; c < Sys::N; ++c) a.gx[j * a.gx_sp + c] = g[c];
 }
 
 __global__ __launch_bounds__(CH_THREADS) void chain_advance_vjp_l96_kernel(ChainVjpArgs a, int W) {
@@ -499,8 +343,7 @@ __global__ __launch_bounds__(CH_THREADS) void chain_advance_vjp_l96_kernel(Chain
     const int64_t j = (int64_t)blockIdx.x * per_block + threadIdx.x / W;
     const bool live = j < a.m && sub < n;
     const int c = sub < n ? sub : 0;
-    const L96Lanes l = l96_lanes(base, c, n);
-    const float h = a.model.h, F = a.model.p[0];
+    const L96LaneSys sys{l96_lanes(base, c, n), a.model.p[0]};
     const int T = a.transitions;
     float g = 0.f;
     if (live) g = a.g[(a.every ? (T - 1) * a.g_st : 0) + j * a.g_sp + c];
@@ -508,11 +351,7 @@ __global__ __launch_bounds__(CH_THREADS) void chain_advance_vjp_l96_kernel(Chain
     for (int t = T - 1; t >= 0; --t) {
         float x0 = 0.f;
         if (live) x0 = t ? a.states[(t - 1) * a.st_st + j * a.st_sp + c] : a.x_in[j * a.in_sp + c];
-        for (int s = a.model.steps - 1; s >= 0; --s) {
-            float x = x0;
-            for (int q = 0; q < s; ++q) x = l96_substep_lanes(x, l, h, F);
-            g = l96_substep_vjp_lanes(x, g, l, h, F);
-        }
+        rk4_transition_vjp(sys, a.model.h, a.model.steps, &x0, &g);
         if (a.every && t && live) g = a.g[(t - 1) * a.g_st + j * a.g_sp + c] + g;
     }
     if (live) a.gx[j * a.gx_sp + c] = g;
@@ -530,18 +369,13 @@ extern "C" int sda_chain_advance_vjp(const sda_chain_vjp* a, void* stream) {
     k.every = a->every ? 1 : 0; k.m = a->m; k.transitions = a->transitions;
     const hipStream_t st = (hipStream_t)stream;
     if (a->model.kind == SDA_CHAIN_LORENZ96) {
-        int W = 4;
-        while (W < a->model.d) W <<= 1;
-        const int per_block = CH_THREADS / W;
-        const int64_t blocks = ((int64_t)a->m + per_block - 1) / per_block;
-        if (blocks > 0x7fffffff) return SDA_E_UNSUPPORTED;
-        hipLaunchKernelGGL(chain_advance_vjp_l96_kernel, dim3((unsigned)blocks), dim3(CH_THREADS), 0, st, k, W);
+        int W;
+        unsigned blocks;
+        rc = chain_l96_geometry(a->model.d, a->m, &W, &blocks);
+        if (rc != SDA_OK) return rc;
+        hipLaunchKernelGGL(chain_advance_vjp_l96_kernel, dim3(blocks), dim3(CH_THREADS), 0, st, k, W);
     } else {
-        const unsigned blocks = (unsigned)((a->m + CH_THREADS - 1) / CH_THREADS);
-        if (a->model.kind == SDA_CHAIN_LORENZ63)
-            hipLaunchKernelGGL(chain_advance_vjp_small_kernel<SDA_CHAIN_LORENZ63>, dim3(blocks), dim3(CH_THREADS), 0, st, k);
-        else
-            hipLaunchKernelGGL(chain_advance_vjp_small_kernel<SDA_CHAIN_LOTKA_VOLTERRA>, dim3(blocks), dim3(CH_THREADS), 0, st, k);
+        CHAIN_LAUNCH_SMALL(a->model.kind, chain_advance_vjp_small_kernel, a->m, CH_THREADS, st, k);
     }
     return sda_launch_status();
 }
@@ -553,51 +387,45 @@ template <int KIND>
 __global__ __launch_bounds__(CH_THREADS) void chain_log_prob_grad_kernel(sda_chain_model model, const float* __restrict__ x, int b,
                                                                          int len, int64_t sb, int64_t sl, double* __restrict__ out,
                                                                          float* __restrict__ grad) {
-    constexpr int D = KIND == SDA_CHAIN_LORENZ63 ? 3 : 2;
+    using Sys = typename ChainSmall<KIND>::Sys;
     const int lane = threadIdx.x & 63;
     const int traj = blockIdx.x * (CH_THREADS / SDA_WAVE) + (threadIdx.x >> 6);
-    const bool have = traj < b;                 // the same in every lane of the wave
+    const bool have = traj < b;                // the same in every lane of the wave
     const float* xt = x + traj * sb;
-    float* gt = grad + (int64_t)traj * len * D;
+    float* gt = grad + (int64_t)traj * len * Sys::N;
     double acc = 0.0;
-    float carry[D];
+    float carry[Sys::N];
 #pragma unroll
-    for (int c = 0; c < D; ++c) carry[c] = 0.f;
+    for (int c = 0; c < Sys::N; ++c) carry[c] = 0.f;
     for (int i0 = 0; i0 < len; i0 += SDA_WAVE) {        // every lane takes every trip: the shuffles below need the whole wave
         const int i = i0 + lane;
-        float r[D], jtr[D];
+        float r[Sys::N], jtr[Sys::N];
 #pragma unroll
-        for (int c = 0; c < D; ++c) { r[c] = 0.f; jtr[c] = 0.f; }
+        for (int c = 0; c < Sys::N; ++c) { r[c] = 0.f; jtr[c] = 0.f; }
         if (have && i + 1 < len) {
-            float p[D], q[D];
+            float p[Sys::N], q[Sys::N];
 #pragma unroll
-            for (int c = 0; c < D; ++c) { p[c] = xt[i * sl + c]; q[c] = xt[(i + 1) * sl + c]; }
+            for (int c = 0; c < Sys::N; ++c) { p[c] = xt[i * sl + c]; q[c] = xt[(i + 1) * sl + c]; }
             acc += chain_pair_residual<KIND>(model, p, q, r, jtr);
         }
 #pragma unroll
-        for (int c = 0; c < D; ++c) {
+        for (int c = 0; c < Sys::N; ++c) {
             const float below = __shfl_up(r[c], 1, SDA_WAVE);
             const float prev = lane ? below : carry[c];
             carry[c] = __shfl(r[c], SDA_WAVE - 1, SDA_WAVE);
-            if (have && i < len) gt[(int64_t)i * D + c] = jtr[c] - prev;
+            if (have && i < len) gt[(int64_t)i * Sys::N + c] = jtr[c] - prev;
         }
     }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off, SDA_WAVE);
+    acc = sda_wave_sum(acc);
     if (lane == 0 && have) out[traj] = acc;
 }
 
 extern "C" int sda_chain_log_prob_grad(const sda_chain_model* model, const float* x, int b, int len, int64_t sb, int64_t sl,
                                        double* out, float* grad, void* stream) {
-    int rc = chain_lpg_check(model, x, b, len, sb, sl, out, grad);
+    int rc = chain_lpg_check(model, x, b, len, sl, out, grad);
     if (rc != SDA_OK) return rc;
-    const unsigned blocks = (unsigned)((b + CH_THREADS / SDA_WAVE - 1) / (CH_THREADS / SDA_WAVE));
-    if (model->kind == SDA_CHAIN_LORENZ63)
-        hipLaunchKernelGGL(chain_log_prob_grad_kernel<SDA_CHAIN_LORENZ63>, dim3(blocks), dim3(CH_THREADS), 0, (hipStream_t)stream,
-                           *model, x, b, len, sb, sl, out, grad);
-    else
-        hipLaunchKernelGGL(chain_log_prob_grad_kernel<SDA_CHAIN_LOTKA_VOLTERRA>, dim3(blocks), dim3(CH_THREADS), 0,
-                           (hipStream_t)stream, *model, x, b, len, sb, sl, out, grad);
+    CHAIN_LAUNCH_SMALL(model->kind, chain_log_prob_grad_kernel, b, CH_THREADS / SDA_WAVE, (hipStream_t)stream, *model, x, b, len, sb, sl,
+                       out, grad);
     return sda_launch_status();
 }
 
@@ -605,37 +433,28 @@ extern "C" int sda_chain_log_prob_grad(const sda_chain_model* model, const float
 template <int KIND>
 __global__ __launch_bounds__(CH_THREADS) void chain_log_prob_kernel(sda_chain_model model, const float* __restrict__ x, int b, int len,
                                                                     int64_t sb, int64_t sl, double* __restrict__ out) {
-    constexpr int D = KIND == SDA_CHAIN_LORENZ63 ? 3 : 2;
+    using Sys = typename ChainSmall<KIND>::Sys;
     const int lane = threadIdx.x & 63;
     const int traj = blockIdx.x * (CH_THREADS / SDA_WAVE) + (threadIdx.x >> 6);
     double acc = 0.0;
     if (traj < b) {
         const float* xt = x + traj * sb;
         for (int i = lane; i + 1 < len; i += SDA_WAVE) {
-            float a[D], n[D];
+            float a[Sys::N], n[Sys::N];
 #pragma unroll
-            for (int c = 0; c < D; ++c) { a[c] = xt[i * sl + c]; n[c] = xt[(i + 1) * sl + c]; }
+            for (int c = 0; c < Sys::N; ++c) { a[c] = xt[i * sl + c]; n[c] = xt[(i + 1) * sl + c]; }
             acc += chain_pair_log_prob<KIND>(model, a, n);
         }
     }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off, SDA_WAVE);
+    acc = sda_wave_sum(acc);
     if (lane == 0 && traj < b) out[traj] = acc;
 }
 
 extern "C" int sda_chain_log_prob(const sda_chain_model* model, const float* x, int b, int len, int64_t sb, int64_t sl, double* out,
                                   void* stream) {
-    int rc = chain_model_check(model);
+    int rc = chain_lp_check(model, x, b, len, sl, out);
     if (rc != SDA_OK) return rc;
-    if (model->kind == SDA_CHAIN_LORENZ96) return SDA_E_UNSUPPORTED;
-    if (!x || !out || b < 1 || len < 2 || sl < model->d || !(model->noise_std > 0.f)) return SDA_E_BADARG;
-    const unsigned blocks = (unsigned)((b + CH_THREADS / SDA_WAVE - 1) / (CH_THREADS / SDA_WAVE));
-    if (model->kind == SDA_CHAIN_LORENZ63)
-        hipLaunchKernelGGL(chain_log_prob_kernel<SDA_CHAIN_LORENZ63>, dim3(blocks), dim3(CH_THREADS), 0, (hipStream_t)stream, *model, x,
-                           b, len, sb, sl, out);
-    else
-        hipLaunchKernelGGL(chain_log_prob_kernel<SDA_CHAIN_LOTKA_VOLTERRA>, dim3(blocks), dim3(CH_THREADS), 0, (hipStream_t)stream,
-                           *model, x, b, len, sb, sl, out);
+    CHAIN_LAUNCH_SMALL(model->kind, chain_log_prob_kernel, b, CH_THREADS / SDA_WAVE, (hipStream_t)stream, *model, x, b, len, sb, sl, out);
     return sda_launch_status();
 }
 
@@ -679,11 +498,9 @@ __global__ __launch_bounds__(CDF_THREADS) void bpf_cdf_kernel(const float* __res
     }
     if (pmax)
         for (int i = tid; i < npmax; i += CDF_THREADS) mx = fmaxf(mx, pmax[i]);
+    mx = sda_wave_max(mx);
 #pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        mx = fmaxf(mx, __shfl_down(mx, off, SDA_WAVE));
-        bad |= __shfl_down(bad, off, SDA_WAVE);
-    }
+    for (int off = 32; off > 0; off >>= 1) bad |= __shfl_down(bad, off, SDA_WAVE);
     if (lane == 0) { s_max[wave] = mx; s_bad[wave] = bad; }
     __syncthreads();
     mx = s_max[0]; bad = s_bad[0];
@@ -760,26 +577,9 @@ extern "C" int sda_bpf_traceback(const float* S, int64_t s_st, int64_t s_sp, con
 
 #else  // SDA_HOST_EMU
 // ---------------------------------------------------------------- CPU replay (tests only; libsda_emu.so): the same
-// __host__ __device__ functions as plain loops over HOST arrays.  Lorenz-96 keeps a particle in one array where the device
-// keeps it on the lanes of a sub-group: the rolls index modulo n where the device shuffles.
-static void l96_f_host(const float* x, int n, float F, float* f) {
-    for (int c = 0; c < n; ++c) f[c] = lorenz96_f(x[(c + n - 1) % n], x[(c + 2) % n], x[(c + 1) % n], x[c], F);
-}
-
-static void l96_transition_host(const sda_chain_model& m, float* x) {
-    const int n = m.d;
-    float k1[64], k2[64], k3[64], k4[64], v[64];
-    for (int s = 0; s < m.steps; ++s) {
-        l96_f_host(x, n, m.p[0], k1);
-        for (int c = 0; c < n; ++c) v[c] = rk4_half(x[c], m.h, k1[c]);
-        l96_f_host(v, n, m.p[0], k2);
-        for (int c = 0; c < n; ++c) v[c] = rk4_half(x[c], m.h, k2[c]);
-        l96_f_host(v, n, m.p[0], k3);
-        for (int c = 0; c < n; ++c) v[c] = rk4_full(x[c], m.h, k3[c]);
-        l96_f_host(v, n, m.p[0], k4);
-        for (int c = 0; c < n; ++c) x[c] = rk4_comb(x[c], m.h, k1[c], k2[c], k3[c], k4[c]);
-    }
-}
+// __host__ __device__ functions and the same RK4 templates inside plain loops over HOST arrays.  Lorenz-96 keeps a particle in
+// one array (L96ArraySys) where the device keeps it on the lanes of a sub-group (L96LaneSys): the stage sequence is the one
+// template, the neighbours are the one l96_lanes, only "index the array" stands where the device shuffles.
 
 extern "C" int sda_chain_advance_host(const sda_chain_adv* a) {
     int rc = chain_adv_check(a);
@@ -791,9 +591,9 @@ extern "C" int sda_chain_advance_host(const sda_chain_adv* a) {
         float x[64];
         for (int c = 0; c < d; ++c) x[c] = a->x_in[src * a->in_sp + c];
         for (int t = 0; t < a->transitions; ++t) {
-            if (md.kind == SDA_CHAIN_LORENZ63) chain_small_transition<SDA_CHAIN_LORENZ63>(md, x);
-            else if (md.kind == SDA_CHAIN_LOTKA_VOLTERRA) chain_small_transition<SDA_CHAIN_LOTKA_VOLTERRA>(md, x);
-            else l96_transition_host(md, x);
+            if (md.kind == SDA_CHAIN_LORENZ63) rk4_transition(Lorenz63Sys{md.p}, md.h, md.steps, x);
+            else if (md.kind == SDA_CHAIN_LOTKA_VOLTERRA) rk4_transition(LotkaVolterraSys{md.p}, md.h, md.steps, x);
+            else rk4_transition(L96ArraySys{d, md.p[0]}, md.h, md.steps, x);
             if (md.noise_std > 0.f)
                 for (int q = 0; 4 * q < d; ++q) {
                     float z[4];
@@ -810,49 +610,6 @@ extern "C" int sda_chain_advance_host(const sda_chain_adv* a) {
     return SDA_OK;
 }
 
-static void l96_substep_host(const sda_chain_model& m, float* x) {
-    sda_chain_model one = m;
-    one.steps = 1;
-    l96_transition_host(one, x);
-}
-
-static void l96_jt_host(const float* v, const float* g, int n, float* o) {
-    for (int j = 0; j < n; ++j)
-        o[j] = lorenz96_jt(g[(j + 1) % n], v[(j + 2) % n], g[(j + n - 2) % n], v[(j + n - 1) % n], g[(j + n - 1) % n],
-                           v[(j + n - 2) % n], v[(j + 1) % n], g[j]);
-}
-
-// the array form of l96_substep_vjp_lanes
-static void l96_substep_vjp_host(const sda_chain_model& m, const float* x, float* g) {
-    const int n = m.d;
-    const float h = m.h, F = m.p[0];
-    float k[64], v2[64], v3[64], v4[64], gk[64], j1[64], j2[64], j3[64], j4[64];
-    l96_f_host(x, n, F, k);
-    for (int c = 0; c < n; ++c) v2[c] = rk4_half(x[c], h, k[c]);
-    l96_f_host(v2, n, F, k);
-    for (int c = 0; c < n; ++c) v3[c] = rk4_half(x[c], h, k[c]);
-    l96_f_host(v3, n, F, k);
-    for (int c = 0; c < n; ++c) v4[c] = rk4_full(x[c], h, k[c]);
-    for (int c = 0; c < n; ++c) gk[c] = rk4r_k4(h, g[c]);
-    l96_jt_host(v4, gk, n, j4);
-    for (int c = 0; c < n; ++c) gk[c] = rk4r_k3(h, g[c], j4[c]);
-    l96_jt_host(v3, gk, n, j3);
-    for (int c = 0; c < n; ++c) gk[c] = rk4r_k2(h, g[c], j3[c]);
-    l96_jt_host(v2, gk, n, j2);
-    for (int c = 0; c < n; ++c) gk[c] = rk4r_k1(h, g[c], j2[c]);
-    l96_jt_host(x, gk, n, j1);
-    for (int c = 0; c < n; ++c) g[c] = rk4r_x(g[c], j1[c], j2[c], j3[c], j4[c]);
-}
-
-static void l96_transition_vjp_host(const sda_chain_model& m, const float* x0, float* g) {
-    for (int s = m.steps - 1; s >= 0; --s) {
-        float x[64];
-        for (int c = 0; c < m.d; ++c) x[c] = x0[c];
-        for (int q = 0; q < s; ++q) l96_substep_host(m, x);
-        l96_substep_vjp_host(m, x, g);
-    }
-}
-
 extern "C" int sda_chain_advance_vjp_host(const sda_chain_vjp* a) {
     int rc = chain_vjp_check(a);
     if (rc != SDA_OK) return rc;
@@ -864,9 +621,9 @@ extern "C" int sda_chain_advance_vjp_host(const sda_chain_vjp* a) {
         for (int t = T - 1; t >= 0; --t) {
             const float* xs = t ? a->states + (t - 1) * a->st_st + j * a->st_sp : a->x_in + j * a->in_sp;
             for (int c = 0; c < d; ++c) x0[c] = xs[c];
-            if (md.kind == SDA_CHAIN_LORENZ63) chain_small_transition_vjp<SDA_CHAIN_LORENZ63>(md, x0, g);
-            else if (md.kind == SDA_CHAIN_LOTKA_VOLTERRA) chain_small_transition_vjp<SDA_CHAIN_LOTKA_VOLTERRA>(md, x0, g);
-            else l96_transition_vjp_host(md, x0, g);
+            if (md.kind == SDA_CHAIN_LORENZ63) rk4_transition_vjp(Lorenz63Sys{md.p}, md.h, md.steps, x0, g);
+            else if (md.kind == SDA_CHAIN_LOTKA_VOLTERRA) rk4_transition_vjp(LotkaVolterraSys{md.p}, md.h, md.steps, x0, g);
+            else rk4_transition_vjp(L96ArraySys{d, md.p[0]}, md.h, md.steps, x0, g);
             if (a->every && t)
                 for (int c = 0; c < d; ++c) g[c] = a->g[(t - 1) * a->g_st + j * a->g_sp + c] + g[c];
         }
@@ -877,7 +634,7 @@ extern "C" int sda_chain_advance_vjp_host(const sda_chain_vjp* a) {
 
 extern "C" int sda_chain_log_prob_grad_host(const sda_chain_model* model, const float* x, int b, int len, int64_t sb, int64_t sl,
                                             double* out, float* grad) {
-    int rc = chain_lpg_check(model, x, b, len, sb, sl, out, grad);
+    int rc = chain_lpg_check(model, x, b, len, sl, out, grad);
     if (rc != SDA_OK) return rc;
     const int d = model->d;
     for (int t = 0; t < b; ++t) {
@@ -901,10 +658,8 @@ extern "C" int sda_chain_log_prob_grad_host(const sda_chain_model* model, const 
 
 extern "C" int sda_chain_log_prob_host(const sda_chain_model* model, const float* x, int b, int len, int64_t sb, int64_t sl,
                                        double* out) {
-    int rc = chain_model_check(model);
+    int rc = chain_lp_check(model, x, b, len, sl, out);
     if (rc != SDA_OK) return rc;
-    if (model->kind == SDA_CHAIN_LORENZ96) return SDA_E_UNSUPPORTED;
-    if (!x || !out || b < 1 || len < 2 || sl < model->d || !(model->noise_std > 0.f)) return SDA_E_BADARG;
     for (int t = 0; t < b; ++t) {
         double acc = 0.0;
         for (int i = 0; i + 1 < len; ++i) {

@@ -12,6 +12,7 @@
 //
 // Under SDA_HOST_EMU the same arithmetic runs as plain loops over host arrays (bottom of the file; libsda_emu.so).
 #include "sda_common.hpp"
+#include "chain_check.hpp"
 #include "philox.hpp"
 
 #define ENKS_SALT 0x454E4B53ull     // 'ENKS': keeps the perturbations off the chain's own transition noise under the same seed
@@ -28,23 +29,14 @@ __host__ __device__ __forceinline__ float enks_observe(float x, float shift, flo
 // elements 4q .. 4q+3 of row j in draw `draw` of the sda_randn_rows stream under the salted seed
 __host__ __device__ __forceinline__ void enks_noise4(uint64_t seed, uint64_t j, int64_t draw, int64_t q, float* e) {
     const uint64_t s = seed ^ ENKS_SALT;
-    const philox4 w = philox_noise_words(q, j, draw, (uint32_t)s, (uint32_t)(s >> 32));
-    box_muller(w.v[0], w.v[1], e[0], e[1]);
-    box_muller(w.v[2], w.v[3], e[2], e[3]);
-}
-
-static int enks_obs_check(const sda_chain_obs* o, int d) {
-    if (!o || !o->y || o->k < 1 || o->k > d || o->k > SDA_CHAIN_MAXOBS || !(o->sigma > 0.f)) return SDA_E_BADARG;
-    for (int r = 0; r < o->k; ++r)
-        if (o->idx[r] < 0 || o->idx[r] >= d || o->scale[r] == 0.f) return SDA_E_BADARG;
-    return SDA_OK;
+    philox_normal4(q, j, draw, (uint32_t)s, (uint32_t)(s >> 32), e);
 }
 
 static int enks_gain_check(const float* x, int m, int64_t sp, int d, const sda_chain_obs* obs, float inflation, int64_t draw,
                            const float* a, const float* z, const float* work, const int32_t* status) {
     if (!x || !a || !z || !work || !status || m < 2 || d < 1 || sp < d || draw < 0 || !(inflation > 0.f)) return SDA_E_BADARG;
     if (d > ENKS_MAX_D || m > ENKS_MAX_M) return SDA_E_UNSUPPORTED;
-    return enks_obs_check(obs, d);
+    return chain_obs_check(obs, d);
 }
 
 static int enks_update_check(const float* S, int64_t s_st, int64_t s_sp, int nslab, int m, int d, int k, float inflation,
@@ -57,12 +49,6 @@ static int enks_update_check(const float* S, int64_t s_st, int64_t s_sp, int nsl
 
 #ifndef SDA_HOST_EMU
 // ---------------------------------------------------------------- device kernels
-__device__ __forceinline__ double enks_wave_sum(double v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, SDA_WAVE);
-    return v;
-}
-
 // ONE workgroup.  LDS (dynamic): C[k][k], L[k][k] doubles, xm[k], hb[k] doubles, one flag.
 __global__ __launch_bounds__(ENKS_GAIN_THREADS) void enks_gain_kernel(const float* __restrict__ x, int m, int64_t sp, sda_chain_obs obs,
                                                                       float lam, uint64_t seed, int64_t draw, float* __restrict__ a,
@@ -86,7 +72,7 @@ __global__ __launch_bounds__(ENKS_GAIN_THREADS) void enks_gain_kernel(const floa
         if (lam != 1.0f) {
             double s = 0.0;
             for (int j = lane; j < m; j += SDA_WAVE) s += (double)x[(int64_t)j * sp + c];
-            s = enks_wave_sum(s);
+            s = sda_wave_sum(s);
             mean = (float)(__shfl(s, 0, SDA_WAVE) / (double)m);
         }
         double s = 0.0;
@@ -97,7 +83,7 @@ __global__ __launch_bounds__(ENKS_GAIN_THREADS) void enks_gain_kernel(const floa
             work[(int64_t)r * m + j] = h;
             s += (double)h;
         }
-        s = enks_wave_sum(s);
+        s = sda_wave_sum(s);
         const double hbar = __shfl(s, 0, SDA_WAVE) / (double)m;
         for (int j = lane; j < m; j += SDA_WAVE) a[(int64_t)r * m + j] = (float)((double)work[(int64_t)r * m + j] - hbar);
     }
@@ -110,7 +96,7 @@ __global__ __launch_bounds__(ENKS_GAIN_THREADS) void enks_gain_kernel(const floa
             if (p % NW != wave) continue;
             double s = 0.0;
             for (int j = lane; j < m; j += SDA_WAVE) s += (double)a[(int64_t)r * m + j] * (double)a[(int64_t)c * m + j];
-            s = enks_wave_sum(s);
+            s = sda_wave_sum(s);
             if (lane == 0) {
                 const double v = s / (double)(m - 1) + (r == c ? s2 : 0.0);
                 C[r * k + c] = v;

@@ -22,15 +22,9 @@
 
 // the d normals of global row `grow` in draw `draw`: what sda_randn_rows writes to that row of an [rows][d] tensor
 __host__ __device__ __forceinline__ void lgss_noise(uint64_t seed, uint64_t grow, int64_t draw, int d, float* z) {
-    philox4 w = philox_noise_words(0, grow, draw, (uint32_t)seed, (uint32_t)(seed >> 32));
-    box_muller(w.v[0], w.v[1], z[0], z[1]);
-    box_muller(w.v[2], w.v[3], z[2], z[3]);
+    philox_normal4(0, grow, draw, (uint32_t)seed, (uint32_t)(seed >> 32), z);
     z[4] = z[5] = z[6] = z[7] = 0.f;
-    if (d > 4) {
-        w = philox_noise_words(1, grow, draw, (uint32_t)seed, (uint32_t)(seed >> 32));
-        box_muller(w.v[0], w.v[1], z[4], z[5]);
-        box_muller(w.v[2], w.v[3], z[6], z[7]);
-    }
+    if (d > 4) philox_normal4(1, grow, draw, (uint32_t)seed, (uint32_t)(seed >> 32), z + 4);
 }
 
 // ---------------------------------------------------------------- simulator (fp32)

@@ -7,9 +7,9 @@
 // one 16-byte store per lane and Philox call; no reads.
 #include "sda_common.hpp"
 
-#include "philox.hpp"      // philox4x32_10, box_muller (shared with chain.hip)
+#include "philox.hpp"      // philox_normal4: the one quad every keyed-noise kernel shares
 
-// out: [rows][per_row]; quad q of a row (elements 4q .. 4q+3) comes from counter {q_lo, row, draw_lo, draw_hi ^ q_hi << 16}
+// out: [rows][per_row]; quad q of a row (elements 4q .. 4q+3) is philox_normal4(q, row0 + row, draw) (philox.hpp: the counter)
 __global__ __launch_bounds__(256) void randn_rows_kernel(float* __restrict__ out, int rows, int64_t per_row, uint32_t k0,
                                                          uint32_t k1, int64_t row0, int64_t draw, const int64_t* draw_dev,
                                                          int64_t mul, int64_t add) {
@@ -19,14 +19,8 @@ __global__ __launch_bounds__(256) void randn_rows_kernel(float* __restrict__ out
     const bool vec = (per_row & 3) == 0 && ((reinterpret_cast<uintptr_t>(out) & 15) == 0);
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
         const int64_t r = i / quads, q = i - r * quads;
-        const uint64_t grow = (uint64_t)(row0 + r);
-        const philox4 x = philox4x32_10((uint32_t)q, (uint32_t)grow, (uint32_t)draw,
-                                        (uint32_t)((uint64_t)draw >> 32) ^ ((uint32_t)((uint64_t)q >> 32) << 16) ^
-                                            ((uint32_t)(grow >> 32) << 24),
-                                        k0, k1);
         float z[4];
-        box_muller(x.v[0], x.v[1], z[0], z[1]);
-        box_muller(x.v[2], x.v[3], z[2], z[3]);
+        philox_normal4(q, (uint64_t)(row0 + r), draw, k0, k1, z);
         float* dst = out + r * per_row + 4 * q;
         if (vec) {
             *reinterpret_cast<float4*>(dst) = make_float4(z[0], z[1], z[2], z[3]);

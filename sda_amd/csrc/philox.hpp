@@ -1,5 +1,8 @@
-// Counter-based Philox4x32-10 (Salmon et al., SC'11; the generator behind torch's device RNG) + Box-Muller, shared by the
-// row-keyed corrector noise (noise.hip) and the Markov-chain / particle-filter kernels (chain.hip).
+// Counter-based Philox4x32-10 (Salmon et al., SC'11; the generator behind torch's device RNG) + Box-Muller, shared by every keyed
+// draw of the library: the row-keyed normals (noise.hip) and the kernels that regenerate them in place -- the keyed corrector
+// (step1d.hip), the loss perturbation (train_loss.hip), the Markov chains and the particle filter (chain.hip), the linear-Gaussian
+// model (lgss.hip) and the ensemble smoother (enks.hip), all through philox_normal4 -- and the window starts and epoch shuffles of
+// the trajectory dataset (dataset.hip).
 //
 // Counter layouts in use (key = the 64-bit seed, low word first):
 //   noise    element 4q..4q+3 of row r in draw t :  {q_lo, r_lo, t_lo, t_hi ^ (q_hi << 16) ^ (r_hi << 24)}
@@ -49,6 +52,14 @@ __host__ __device__ __forceinline__ philox4 philox_noise_words(int64_t q, uint64
                          (uint32_t)((uint64_t)draw >> 32) ^ ((uint32_t)((uint64_t)q >> 32) << 16) ^
                              ((uint32_t)(grow >> 32) << 24),
                          k0, k1);
+}
+
+// THE four normals of quad q of global row `grow` in draw `draw`: what sda_randn_rows writes to elements 4q .. 4q+3 of that row.
+// Every keyed-noise kernel draws through this one function, so they all see the same stream.
+__host__ __device__ __forceinline__ void philox_normal4(int64_t q, uint64_t grow, int64_t draw, uint32_t k0, uint32_t k1, float* z) {
+    const philox4 w = philox_noise_words(q, grow, draw, k0, k1);
+    box_muller(w.v[0], w.v[1], z[0], z[1]);
+    box_muller(w.v[2], w.v[3], z[2], z[3]);
 }
 
 // word 0 behind the window start of row b in global batch s (the `window` counter)

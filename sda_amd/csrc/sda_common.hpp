@@ -127,9 +127,19 @@ __host__ __device__ __forceinline__ float sda_dot8(const float* w, const float* 
     return ((a[0] + a[1]) + (a[2] + a[3])) + ((a[4] + a[5]) + (a[6] + a[7]));
 }
 
-// 64-wide wavefront sum (CDNA wave = 64 lanes)
+// 64-wide wavefront sum / max (CDNA wave = 64 lanes): lane 0 holds the result; offsets 32, 16, .., 1, in that order
 __device__ __forceinline__ float sda_wave_sum(float v) {
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, SDA_WAVE);
+    return v;
+}
+__device__ __forceinline__ double sda_wave_sum(double v) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, SDA_WAVE);
+    return v;
+}
+__device__ __forceinline__ float sda_wave_max(float v) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v = fmaxf(v, __shfl_down(v, off, SDA_WAVE));
     return v;
 }

@@ -282,10 +282,8 @@ __global__ __launch_bounds__(256) void pc_correct_keyed_kernel(float* __restrict
     const int64_t quads = (per_sample + 3) >> 2;
     const uint64_t grow = (uint64_t)(row0 + b);
     for (int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x; q < quads; q += (int64_t)gridDim.x * 256) {
-        const philox4 w = philox_noise_words(q, grow, draw, k0, k1);
         float z[4];
-        box_muller(w.v[0], w.v[1], z[0], z[1]);
-        box_muller(w.v[2], w.v[3], z[2], z[3]);
+        philox_normal4(q, grow, draw, k0, k1, z);
         const int64_t left = per_sample - 4 * q;
 #pragma unroll
         for (int e = 0; e < 4; ++e)

@@ -46,10 +46,8 @@ __global__ __launch_bounds__(PB_THREADS) void loss_perturb_kernel(const float* _
     const float tv = ((float)(wt.v[0] >> 8) + 0.5f) * (1.0f / 16777216.0f);
     float mu, sg;
     sda_vp_mu_sigma(tv, alpha_kind, eta, k, sigma_kind, mu, sg);
-    const philox4 w = philox_noise_words(q, grow, draw, k0, k1);
     float z[4];
-    box_muller(w.v[0], w.v[1], z[0], z[1]);
-    box_muller(w.v[2], w.v[3], z[2], z[3]);
+    philox_normal4(q, grow, draw, k0, k1, z);
     if (q == 0) t[b] = tv;
     const int64_t e0 = (int64_t)b * per_row + 4 * q;
     if (vec) {

@@ -35,7 +35,8 @@ def test_philox_words_bit_exact(dev):
     assert [hex(int(v)) for v in philox_ref.philox_words(1, 0, 0, 0, 0)] == ['0x6627e8d5', '0xe169c58d', '0xbc57ac4c', '0x9b00dbd8']
 
 
-@pytest.mark.parametrize('rows,per_row,row0,draw', [(3, 64, 0, 0), (2, 1001, 5, 7), (1, 7, 2 ** 33 + 1, 2 ** 35 + 3), (5, 4096, 120, 1999)])
+@pytest.mark.parametrize('rows,per_row,row0,draw', [(3, 64, 0, 0), (2, 1001, 5, 7), (1, 7, 2 ** 33 + 1, 2 ** 35 + 3), (5, 4096, 120, 1999),
+                                                    (2, 6, 2 ** 33 + 3, 2 ** 32 + 7)])
 def test_randn_rows_matches_numpy_restatement(dev, rows, per_row, row0, draw):
     from sda_amd import ops
     out = torch.empty(rows, per_row, device=dev)
@@ -47,6 +48,24 @@ def test_randn_rows_matches_numpy_restatement(dev, rows, per_row, row0, draw):
     out2 = torch.empty_like(out)
     ops.randn_rows(out2, 0x1234567890abcdef, row0, draw_dev=d, draw_mul=3, draw_add=draw % 3)
     assert torch.equal(out, out2)
+
+
+def test_chain_noise_is_the_randn_rows_stream_past_32_bits(dev):
+    """Every keyed-noise kernel draws through philox.hpp's philox_normal4.  Pinned where the counter's high words are in play (row and
+    draw past 2^32): a noisy Lorenz-63 transition is, bit for bit, the noise-free transition plus noise_std times what sda_randn_rows
+    writes for the same seed, rows and draw (the kernel forms x + noise_std * z in fp32, uncontracted, as torch does here)."""
+    from sda_amd import chains, ops
+    seed, row0, draw = 0x1234567890abcdef, 2 ** 33 + 3, 2 ** 32 + 7
+    model = chains.NoisyLorenz63(dt=0.025).model()
+    noise_std = model.noise_std
+    assert noise_std > 0
+    x = torch.tensor([[1.0, 2.0, 20.0], [-3.5, 0.25, 17.0]], device=dev)
+    noisy = ops.chain_advance(model, x, torch.empty(2, 3, device=dev), 1, seed=seed, row0=row0, draw0=draw)
+    model.noise_std = 0.0
+    clean = ops.chain_advance(model, x, torch.empty(2, 3, device=dev), 1, seed=seed, row0=row0, draw0=draw)
+    z = ops.randn_rows(torch.empty(2, 3, device=dev), seed, row0, draw=draw)[:, :3]
+    assert not torch.equal(noisy, clean)
+    assert torch.equal(noisy, clean + noise_std * z)
 
 
 def test_randn_rows_is_standard_normal_and_row_keyed(dev):
