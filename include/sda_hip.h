@@ -1118,6 +1118,43 @@ int sda_enks_gain(const float* x, int m, int64_t sp, int d, const sda_chain_obs*
 int sda_enks_update(float* S, int64_t s_st, int64_t s_sp, int nslab, int m, int d, int k, float inflation, const float* a,
                     const float* z, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * The same smoother solved in ENSEMBLE space (csrc/enks_wide.hip; additive, ABI stays v14), for wide states and a modest
+ * ensemble: an m x m system instead of a k x k one, and the observed values H = A(members) come from the caller, so A is any
+ * callable.  The ensemble is S [T][m][d] fp32, time-major as above; H, Y, D, eps are [m][k] fp32, member-major, k contiguous;
+ * W is [m][m] fp32.  It is the analysis above reordered:
+ *   step 1  inflation of the observed slab: x_j <- x_j + (lambda - 1)(x_j - xbar), xbar summed in float64 in member order and
+ *           rounded to fp32; lambda == 1 touches nothing (sda_enkw_transform, mode 1, a launch of its own BEFORE H is formed);
+ *   step 2  hbar = the member mean of H, float64, member order; Y = H - hbar (fp32); D_j = (y + sigma eps_j) - h_j (fp32),
+ *           eps_j = row j of sda_randn_rows(.., seed ^ 0x454E4B53, 0, draw): the perturbations of sda_enks_gain;
+ *   step 3  G = Y Y^T, B = Y D^T, both m x m, contracted over k in float64 (products of fp32 operands are exact there);
+ *   step 4  W = (G / (m - 1) + sigma^2 I)^-1  B / (m - 1) by a float64 Cholesky factor, stored fp32;
+ *   step 5  for every slab s of the window and component c: x_j[s][c] += sum_m W[m][j] (x_m[s][c] - xbar[s][c]), xbar in
+ *           float64 in member order, the centred values rounded to fp32, the product an fp32 fma chain in member order on
+ *           the matrix cores; it is formed on the centred values only (1^T W = 0 holds analytically, not in rounding).
+ * By the push-through identity Y^T (Y Y^T / (m - 1) + sigma^2 I)^-1 = (Y^T Y / (m - 1) + sigma^2 I)^-1 Y^T this is steps 1 - 5
+ * above exactly.  Four launches per analysis (five with inflation) whatever m, k, d and the window; no atomics, nothing read
+ * back, no workgroup waits for another; bitwise reproducible; a slab's result does not depend on the other slabs of a launch.
+ *
+ * sda_enkw_prepare: step 2.  eps may be NULL.
+ * sda_enkw_gram: step 3, split over k into chunks of 512: part holds sda_enkw_gram_doubles(m, k) doubles, per chunk the
+ *   [pad16(m)][2 pad16(m)] partial of [G | B] (v_mfma_f64_16x16x4_f64; rows past m and values past k enter as zeros).
+ * sda_enkw_solve: step 4 in one workgroup: sums the partials in chunk order, factors, solves (bwork: m x m doubles of
+ *   scratch), writes W and status[0] = 0, or 1 when a pivot is not positive and finite or an entry of W is not finite; W is
+ *   then all zeros, so the transform adds nothing.  Read the status once, at the end.
+ * sda_enkw_transform: mode 0 is step 5 in place over the nslab slabs S + s * s_st (grid: tiles of 128 components x slabs;
+ *   v_mfma_f32_16x16x4_f32); mode 1 is step 1 on those slabs (W unused).  Memory outside those slabs is not touched.
+ * Served: 2 <= m <= 128, 1 <= k <= 2^24, d >= 1 with member stride s_sp >= d, nslab <= 65535, fp32; anything else is
+ * SDA_E_BADARG / SDA_E_UNSUPPORTED before any launch.
+ * ------------------------------------------------------------------------------------------ */
+int64_t sda_enkw_gram_doubles(int m, int k);
+int sda_enkw_prepare(const float* H, int m, int k, const float* y, float sigma, uint64_t seed, int64_t draw, float* Y, float* D,
+                     float* eps, void* stream);
+int sda_enkw_gram(const float* Y, const float* D, int m, int k, double* part, void* stream);
+int sda_enkw_solve(const double* part, int m, int k, float sigma, double* bwork, float* W, int32_t* status, void* stream);
+int sda_enkw_transform(float* S, int64_t s_st, int64_t s_sp, int nslab, int m, int64_t d, const float* W, float inflation, int mode,
+                       void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -456,6 +456,12 @@ SIGNATURES = {
     # ensemble Kalman smoother (csrc/enks.hip)
     'sda_enks_gain': (c_int, [c_fp, c_int, c_int64, c_int, POINTER(ChainObs), c_float, c_uint64, c_int64, c_fp, c_fp, c_fp, c_fp, c_void_p]),
     'sda_enks_update': (c_int, [c_fp, c_int64, c_int64, c_int, c_int, c_int, c_int, c_float, c_fp, c_fp, c_void_p]),
+    # its ensemble-space form for wide states (csrc/enks_wide.hip)
+    'sda_enkw_gram_doubles': (c_int64, [c_int, c_int]),
+    'sda_enkw_prepare': (c_int, [c_fp, c_int, c_int, c_fp, c_float, c_uint64, c_int64, c_fp, c_fp, c_fp, c_void_p]),
+    'sda_enkw_gram': (c_int, [c_fp, c_fp, c_int, c_int, c_fp, c_void_p]),
+    'sda_enkw_solve': (c_int, [c_fp, c_int, c_int, c_float, c_fp, c_fp, c_fp, c_void_p]),
+    'sda_enkw_transform': (c_int, [c_fp, c_int64, c_int64, c_int, c_int, c_int64, c_fp, c_float, c_int, c_void_p]),
 }
 
 _lib = None

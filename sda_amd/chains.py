@@ -30,7 +30,7 @@ from . import ops
 from ._lib import CHAIN_MAXOBS, SdaHipError
 
 __all__ = ['MarkovChain', 'DiscreteODE', 'Lorenz63', 'NoisyLorenz63', 'Lorenz96', 'LotkaVolterra', 'KolmogorovFlow', 'LinearGaussian',
-           'DampedSpring', 'AffineObservation', 'probe_affine', 'probe_linear', 'bpf_fused', 'enks_fused', 'install']
+           'DampedSpring', 'AffineObservation', 'probe_affine', 'probe_linear', 'bpf_fused', 'enks_fused', 'enks_wide', 'install']
 
 
 def _draw_seed() -> int:
@@ -817,6 +817,65 @@ def enks_fused(chain: MarkovChain, x: Tensor, y: Tensor, obs: AffineObservation,
         record.update(status=status.clone())
     ops.enks_check(status)                                   # the one read-back of the smoother
     return S.permute(1, 0, 2).contiguous()
+
+
+def enks_wide(chain: MarkovChain, x: Tensor, y: Tensor, A: Callable[[Tensor], Tensor], sigma: float, step: int = 1, *,
+              lag: Optional[int] = None, inflation: float = 1.0, seed: Optional[int] = None, record: Optional[dict] = None) -> Tensor:
+    r"""``enks_fused``'s smoother solved in ensemble space (csrc/enks_wide.hip; the arithmetic is in include/sda_hip.h): for wide
+    states and M <= 128 members, with ``A`` ANY callable from (M, \*event) members to (M, \*obs) observed values, applied with
+    torch or the ``observe`` operators.  x (M, \*event) initial members, y (N, \*obs); returns (M, N step + 1, \*event).  Time
+    convention, ``lag`` and ``inflation`` are ``enks_fused``'s, and the perturbation of member j at observation i is the same row j
+    of ``ops.randn_rows(.., seed ^ 0x454E4B53, 0, draw=i)``.
+
+    Every forecast is ``chain.trajectory``; per analysis four launches (five with inflation) beside ``A`` itself.  One read-back, at
+    the end: raises SdaHipError if an analysis had no Cholesky factor or a non-finite transform.  ``record``: a dict that receives,
+    per analysis, the ensemble before it (``S``, time-major and flattened to (time, M, d)), ``H``, ``W``, and the status words (tests
+    and small shapes only: every entry is a copy)."""
+    ops._dev(x)
+    if x.dim() < 2:
+        raise SdaHipError(f'enks_wide: members of shape {tuple(x.shape)}, expected (M, *event)')
+    m, event = x.shape[0], tuple(x.shape[1:])
+    n = len(y)
+    y = y.to(device=x.device, dtype=torch.float32).reshape(n, -1).contiguous()
+    k = y.shape[1]
+    if n < 1 or k < 1 or step < 1 or not 2 <= m <= ops.ENKW_MAX_M or (lag is not None and lag < 0):
+        raise SdaHipError(f'enks_wide: {tuple(y.shape)} observations, {m} members (2 .. {ops.ENKW_MAX_M} are served), step {step}, '
+                          f'lag {lag}')
+    seed = _draw_seed() if seed is None else int(seed)
+    kw = {'seed': seed} if isinstance(chain, (LinearGaussian, NoisyLorenz63)) else {}
+    dev = x.device
+    S = torch.empty((n * step + 1, m) + event, device=dev, dtype=torch.float32)
+    S[0] = x
+    flat = S.view(n * step + 1, m, -1)
+    Y, D, eps = (torch.empty(m, k, device=dev, dtype=torch.float32) for _ in range(3))
+    part = torch.empty(ops._lib.load().sda_enkw_gram_doubles(m, k), device=dev, dtype=torch.float64)
+    work = torch.empty(m * m, device=dev, dtype=torch.float64)
+    W = torch.empty(m, m, device=dev, dtype=torch.float32)
+    status = torch.zeros(n, device=dev, dtype=torch.int32)
+    if record is not None:
+        record.update(S=[], H=[], W=[], seed=seed)
+    for i in range(n):
+        t = (i + 1) * step
+        S[i * step + 1:t + 1] = chain.trajectory(S[i * step], step, **kw)
+        lo = 0 if lag is None else max(0, t - lag * step)
+        if record is not None:
+            record['S'].append(flat.clone())
+        ops.enkw_inflate(flat, t, inflation)
+        H = A(S[t])
+        if H.shape[0] != m or H.numel() != m * k:
+            raise SdaHipError(f'enks_wide: A gave {tuple(H.shape)} for {m} members and observations of {k} values')
+        H = H.to(torch.float32).reshape(m, k).contiguous()
+        ops.enkw_prepare(H, y[i], sigma, seed=seed, draw=i, Y=Y, D=D, eps=eps)
+        ops.enkw_gram(Y, D, part=part)
+        ops.enkw_solve(part, m, k, sigma, W=W, status=status[i:i + 1], work=work)
+        ops.enkw_transform(flat, lo, t, W)
+        if record is not None:
+            record['H'].append(H.clone())
+            record['W'].append(W.clone())
+    if record is not None:
+        record.update(status=status.clone())
+    ops.enks_check(status)                                   # the one read-back of the smoother
+    return S.transpose(0, 1).contiguous()
 
 
 def install() -> None:

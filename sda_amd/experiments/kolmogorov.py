@@ -41,6 +41,26 @@ def strong_4d_var(x_b: Tensor, y: Tensor, A: Callable[[Tensor], Tensor] = lambda
     return x0.data
 
 
+def enks(y: Tensor, A: Callable[[Tensor], Tensor] = lambda x: x, sigma: float = 1.0, step: int = 1, members: int = 64, *,
+         chain: Optional[MarkovChain] = None, lag: Optional[int] = None, inflation: float = 1.0, burn: int = 0,
+         seed: Optional[int] = None, device=None) -> Tensor:
+    r"""Ensemble-Kalman-smoother samples of p(x_{0:L} | y) with ``experiments.lorenz.enks``'s time convention: prior, ``burn``
+    transitions, then per observation ``step`` transitions and one stochastic analysis over the window, solved in ensemble space
+    (``chains.enks_wide``, at most 128 members); returns ``enks_wide(...)[:, step:]`` on the device, (members, (N - 1) step + 1, 2,
+    size, size).  ``A`` is any callable on the members (``Coarsen``, ``Subsample``, ``Vorticity`` and their compositions).  ``chain``
+    defaults to ``make_chain()``.  There is no localisation: so few members on so many components are rank-limited, and
+    ``inflation`` is the only remedy offered."""
+    from .. import chains
+    chain = make_chain() if chain is None else chain
+    if device is None:
+        device = y.device if y.is_cuda else torch.device('cuda')
+    kw = {'seed': seed} if isinstance(chain, KolmogorovFlow) else {}
+    x = chain.prior((members,), device=device, **kw)
+    if burn > 0:
+        x = chain.trajectory(x, length=burn, last=True)
+    return chains.enks_wide(chain, x, y.to(device), A, sigma, step, lag=lag, inflation=inflation, seed=seed)[:, step:]
+
+
 class LocalScoreUNet(ScoreUNet):
     r"""Score U-Net with a forcing channel sin(4 * 2 pi (i + 1/2) / size) as its single context channel
     (kolmogorov/utils.py:29-46), defined as the reference defines it: ``forward`` hands ``self.forcing`` on as the context.

@@ -132,23 +132,30 @@ def posterior(y: Tensor, A: Callable[[Tensor], Tensor] = lambda x: x, sigma: flo
 
 def enks(y: Tensor, A: Callable[[Tensor], Tensor] = lambda x: x, sigma: float = 1.0, step: int = 1, members: int = 1024, *,
          lag: Optional[int] = None, inflation: float = 1.0, chain: Optional[chains.MarkovChain] = None, burn: int = 64,
-         seed: Optional[int] = None, device=None) -> Tensor:
+         seed: Optional[int] = None, device=None, space: str = 'observation') -> Tensor:
     r"""Ensemble-Kalman-smoother samples of p(x_{0:L} | y) with ``posterior``'s time convention and return shape: prior, ``burn``
     transitions, then per observation ``step`` transitions and one stochastic analysis over the window (``chains.enks_fused``);
     returns ``enks_fused(...)[:, step:]`` on the device.  ``A`` must be a ``chains.AffineObservation`` or probe as one
     (``chains.probe_affine``), else this raises as ``posterior(fused=True)`` does.  ``chain`` defaults to ``make_chain()``; any
-    ``DiscreteODE`` the kernels serve works (``chains.Lorenz96(n)``), where a particle filter has no hope."""
+    ``DiscreteODE`` the kernels serve works (``chains.Lorenz96(n)``), where a particle filter has no hope.
+
+    ``space='ensemble'`` solves the same analysis in ensemble space (``chains.enks_wide``): at most 128 members, and ``A`` is any
+    callable on the members; it is not probed."""
+    if space not in ('observation', 'ensemble'):
+        raise ValueError(f"enks: space={space!r}, expected 'observation' or 'ensemble'")
     chain = make_chain() if chain is None else chain
     if device is None:
         device = y.device if y.is_cuda else torch.device('cuda')
     x = chain.prior((members,), device=device)
-    obs = chains.probe_affine(A, chain, x.shape[-1])
-    if obs is None:
+    obs = chains.probe_affine(A, chain, x.shape[-1]) if space == 'observation' else None
+    if obs is None and space == 'observation':
         raise SdaHipError('enks: A is not an affine selection of state components (each output an affine function of exactly one '
                           'component)')
     kw = {'seed': seed} if isinstance(chain, (chains.NoisyLorenz63, chains.LinearGaussian)) else {}
     if burn > 0:
         x = chain.trajectory(x, length=burn, last=True, **kw)
+    if space == 'ensemble':
+        return chains.enks_wide(chain, x, y.to(device), A, sigma, step, lag=lag, inflation=inflation, seed=seed)[:, step:]
     return chains.enks_fused(chain, x, y.to(device), obs, sigma, step, lag=lag, inflation=inflation, seed=seed)[:, step:]
 
 

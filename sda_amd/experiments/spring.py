@@ -80,20 +80,25 @@ def posterior(y: Tensor, A: Callable[[Tensor], Tensor] = _IDENTITY, sigma: float
 
 def enks(y: Tensor, A: Callable[[Tensor], Tensor] = _IDENTITY, sigma: float = 1.0, step: int = 1, members: int = 1024, *,
          lag: Optional[int] = None, inflation: float = 1.0, chain: Optional[chains.LinearGaussian] = None, burn: int = 64,
-         seed: Optional[int] = None, device=None) -> Tensor:
+         seed: Optional[int] = None, device=None, space: str = 'observation') -> Tensor:
     r"""Ensemble-Kalman-smoother samples of p(x_{0:L} | y), (members, T + 1, d) fp32 on the device under the time convention above
     (``chains.enks_fused(...)[:, step:]``): the approximate counterpart of ``posterior``, which it approaches as ``members`` grows.
-    ``A`` must probe as an affine selection of state components (``chains.probe_affine``)."""
+    ``A`` must probe as an affine selection of state components (``chains.probe_affine``).  ``space='ensemble'`` solves the same
+    analysis in ensemble space (``chains.enks_wide``): at most 128 members, ``A`` any callable on the members, not probed."""
+    if space not in ('observation', 'ensemble'):
+        raise ValueError(f"enks: space={space!r}, expected 'observation' or 'ensemble'")
     chain = make_chain() if chain is None else chain
     if device is None:
         device = y.device if y.is_cuda else torch.device('cuda')
-    obs = chains.probe_affine(A, chain, chain.d)
-    if obs is None:
+    obs = chains.probe_affine(A, chain, chain.d) if space == 'observation' else None
+    if obs is None and space == 'observation':
         raise SdaHipError('enks: A is not an affine selection of state components (each output an affine function of exactly one '
                           'component)')
     x = chain.prior((members,), device=device)
     if burn > 0:
         x = chain.trajectory(x, length=burn, last=True, seed=seed)
+    if space == 'ensemble':
+        return chains.enks_wide(chain, x, y.to(device), A, sigma, step, lag=lag, inflation=inflation, seed=seed)[:, step:]
     return chains.enks_fused(chain, x, y.to(device), obs, sigma, step, lag=lag, inflation=inflation, seed=seed)[:, step:]
 
 

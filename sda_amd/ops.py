@@ -1446,6 +1446,101 @@ def enks_check(status: Tensor) -> None:
         raise _lib.SdaHipError(f'ensemble Kalman smoother: the innovation covariance is not positive definite at observation(s) {bad}')
 
 
+# ---------------------------------------------------------------- its ensemble-space form (csrc/enks_wide.hip)
+ENKW_MAX_M = 128
+
+
+def _enkw_mk(t: Optional[Tensor], m: int, k: int, like: Tensor, what: str) -> Tensor:
+    if t is None:
+        return torch.empty(m, k, device=like.device, dtype=torch.float32)
+    _dev(t)
+    if tuple(t.shape) != (m, k) or not t.is_contiguous():
+        raise _lib.SdaHipError(f'{what}: a contiguous ({m}, {k}) fp32 device tensor expected')
+    return t
+
+
+def _enkw_f64(t: Optional[Tensor], n: int, like: Tensor, what: str) -> Tensor:
+    if t is None:
+        return torch.empty(n, device=like.device, dtype=torch.float64)
+    if not t.is_cuda or t.dtype != torch.float64 or not t.is_contiguous() or t.numel() < n:
+        raise _lib.SdaHipError(f'{what}: at least {n} contiguous float64 values on the device expected')
+    return t
+
+
+def enkw_prepare(H: Tensor, y: Tensor, sigma: float, *, seed: int = 0, draw: int = 0, Y: Optional[Tensor] = None,
+                 D: Optional[Tensor] = None, eps: Optional[Tensor] = None):
+    """Step 2 of the ensemble-space analysis (include/sda_hip.h): H (members, k) observed values, y (k,) -> the anomalies ``Y``,
+    the perturbed innovations ``D`` and the perturbations ``eps``, all (members, k), one launch."""
+    _dev(H, y)
+    if H.dim() != 2 or not H.is_contiguous() or H.shape[1] < 1 or y.numel() != H.shape[1] or not y.is_contiguous():
+        raise _lib.SdaHipError(f'enkw_prepare: H {tuple(H.shape)} and y {tuple(y.shape)}, expected contiguous (members, k) and (k,)')
+    m, k = H.shape
+    Y, D, eps = (_enkw_mk(v, m, k, H, 'enkw_prepare') for v in (Y, D, eps))
+    _lib.check(_lib.load().sda_enkw_prepare(H.data_ptr(), m, k, y.data_ptr(), float(sigma), seed & 0xffffffffffffffff, draw,
+                                            Y.data_ptr(), D.data_ptr(), eps.data_ptr(), _stream()), 'sda_enkw_prepare')
+    return Y, D, eps
+
+
+def enkw_gram(Y: Tensor, D: Tensor, *, part: Optional[Tensor] = None) -> Tensor:
+    """Step 3: the float64 partials of [Y Y^T | Y D^T], one (pad16(m), 2 pad16(m)) block per chunk of 512 observed values."""
+    _dev(Y, D)
+    if Y.dim() != 2 or Y.shape != D.shape or not Y.is_contiguous() or not D.is_contiguous() or Y.shape[1] < 1:
+        raise _lib.SdaHipError(f'enkw_gram: Y {tuple(Y.shape)} and D {tuple(D.shape)}, expected contiguous (members, k)')
+    m, k = Y.shape
+    n = _lib.load().sda_enkw_gram_doubles(m, k)
+    if n <= 0:
+        _lib.check(-2, 'sda_enkw_gram')
+    part = _enkw_f64(part, n, Y, 'enkw_gram: part')
+    _lib.check(_lib.load().sda_enkw_gram(Y.data_ptr(), D.data_ptr(), m, k, part.data_ptr(), _stream()), 'sda_enkw_gram')
+    return part
+
+
+def enkw_solve(part: Tensor, m: int, k: int, sigma: float, *, W: Optional[Tensor] = None, status: Optional[Tensor] = None,
+               work: Optional[Tensor] = None):
+    """Step 4: ``W`` (m, m) fp32 and status (1,) int32 (1: no Cholesky factor, or a non-finite W; W is then zero) from the partials
+    of ``enkw_gram(Y, D)`` with Y (m, k), one launch of one workgroup, nothing read back."""
+    n = _lib.load().sda_enkw_gram_doubles(m, k)
+    if n <= 0:
+        _lib.check(-2, 'sda_enkw_solve')
+    part = _enkw_f64(part, n, part, 'enkw_solve: part')
+    work = _enkw_f64(work, m * m, part, 'enkw_solve: work')
+    if W is None:
+        W = torch.empty(m, m, device=part.device, dtype=torch.float32)
+    _dev(W)
+    if tuple(W.shape) != (m, m) or not W.is_contiguous():
+        raise _lib.SdaHipError(f'enkw_solve: a contiguous ({m}, {m}) fp32 device tensor expected for W')
+    status = torch.zeros(1, device=part.device, dtype=torch.int32) if status is None else status
+    if status.dtype != torch.int32 or status.numel() < 1 or not status.is_cuda:
+        raise _lib.SdaHipError('enkw_solve: status (1,) int32 on the device expected')
+    _lib.check(_lib.load().sda_enkw_solve(part.data_ptr(), m, k, float(sigma), work.data_ptr(), W.data_ptr(), status.data_ptr(),
+                                          _stream()), 'sda_enkw_solve')
+    return W, status
+
+
+def enkw_transform(S: Tensor, lo: int, t: int, W: Tensor) -> Tensor:
+    """Step 5, in place on the slabs ``S[lo] .. S[t]`` of the time-major ensemble S (time, members, d), one launch."""
+    _enks_slabs(S, 'enkw_transform')
+    if not 0 <= lo <= t < S.shape[0]:
+        raise _lib.SdaHipError(f'enkw_transform: window {lo} .. {t} of {S.shape[0]} slabs')
+    m, d = S.shape[1], S.shape[2]
+    _dev(W)
+    if tuple(W.shape) != (m, m) or not W.is_contiguous():
+        raise _lib.SdaHipError(f'enkw_transform: W {tuple(W.shape)}, expected contiguous ({m}, {m})')
+    _lib.check(_lib.load().sda_enkw_transform(S[lo].data_ptr(), S.stride(0), S.stride(1), t - lo + 1, m, d, W.data_ptr(), 1.0, 0,
+                                              _stream()), 'sda_enkw_transform')
+    return S
+
+
+def enkw_inflate(S: Tensor, t: int, inflation: float) -> Tensor:
+    """Step 1, in place on slab ``S[t]`` (the transform launch in its inflation mode); ``inflation == 1`` launches nothing."""
+    _enks_slabs(S, 'enkw_inflate')
+    if not 0 <= t < S.shape[0]:
+        raise _lib.SdaHipError(f'enkw_inflate: slab {t} of {S.shape[0]}')
+    _lib.check(_lib.load().sda_enkw_transform(S[t].data_ptr(), S.stride(0), S.stride(1), 1, S.shape[1], S.shape[2], None,
+                                              float(inflation), 1, _stream()), 'sda_enkw_transform')
+    return S
+
+
 # ---------------------------------------------------------------- Kolmogorov flow (csrc/kflow.hip)
 _KFLOW_CONST = {}
 _KFLOW_SOLVE = {}
