@@ -1155,6 +1155,48 @@ int sda_enkw_solve(const double* part, int m, int k, float sigma, double* bwork,
 int sda_enkw_transform(float* S, int64_t s_st, int64_t s_sp, int nslab, int m, int64_t d, const float* W, float inflation, int mode,
                        void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * The ensemble-space smoother LOCALISED by domain (csrc/enks_local.hip; additive, ABI stays v14): R-localisation as in the LETKF
+ * literature, in this project's perturbed-observation form.
+ *   Grid and blocks.  The state event is a periodic grid [C][Hg][Wg] (a ring of n components is [1][1][n]), cut into blocks of
+ *     bh x bw points, Hg % bh == 0 and Wg % bw == 0; block b = br (Wg / bw) + bc.  All C channels of a block's points share one
+ *     weight matrix W[b].  A block's components are numbered q = (channel, row, column inside the block), row-major.
+ *   Weights.  Observed value i sits at the real-valued grid position p_i = (row, col).  For block b with centre c_b (the mean of its
+ *     points' coordinates) rho_{b,i} = GC(dist(c_b, p_i) / radius), dist the periodic Euclidean distance on the Hg x Wg torus and GC
+ *     the Gaspari-Cohn fifth-order function, of support 2 radius:
+ *       0 <= z <= 1:  -z^5/4 + z^4/2 + 5 z^3/8 - 5 z^2/3 + 1
+ *       1 <  z <  2:   z^5/12 - z^4/2 + 5 z^3/8 + 5 z^2/3 - 5 z + 4 - 2/(3 z)
+ *       otherwise 0.
+ *   Plan.  Positions are fixed for a run, so the lists are built once, on the host, in float64, and uploaded as a CSR table:
+ *     offsets[nblk + 1], idx[nnz] int32 ascending inside a block, rho[nnz] rounded to fp32; only entries whose fp32 value is
+ *     strictly positive are listed.  (The library takes the table; sda_amd.ops.enkl_plan builds it.)
+ *   Per analysis.  Steps 1 and 2 are sda_enkw_transform (mode 1) and sda_enkw_prepare above, unchanged: the same Y, D and
+ *     perturbation stream.  Then for every block b, summed over its listed i in list order:
+ *       G_b = sum_i rho_{b,i} Y[:, i] Y[:, i]^T,   B_b = sum_i rho_{b,i} Y[:, i] D[:, i]^T      (float64; rho Y is exact there)
+ *       W_b = (G_b / (m - 1) + sigma^2 I)^-1  B_b / (m - 1)                                      (float64 Cholesky, stored fp32)
+ *     and for every slab s of the window and component q of the block x_j[s][q] += sum_m W_b[m][j] (x_m[s][q] - xbar[s][q]),
+ *     formed as step 5 above.  With every rho = 1 and one block this is the analysis above; a block with an empty list has
+ *     W_b = 0 and is not touched.
+ * sda_enkl_pack: T [k][2 m] fp32, T[i] = (Y[:, i] | D[:, i]), so a gathered observed value is 2 m contiguous floats.
+ * sda_enkl_weights: one workgroup per block: [G_b | B_b] on v_mfma_f64_16x16x4_f64 over the list, the factor in LDS (m^2 doubles:
+ *   m <= 128), the solve; bwork: nblk m^2 doubles of scratch; W [nblk][m][m] fp32; status[b] = 0, or 1 when a pivot is not
+ *   positive and finite, an entry of W[b] is not finite or an index is outside 0 .. k - 1 (it is then not read); W[b] is then
+ *   all zeros, and no other block is affected.  Read the status once, at the end.
+ * sda_enkl_transform: grid (blocks x tiles of 128 block components, slabs), in place over the nslab slabs S + s * s_st, member
+ *   stride s_sp >= C Hg Wg; v_mfma_f32_16x16x4_f32.  A block with an empty list is skipped without a load.  Memory outside
+ *   those slabs is not touched.
+ * Three launches per analysis after prepare; no atomics, nothing read back, no workgroup waits for another; bitwise
+ * reproducible; a block's result depends on its own list alone and a slab's on m, the block and W[b] alone.
+ * Served: 2 <= m <= 128, 1 <= k <= 2^24, nblk <= 2^22, nslab <= 65535, fp32, periodic grids only; anything else is
+ * SDA_E_BADARG / SDA_E_UNSUPPORTED before any launch.  The analysis is discontinuous across block edges (no interpolation of
+ * the weights between blocks), and there is no localisation in time.
+ * ------------------------------------------------------------------------------------------ */
+int sda_enkl_pack(const float* Y, const float* D, int m, int k, float* T, void* stream);
+int sda_enkl_weights(const float* T, int m, int k, const int32_t* offsets, const int32_t* idx, const float* rho, int nblk, float sigma,
+                     double* bwork, float* W, int32_t* status, void* stream);
+int sda_enkl_transform(float* S, int64_t s_st, int64_t s_sp, int nslab, int m, int C, int Hg, int Wg, int bh, int bw,
+                       const int32_t* offsets, const float* W, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

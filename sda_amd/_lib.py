@@ -462,6 +462,10 @@ SIGNATURES = {
     'sda_enkw_gram': (c_int, [c_fp, c_fp, c_int, c_int, c_fp, c_void_p]),
     'sda_enkw_solve': (c_int, [c_fp, c_int, c_int, c_float, c_fp, c_fp, c_fp, c_void_p]),
     'sda_enkw_transform': (c_int, [c_fp, c_int64, c_int64, c_int, c_int, c_int64, c_fp, c_float, c_int, c_void_p]),
+    # its domain-localised form for grid states (csrc/enks_local.hip)
+    'sda_enkl_pack': (c_int, [c_fp, c_fp, c_int, c_int, c_fp, c_void_p]),
+    'sda_enkl_weights': (c_int, [c_fp, c_int, c_int, c_fp, c_fp, c_fp, c_int, c_float, c_fp, c_fp, c_fp, c_void_p]),
+    'sda_enkl_transform': (c_int, [c_fp, c_int64, c_int64, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_fp, c_fp, c_void_p]),
 }
 
 _lib = None

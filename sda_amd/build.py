@@ -16,11 +16,11 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, 'csrc')
 LIBDIR = os.environ.get('SDA_LIBDIR') or os.path.join(HERE, 'lib')      # (SDA_LIBDIR: tooling builds beside the product one)
 ARCH = 'gfx950'
-SOURCES = ['conv_igemm.hip', 'conv_wino4.hip', 'conv_small1d.hip', 'conv_few.hip', 'conv_par4.hip', 'conv_h2.hip', 'conv3d.hip', 'conv_wgrad.hip', 'conv_wgrad3.hip', 'block1d.hip', 'net1d.hip', 'net1d_train.hip', 'step1d.hip', 'norm.hip', 'elementwise.hip', 'linear.hip', 'mlp1d.hip', 'mlp_train.hip', 'optim.hip', 'train_loss.hip', 'dataset.hip', 'observe.hip', 'metrics.hip', 'assign.hip', 'noise.hip', 'chain.hip', 'lgss.hip', 'enks.hip', 'enks_wide.hip', 'kflow.hip', 'probe.hip']
+SOURCES = ['conv_igemm.hip', 'conv_wino4.hip', 'conv_small1d.hip', 'conv_few.hip', 'conv_par4.hip', 'conv_h2.hip', 'conv3d.hip', 'conv_wgrad.hip', 'conv_wgrad3.hip', 'block1d.hip', 'net1d.hip', 'net1d_train.hip', 'step1d.hip', 'norm.hip', 'elementwise.hip', 'linear.hip', 'mlp1d.hip', 'mlp_train.hip', 'optim.hip', 'train_loss.hip', 'dataset.hip', 'observe.hip', 'metrics.hip', 'assign.hip', 'noise.hip', 'chain.hip', 'lgss.hip', 'enks.hip', 'enks_wide.hip', 'enks_local.hip', 'kflow.hip', 'probe.hip']
 HIPCC = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
 # extra compile flags (e.g. SDA_EXTRA_HIPCC_FLAGS=-DSDA_W4_VARIANTS builds the tuning variants tools/wino4_check.py compares)
 EXTRA_FLAGS = os.environ.get('SDA_EXTRA_HIPCC_FLAGS', '').split()
-EMU_SOURCES = ['conv_igemm.hip', 'conv_wino4.hip', 'conv_h2.hip', 'conv_wgrad.hip', 'conv_wgrad3.hip', 'chain.hip', 'lgss.hip', 'enks.hip', 'enks_wide.hip', 'mlp_train.hip', 'net1d_train.hip', 'optim.hip', 'assign.hip']       # host replays of the tile algorithms, the Winograd / f16x2 kernels' pick functions, the chain, linear-Gaussian and ensemble-smoother arithmetic, the optimizer step and the auction (libsda_emu.so)
+EMU_SOURCES = ['conv_igemm.hip', 'conv_wino4.hip', 'conv_h2.hip', 'conv_wgrad.hip', 'conv_wgrad3.hip', 'chain.hip', 'lgss.hip', 'enks.hip', 'enks_wide.hip', 'enks_local.hip', 'mlp_train.hip', 'net1d_train.hip', 'optim.hip', 'assign.hip']       # host replays of the tile algorithms, the Winograd / f16x2 kernels' pick functions, the chain, linear-Gaussian and ensemble-smoother arithmetic, the optimizer step and the auction (libsda_emu.so)
 CONV_PARTS = 4                                       # see SDA_CONV_PART in csrc/conv_igemm.hip
 
 

@@ -30,7 +30,7 @@ from . import ops
 from ._lib import CHAIN_MAXOBS, SdaHipError
 
 __all__ = ['MarkovChain', 'DiscreteODE', 'Lorenz63', 'NoisyLorenz63', 'Lorenz96', 'LotkaVolterra', 'KolmogorovFlow', 'LinearGaussian',
-           'DampedSpring', 'AffineObservation', 'probe_affine', 'probe_linear', 'bpf_fused', 'enks_fused', 'enks_wide', 'install']
+           'DampedSpring', 'AffineObservation', 'probe_affine', 'probe_linear', 'bpf_fused', 'enks_fused', 'enks_wide', 'enks_local', 'install']
 
 
 def _draw_seed() -> int:
@@ -875,6 +875,68 @@ def enks_wide(chain: MarkovChain, x: Tensor, y: Tensor, A: Callable[[Tensor], Te
     if record is not None:
         record.update(status=status.clone())
     ops.enks_check(status)                                   # the one read-back of the smoother
+    return S.transpose(0, 1).contiguous()
+
+
+def enks_local(chain: MarkovChain, x: Tensor, y: Tensor, A: Callable[[Tensor], Tensor], sigma: float, step: int = 1, *,
+               positions, radius: float, block, lag: Optional[int] = None, inflation: float = 1.0, seed: Optional[int] = None,
+               record: Optional[dict] = None) -> Tensor:
+    r"""``enks_wide``'s smoother with the analysis LOCALISED by domain (csrc/enks_local.hip; the arithmetic is in
+    include/sda_hip.h): the event of ``x`` is a periodic grid (C, Hg, Wg), or a ring (n,), cut into blocks of ``block`` points;
+    every block solves its own M x M system over the observed values within ``2 radius`` grid points of its centre, each weighted
+    by the Gaspari-Cohn function of its distance, and updates its own components.  ``positions`` (k, 2) are the (row, col) of the
+    observed values in ``A``'s flattened output order ((k,) on a ring; ``observe.positions(A, event)`` gives them for the operators
+    whose outputs sit on the grid); ``radius=float('inf')`` with one block is ``enks_wide``'s analysis.  Signature otherwise, time
+    convention, ``lag``, ``inflation``, perturbation stream and return shape are ``enks_wide``'s; M <= 128.
+
+    The plan is built once (``ops.enkl_plan``); per analysis four launches (five with inflation) beside ``A`` itself.  One
+    read-back, at the end: raises SdaHipError if a block of an analysis had no Cholesky factor or a non-finite transform (that
+    block alone was left untouched).  ``record`` receives what ``enks_wide``'s does, with ``W`` of shape (nblk, M, M) and the
+    status words (N, nblk), and the ``plan``."""
+    ops._dev(x)
+    if x.dim() not in (2, 4):
+        raise SdaHipError(f'enks_local: members of shape {tuple(x.shape)}, expected (M, C, Hg, Wg) or (M, n)')
+    m, event = x.shape[0], tuple(x.shape[1:])
+    n = len(y)
+    y = y.to(device=x.device, dtype=torch.float32).reshape(n, -1).contiguous()
+    k = y.shape[1]
+    if n < 1 or k < 1 or step < 1 or not 2 <= m <= ops.ENKW_MAX_M or (lag is not None and lag < 0):
+        raise SdaHipError(f'enks_local: {tuple(y.shape)} observations, {m} members (2 .. {ops.ENKW_MAX_M} are served), step {step}, '
+                          f'lag {lag}')
+    plan = ops.enkl_plan(event, positions, radius, block, device=x.device)
+    if plan.k != k:
+        raise SdaHipError(f'enks_local: {plan.k} positions for observations of {k} values')
+    seed = _draw_seed() if seed is None else int(seed)
+    kw = {'seed': seed} if isinstance(chain, (LinearGaussian, NoisyLorenz63)) else {}
+    dev = x.device
+    S = torch.empty((n * step + 1, m) + event, device=dev, dtype=torch.float32)
+    S[0] = x
+    flat = S.view(n * step + 1, m, -1)
+    Y, D, eps = (torch.empty(m, k, device=dev, dtype=torch.float32) for _ in range(3))
+    W = torch.empty(plan.nblk, m, m, device=dev, dtype=torch.float32)
+    status = torch.zeros(n, plan.nblk, device=dev, dtype=torch.int32)
+    if record is not None:
+        record.update(S=[], H=[], W=[], seed=seed, plan=plan)
+    for i in range(n):
+        t = (i + 1) * step
+        S[i * step + 1:t + 1] = chain.trajectory(S[i * step], step, **kw)
+        lo = 0 if lag is None else max(0, t - lag * step)
+        if record is not None:
+            record['S'].append(flat.clone())
+        ops.enkw_inflate(flat, t, inflation)
+        H = A(S[t])
+        if H.shape[0] != m or H.numel() != m * k:
+            raise SdaHipError(f'enks_local: A gave {tuple(H.shape)} for {m} members and observations of {k} values')
+        H = H.to(torch.float32).reshape(m, k).contiguous()
+        ops.enkw_prepare(H, y[i], sigma, seed=seed, draw=i, Y=Y, D=D, eps=eps)
+        ops.enkl_weights(plan, Y, D, sigma, W=W, status=status[i])
+        ops.enkl_transform(plan, flat, lo, t, W)
+        if record is not None:
+            record['H'].append(H.clone())
+            record['W'].append(W.clone())
+    if record is not None:
+        record.update(status=status.clone())
+    ops.enkl_check(status)                                   # the one read-back of the smoother
     return S.transpose(0, 1).contiguous()
 
 

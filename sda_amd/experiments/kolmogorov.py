@@ -43,13 +43,18 @@ def strong_4d_var(x_b: Tensor, y: Tensor, A: Callable[[Tensor], Tensor] = lambda
 
 def enks(y: Tensor, A: Callable[[Tensor], Tensor] = lambda x: x, sigma: float = 1.0, step: int = 1, members: int = 64, *,
          chain: Optional[MarkovChain] = None, lag: Optional[int] = None, inflation: float = 1.0, burn: int = 0,
-         seed: Optional[int] = None, device=None) -> Tensor:
+         seed: Optional[int] = None, device=None, radius: Optional[float] = None, block=(4, 4), positions=None) -> Tensor:
     r"""Ensemble-Kalman-smoother samples of p(x_{0:L} | y) with ``experiments.lorenz.enks``'s time convention: prior, ``burn``
     transitions, then per observation ``step`` transitions and one stochastic analysis over the window, solved in ensemble space
     (``chains.enks_wide``, at most 128 members); returns ``enks_wide(...)[:, step:]`` on the device, (members, (N - 1) step + 1, 2,
     size, size).  ``A`` is any callable on the members (``Coarsen``, ``Subsample``, ``Vorticity`` and their compositions).  ``chain``
-    defaults to ``make_chain()``.  There is no localisation: so few members on so many components are rank-limited, and
-    ``inflation`` is the only remedy offered."""
+    defaults to ``make_chain()``.
+
+    ``radius=None`` is the global analysis: so few members on so many components are rank-limited.  A number localises it by
+    domain (``chains.enks_local``): blocks of ``block`` grid points, each analysed with the observed values within ``2 radius``
+    grid points under Gaspari-Cohn weights.  The positions of the observed values come from ``observe.positions(A, event)``
+    (``Coarsen``, ``Subsample`` / ``Crop``, ``Vorticity``, ``Pointwise``, ``Mask`` and their compositions); for any other ``A``
+    pass ``positions`` (k, 2) yourself."""
     from .. import chains
     chain = make_chain() if chain is None else chain
     if device is None:
@@ -58,6 +63,12 @@ def enks(y: Tensor, A: Callable[[Tensor], Tensor] = lambda x: x, sigma: float = 
     x = chain.prior((members,), device=device, **kw)
     if burn > 0:
         x = chain.trajectory(x, length=burn, last=True)
+    if radius is not None:
+        if positions is None:
+            from .. import observe
+            positions = observe.positions(A, tuple(x.shape[1:]))
+        return chains.enks_local(chain, x, y.to(device), A, sigma, step, positions=positions, radius=radius, block=block, lag=lag,
+                                 inflation=inflation, seed=seed)[:, step:]
     return chains.enks_wide(chain, x, y.to(device), A, sigma, step, lag=lag, inflation=inflation, seed=seed)[:, step:]
 
 

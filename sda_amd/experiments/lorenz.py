@@ -132,7 +132,8 @@ def posterior(y: Tensor, A: Callable[[Tensor], Tensor] = lambda x: x, sigma: flo
 
 def enks(y: Tensor, A: Callable[[Tensor], Tensor] = lambda x: x, sigma: float = 1.0, step: int = 1, members: int = 1024, *,
          lag: Optional[int] = None, inflation: float = 1.0, chain: Optional[chains.MarkovChain] = None, burn: int = 64,
-         seed: Optional[int] = None, device=None, space: str = 'observation') -> Tensor:
+         seed: Optional[int] = None, device=None, space: str = 'observation', radius: Optional[float] = None, block: int = 4,
+         positions=None) -> Tensor:
     r"""Ensemble-Kalman-smoother samples of p(x_{0:L} | y) with ``posterior``'s time convention and return shape: prior, ``burn``
     transitions, then per observation ``step`` transitions and one stochastic analysis over the window (``chains.enks_fused``);
     returns ``enks_fused(...)[:, step:]`` on the device.  ``A`` must be a ``chains.AffineObservation`` or probe as one
@@ -140,7 +141,11 @@ def enks(y: Tensor, A: Callable[[Tensor], Tensor] = lambda x: x, sigma: float = 
     ``DiscreteODE`` the kernels serve works (``chains.Lorenz96(n)``), where a particle filter has no hope.
 
     ``space='ensemble'`` solves the same analysis in ensemble space (``chains.enks_wide``): at most 128 members, and ``A`` is any
-    callable on the members; it is not probed."""
+    callable on the members; it is not probed.  There ``radius`` (in components; None: the global analysis) localises the
+    analysis on the ring (``chains.enks_local``): blocks of ``block`` components, each analysed with the observed values within
+    ``2 radius`` under Gaspari-Cohn weights.  The positions of the observed values are those of ``observe.positions`` for an
+    ``observe`` operator, else the components a probe finds when ``A`` is a plain selection of them; for anything else pass
+    ``positions`` (k,)."""
     if space not in ('observation', 'ensemble'):
         raise ValueError(f"enks: space={space!r}, expected 'observation' or 'ensemble'")
     chain = make_chain() if chain is None else chain
@@ -154,9 +159,29 @@ def enks(y: Tensor, A: Callable[[Tensor], Tensor] = lambda x: x, sigma: float = 
     kw = {'seed': seed} if isinstance(chain, (chains.NoisyLorenz63, chains.LinearGaussian)) else {}
     if burn > 0:
         x = chain.trajectory(x, length=burn, last=True, **kw)
+    if radius is not None:
+        if space != 'ensemble':
+            raise ValueError("enks: radius= localises the ensemble-space analysis; pass space='ensemble'")
+        if positions is None:
+            positions = _ring_positions(A, chain, x.shape[-1])
+        return chains.enks_local(chain, x, y.to(device), A, sigma, step, positions=positions, radius=radius, block=block, lag=lag,
+                                 inflation=inflation, seed=seed)[:, step:]
     if space == 'ensemble':
         return chains.enks_wide(chain, x, y.to(device), A, sigma, step, lag=lag, inflation=inflation, seed=seed)[:, step:]
     return chains.enks_fused(chain, x, y.to(device), obs, sigma, step, lag=lag, inflation=inflation, seed=seed)[:, step:]
+
+
+def _ring_positions(A, chain, d: int):
+    """Where on the ring the outputs of ``A`` sit: ``observe.positions`` for an ``observe`` operator, else the components of a
+    probed selection (``chains.probe_affine``)."""
+    from .. import observe
+    if isinstance(A, observe.Observation):
+        return observe.positions(A, (d,))[:, 1]
+    obs = chains.probe_affine(A, chain, d)
+    if obs is None:
+        raise SdaHipError('enks: A is not a selection of state components, so the positions of its outputs are not known; pass '
+                          'positions=')
+    return [float(i) for i in obs.index]
 
 
 def weak_4d_var(x: Tensor, y: Tensor, A: Callable[[Tensor], Tensor] = lambda x: x, sigma: float = 1.0, step: int = 1,

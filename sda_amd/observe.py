@@ -417,3 +417,44 @@ class Compose(Observation):
         for op, shp in zip(reversed(self.ops), reversed(shapes)):
             r = op.adjoint(r, shp)
         return r
+
+
+def positions(A, event):
+    """The grid positions of ``A``'s outputs for a state of shape ``event`` = (C, Hg, Wg), or (n,) for a ring: (k, 2) float64
+    (row, col) in the flattened output order, what ``chains.enks_local`` localises with.  Served are the operators whose outputs sit
+    on the grid: ``Coarsen(r)`` (cell centres), ``Subsample`` / ``Crop`` (the sampled points), ``Vorticity``, ``Pointwise`` and
+    ``Mask`` (positions pass through) and a ``Compose`` of them; anything else raises: hand the positions over yourself."""
+    import numpy as np
+    event = tuple(int(e) for e in event)
+    if len(event) == 1:
+        grid = np.stack([np.zeros(event[0]), np.arange(event[0], dtype=np.float64)], axis=-1)
+    elif len(event) == 3:
+        r, c = np.meshgrid(np.arange(event[1], dtype=np.float64), np.arange(event[2], dtype=np.float64), indexing='ij')
+        grid = np.broadcast_to(np.stack([r, c], axis=-1), event + (2,)).copy()
+    else:
+        raise _lib.SdaHipError(f'positions: event {event}, expected (C, Hg, Wg) or (n,)')
+
+    def walk(op, p):
+        if isinstance(op, Compose):
+            for member in op.ops:
+                p = walk(member, p)
+            return p
+        if isinstance(op, Coarsen):
+            *lead, h, w, two = p.shape
+            if len(p.shape) < 3 or h % op.f or w % op.f:
+                raise _lib.SdaHipError(f'positions: Coarsen({op.f}) of a field of shape {p.shape[:-1]}')
+            return p.reshape(*lead, h // op.f, op.f, w // op.f, op.f, 2).mean(axis=(-4, -2))
+        if isinstance(op, Subsample):                                      # (Crop is one)
+            nd = len(op.slices)
+            if nd > p.ndim - 1:
+                raise _lib.SdaHipError(f'positions: {nd} slices for a field of shape {p.shape[:-1]}')
+            return p[(Ellipsis,) + op.slices + (slice(None),)]
+        if isinstance(op, Vorticity):
+            if p.ndim < 4 or p.shape[-4] != 2:
+                raise _lib.SdaHipError(f'positions: Vorticity of a field of shape {p.shape[:-1]}')
+            return p[..., 0, :, :, :]
+        if isinstance(op, (Pointwise, Mask)):
+            return p
+        raise _lib.SdaHipError(f'positions: the outputs of {type(op).__name__} have no grid positions known here; pass positions=')
+
+    return np.ascontiguousarray(walk(A, grid).reshape(-1, 2))

@@ -1541,6 +1541,143 @@ def enkw_inflate(S: Tensor, t: int, inflation: float) -> Tensor:
     return S
 
 
+# ---------------------------------------------------------------- its domain-localised form (csrc/enks_local.hip)
+def gaspari_cohn(z):
+    """The Gaspari-Cohn fifth-order function of a float64 numpy array z >= 0 (support 2; include/sda_hip.h)."""
+    import numpy as np
+    z = np.asarray(z, np.float64)
+    near = ((((-0.25 * z + 0.5) * z + 0.625) * z - 5.0 / 3.0) * z * z) + 1.0
+    zf = np.where(z > 1.0, z, 1.0)                                    # (keeps 2 / (3 z) finite where the far branch is unused)
+    far = ((((zf / 12.0 - 0.5) * zf + 0.625) * zf + 5.0 / 3.0) * zf - 5.0) * zf + 4.0 - 2.0 / (3.0 * zf)
+    return np.where(z <= 1.0, near, np.where(z < 2.0, far, 0.0))
+
+
+class EnklPlan:
+    """What ``enkl_plan`` returns: the grid ``event`` (C, Hg, Wg), ``block`` (bh, bw), ``nblk``, ``k`` observed values, the CSR
+    lists on the device (``offsets`` (nblk + 1,) int32, ``idx`` (nnz,) int32, ``rho`` (nnz,) fp32) and their host copies
+    (``offsets_host`` ..., numpy).  Scratch of the weights launch is kept here per ensemble size."""
+
+    def __init__(self, event, block, k, offsets, idx, rho, radius, device):
+        self.event, self.block, self.k, self.radius = event, block, k, radius
+        self.nblk = (event[1] // block[0]) * (event[2] // block[1])
+        self.offsets_host, self.idx_host, self.rho_host = offsets, idx, rho
+        self.device = torch.device(device)
+        self.offsets = torch.from_numpy(offsets).to(self.device)
+        self.idx = torch.from_numpy(idx).to(self.device) if idx.size else torch.zeros(1, dtype=torch.int32, device=self.device)
+        self.rho = torch.from_numpy(rho).to(self.device) if rho.size else torch.zeros(1, dtype=torch.float32, device=self.device)
+        self._scratch = {}
+
+    @property
+    def d(self) -> int:
+        return self.event[0] * self.event[1] * self.event[2]
+
+    def scratch(self, m: int):
+        if m not in self._scratch:
+            self._scratch = {m: (torch.empty(self.k, 2 * m, device=self.device, dtype=torch.float32),
+                                 torch.empty(self.nblk * m * m, device=self.device, dtype=torch.float64))}
+        return self._scratch[m]
+
+
+def enkl_plan(event, positions, radius: float, block, *, device=None) -> EnklPlan:
+    """The localisation plan of a run (include/sda_hip.h), built in float64 on the host and uploaded once.  ``event``: the state's
+    shape (C, Hg, Wg), or (n,) for a ring (= (1, 1, n)); ``positions``: (k, 2) real-valued (row, col) of the observed values in
+    their flattened order, (k,) on a ring; ``block``: (bh, bw), or an int on a ring; ``radius`` > 0 in grid points, the
+    Gaspari-Cohn weight vanishes at twice that; ``float('inf')`` gives all-ones weights.  ``device`` defaults to the current HIP
+    device."""
+    import numpy as np
+    event = tuple(int(e) for e in event)
+    ring = len(event) == 1
+    if ring:
+        event = (1, 1, event[0])
+        block = (1, int(block)) if not isinstance(block, (tuple, list)) else tuple(block)
+        if len(block) == 1:
+            block = (1, int(block[0]))
+    if len(event) != 3 or min(event) < 1:
+        raise _lib.SdaHipError(f'enkl_plan: event {event}, expected (C, Hg, Wg) or (n,)')
+    block = tuple(int(v) for v in block) if isinstance(block, (tuple, list)) else None
+    if block is None or len(block) != 2 or min(block) < 1 or event[1] % block[0] or event[2] % block[1]:
+        raise _lib.SdaHipError(f'enkl_plan: block {block} does not divide the grid {event[1:]}')
+    if not radius > 0:
+        raise _lib.SdaHipError(f'enkl_plan: radius {radius}, expected > 0')
+    pos = positions.detach().cpu().numpy() if isinstance(positions, Tensor) else np.asarray(positions)
+    pos = pos.astype(np.float64)
+    if ring and pos.ndim == 1:
+        pos = np.stack([np.zeros_like(pos), pos], axis=1)
+    if pos.ndim != 2 or pos.shape[1] != 2 or pos.shape[0] < 1 or not np.isfinite(pos).all():
+        raise _lib.SdaHipError(f'enkl_plan: positions of shape {tuple(np.shape(positions))}, expected (k, 2)' +
+                               (' or (k,) on a ring' if ring else ''))
+    C, Hg, Wg = event
+    bh, bw = block
+    cr = np.arange(Hg // bh, dtype=np.float64) * bh + (bh - 1) / 2.0
+    cc = np.arange(Wg // bw, dtype=np.float64) * bw + (bw - 1) / 2.0
+    dr = np.abs(cr[:, None] - pos[None, :, 0]) % Hg
+    dc = np.abs(cc[:, None] - pos[None, :, 1]) % Wg
+    dr, dc = np.minimum(dr, Hg - dr), np.minimum(dc, Wg - dc)
+    dist = np.sqrt(dr[:, None, :] ** 2 + dc[None, :, :] ** 2).reshape(-1, pos.shape[0])          # (nblk, k)
+    rho = gaspari_cohn(dist / radius).astype(np.float32)
+    keep = rho > 0
+    offsets = np.zeros(dist.shape[0] + 1, np.int64)
+    np.cumsum(keep.sum(axis=1), out=offsets[1:])
+    if offsets[-1] > 0x7fffffff:
+        raise _lib.SdaHipError(f'enkl_plan: {int(offsets[-1])} list entries (at most 2^31 - 1 are served)')
+    idx = np.nonzero(keep)[1].astype(np.int32)
+    if device is None:
+        device = torch.device('cuda', torch.cuda.current_device())
+    return EnklPlan(event, block, pos.shape[0], offsets.astype(np.int32), idx, np.ascontiguousarray(rho[keep]), float(radius), device)
+
+
+def enkl_weights(plan: EnklPlan, Y: Tensor, D: Tensor, sigma: float, *, W: Optional[Tensor] = None, status: Optional[Tensor] = None):
+    """Per block ``W`` (nblk, m, m) fp32 and ``status`` (nblk,) int32 (1: no Cholesky factor or a non-finite W[b]; W[b] is then zero)
+    from ``enkw_prepare``'s Y, D (members, k): two launches (the pack and one workgroup per block), nothing read back."""
+    _dev(Y, D)
+    if Y.dim() != 2 or Y.shape != D.shape or not Y.is_contiguous() or not D.is_contiguous() or Y.shape[1] != plan.k:
+        raise _lib.SdaHipError(f'enkl_weights: Y {tuple(Y.shape)} and D {tuple(D.shape)}, expected contiguous (members, {plan.k})')
+    if Y.device != plan.device:
+        raise _lib.SdaHipError(f'enkl_weights: Y on {Y.device}, the plan on {plan.device}')
+    m, k = Y.shape
+    if not 2 <= m <= ENKW_MAX_M:
+        _lib.check(-2, 'sda_enkl_weights')
+    if W is None:
+        W = torch.empty(plan.nblk, m, m, device=Y.device, dtype=torch.float32)
+    _dev(W)
+    if tuple(W.shape) != (plan.nblk, m, m) or not W.is_contiguous():
+        raise _lib.SdaHipError(f'enkl_weights: a contiguous ({plan.nblk}, {m}, {m}) fp32 device tensor expected for W')
+    status = torch.zeros(plan.nblk, device=Y.device, dtype=torch.int32) if status is None else status
+    if status.dtype != torch.int32 or tuple(status.shape) != (plan.nblk,) or not status.is_cuda or not status.is_contiguous():
+        raise _lib.SdaHipError(f'enkl_weights: status ({plan.nblk},) int32 contiguous on the device expected')
+    T, work = plan.scratch(m)
+    lib = _lib.load()
+    _lib.check(lib.sda_enkl_pack(Y.data_ptr(), D.data_ptr(), m, k, T.data_ptr(), _stream()), 'sda_enkl_pack')
+    _lib.check(lib.sda_enkl_weights(T.data_ptr(), m, k, plan.offsets.data_ptr(), plan.idx.data_ptr(), plan.rho.data_ptr(), plan.nblk,
+                                    float(sigma), work.data_ptr(), W.data_ptr(), status.data_ptr(), _stream()), 'sda_enkl_weights')
+    return W, status
+
+
+def enkl_transform(plan: EnklPlan, S: Tensor, lo: int, t: int, W: Tensor) -> Tensor:
+    """The localised update, in place on the slabs ``S[lo] .. S[t]`` of the time-major ensemble S (time, members, C Hg Wg) with
+    the per-block ``W`` (nblk, m, m), one launch.  Blocks with an empty list are not touched."""
+    _enks_slabs(S, 'enkl_transform')
+    if not 0 <= lo <= t < S.shape[0]:
+        raise _lib.SdaHipError(f'enkl_transform: window {lo} .. {t} of {S.shape[0]} slabs')
+    m, d = S.shape[1], S.shape[2]
+    _dev(W)
+    if d != plan.d or tuple(W.shape) != (plan.nblk, m, m) or not W.is_contiguous() or S.device != plan.device:
+        raise _lib.SdaHipError(f'enkl_transform: slabs {tuple(S.shape)} and W {tuple(W.shape)} for a plan of {plan.nblk} blocks on '
+                               f'{plan.event}, expected (time, m, {plan.d}) and contiguous ({plan.nblk}, m, m)')
+    C, Hg, Wg = plan.event
+    _lib.check(_lib.load().sda_enkl_transform(S[lo].data_ptr(), S.stride(0), S.stride(1), t - lo + 1, m, C, Hg, Wg, plan.block[0],
+                                              plan.block[1], plan.offsets.data_ptr(), W.data_ptr(), _stream()), 'sda_enkl_transform')
+    return S
+
+
+def enkl_check(status: Tensor) -> None:
+    """Raise if a block of any analysis had no Cholesky factor or a non-finite transform; status (N, nblk)."""
+    bad = status.nonzero().tolist()
+    if bad:
+        raise _lib.SdaHipError(f'localised ensemble Kalman smoother: {len(bad)} block solve(s) failed, the first at (observation, '
+                               f'block) {tuple(bad[0])}')
+
+
 # ---------------------------------------------------------------- Kolmogorov flow (csrc/kflow.hip)
 _KFLOW_CONST = {}
 _KFLOW_SOLVE = {}
