@@ -163,6 +163,11 @@ int sda_conv_parity4(const sda_conv_desc* d, void* stream);
  * per stage), 3 = the single-round-trip small 1-D kernel, 4 = the 3 x 3 kernel for <= 16 output channels; <0 error.
  * (1 was the first-generation Winograd kernel: retired, never returned.) */
 int sda_conv_igemm_path(const sda_conv_desc* d);
+/* positions per workgroup (16, 32 or 64) of the small 1-D kernel's launch where sda_conv_igemm_path(d) is 3: 16 while
+ * n * ceil(wo / 16) <= 1024, else 32 while n * ceil(wo / 32) <= 1024, else 64 (SDA_SMALL1D_TP=16|32|64 in the environment forces
+ * one); 0 where that kernel does not take the launch (more than 4096 workgroups among the reasons); SDA_E_BADARG for ln_mean
+ * without ln_rstd.  Host only, nothing is launched; x, w, out and the ln_* pointers are tested for NULL, never dereferenced. */
+int sda_small1d_tile(const sda_conv_desc* d);
 /* bytes of dynamic LDS the launch would use (or <0 error), for planning / tests */
 int64_t sda_conv_igemm_lds_bytes(const sda_conv_desc* d);
 

@@ -337,6 +337,7 @@ SIGNATURES = {
                                      c_int64, c_void_p]),
     'sda_conv_parity4': (c_int, [POINTER(ConvDesc), c_void_p]),
     'sda_conv_igemm_path': (c_int, [POINTER(ConvDesc)]),
+    'sda_small1d_tile': (c_int, [POINTER(ConvDesc)]),
     'sda_conv_wgrad': (c_int, [POINTER(WgradDesc), c_void_p]),
     'sda_conv_wgrad_slabs': (c_int, [POINTER(WgradDesc)]),
     'sda_conv_wgrad_work_floats': (c_int64, [POINTER(WgradDesc)]),

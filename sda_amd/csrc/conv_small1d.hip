@@ -165,6 +165,7 @@ __global__ __launch_bounds__(256) void conv_small1d_kernel(const sda_conv_desc d
 // eligibility + tile length (16 / 32 / 64 positions); 0 -> the launch is served by the general kernels, < 0 -> bad descriptor
 static int small1d_plan(const sda_conv_desc* d) {
     static const bool off = getenv("SDA_CONV_SMALL1D") && atoi(getenv("SDA_CONV_SMALL1D")) == 0;
+    static const int forced = getenv("SDA_SMALL1D_TP") ? atoi(getenv("SDA_SMALL1D_TP")) : 0;      // 16 / 32 / 64: that tile (A/B runs, tests)
     if (off || !d) return 0;
     if (d->kh != 1 || d->kw != 3 || d->stride_h != 1 || d->stride_w != 1 || d->hs != 1 || d->ho != 1 || d->up_h != 1 || d->up_w != 1 ||
         d->zins_h != 1 || d->zins_w != 1 || d->cctx != 0 || d->explicit_pad || d->out_sn || d->out_sc || d->out_sy || d->out_sx)
@@ -174,11 +175,16 @@ static int small1d_plan(const sda_conv_desc* d) {
         return 0;
     if ((d->ln_mean == nullptr) != (d->ln_rstd == nullptr)) return SDA_E_BADARG;
     // 64-position tiles for batches that fill the chip, smaller ones otherwise (see block1d.hip)
-    const int tp = (int64_t)d->n * ((d->wo + 15) / 16) <= 1024 ? 16 : ((int64_t)d->n * ((d->wo + 31) / 32) <= 1024 ? 32 : 64);
+    int tp = (int64_t)d->n * ((d->wo + 15) / 16) <= 1024 ? 16 : ((int64_t)d->n * ((d->wo + 31) / 32) <= 1024 ? 32 : 64);
+    if (forced == 16 || forced == 32 || forced == 64) tp = forced;
     // this kernel is for launches that cannot fill the chip with the staged kernel's tiles; big batches stay there
     if ((int64_t)d->n * ((d->wo + tp - 1) / tp) > 4096) return 0;
     return tp;
 }
+
+// positions per workgroup (16 / 32 / 64) of the conv_small1d_kernel launch that serves `d`, 0 where the general kernels serve it,
+// < 0 for a bad descriptor: host only, no launch; the pointer fields are tested for NULL, never dereferenced
+extern "C" int sda_small1d_tile(const sda_conv_desc* d) { return small1d_plan(d); }
 
 // would sda_conv_igemm serve this launch with conv_small1d_kernel?  (sda_conv_igemm_path)
 int sda_small1d_path(const sda_conv_desc* d) { return small1d_plan(d) > 0; }

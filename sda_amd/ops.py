@@ -321,6 +321,15 @@ def conv_path(desc: ConvDesc) -> int:
     return _lib.load().sda_conv_igemm_path(ctypes.byref(desc))
 
 
+def small1d_tile(desc: ConvDesc) -> int:
+    """Positions per workgroup (16, 32 or 64) of the small 1-D kernel's launch serving ``desc``; 0 where the general kernels serve
+    it (host only: nothing is launched, no pointer is followed)."""
+    tile = _lib.load().sda_small1d_tile(ctypes.byref(desc))
+    if tile < 0:
+        _lib.check(tile, 'sda_small1d_tile')
+    return tile
+
+
 def pack_conv_weight(w: Tensor, cout: int, cin: int, kh: int, kw: int, transpose: bool, keep: int, dst: Tensor,
                      k_pad: int, m_pad: int):
     _lib.check(_lib.load().sda_pack_conv_weight(w.data_ptr(), cout, cin, kh, kw, int(transpose), keep, dst.data_ptr(),

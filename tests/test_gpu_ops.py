@@ -507,7 +507,8 @@ def test_gauss_cotangent_matches_torch(dev):
 @pytest.mark.gpu
 def test_small_1d_conv_kernel_serves_the_lorenz_shapes(dev):
     """conv_small1d (one round trip per launch) against torch on the layer shapes of the Lorenz nets, every fusion on, both
-    paddings, lengths that are not multiples of the tile; SDA_CONV_SMALL1D=0 is the staged kernel (compared too)."""
+    paddings, lengths that are not multiples of the tile.  All five shapes run on the 16-position instance; the other instances, each
+    fusion alone, the source views and the comparison with the staged kernel (SDA_CONV_SMALL1D=0) are in tests/test_gpu_small1d.py."""
     import torch.nn.functional as F
     from sda_amd._lib import ACT_IDS
     torch.manual_seed(5)
